@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: Mpix/s segmented (Gabor bank + k-means) on synthetic 481x321x3 batches.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints the headline figure. `--full` adds everything else this script
+measures: per-kernel HIP events in the timed region with the roofline figures built on them, the other codebook mode,
+the two-slab placement, the host paths, BASELINE configs 4 and 5, the scoring rate, the CPU baseline and the label check
+against the C oracle. `--dump-outputs DIR` writes the label maps of the last timed step to DIR as float32 .npy files.
 
 N > 1 is launched by the driver as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
@@ -233,13 +238,21 @@ def main():
     ap.add_argument("--n-iter", type=int, default=10)
     ap.add_argument("--k", type=int, default=8)
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for dry runs)")
-    ap.add_argument("--no-other-mode", action="store_true", help="skip timing the other codebook mode")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-check", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also per-kernel events and roofline figures, the other codebook mode, the two-slab placement, the "
+                         "host paths, BASELINE configs 4 and 5, the scoring rate, the CPU baseline and the label check")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the label maps of the last timed step as DIR/labels.npy (float32; DIR/labels_rank<r>.npy "
+                         "per rank when N > 1), at most 64 MB in all: the first images of each shard if more")
+    ap.add_argument("--no-other-mode", action="store_true", help="with --full: skip timing the other codebook mode")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-check", action="store_true", help="with --full: skip the label check against the C oracle")
     ap.add_argument("--spinup-steps", type=int, default=15, help="device clock spin-up before the warm-up steps (0 = none)")
-    ap.add_argument("--no-host-path", action="store_true", help="skip the host-array-in / host-array-out timing")
-    ap.add_argument("--no-events", action="store_true", help="diagnostic: no per-kernel HIP events in the timed region")
+    ap.add_argument("--no-host-path", action="store_true", help="with --full: skip the host-array-in / host-array-out timing")
+    ap.add_argument("--no-events", action="store_true", help="with --full, diagnostic: no per-kernel HIP events in the timed region")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -313,15 +326,24 @@ def main():
     for _ in range(args.spinup_steps):       # a fixed count: every rank must issue the same collectives
         step(args.mode)
     torch.cuda.synchronize(dev)
-    dt = timed(args.mode, args.steps, args.warmup, events=not args.no_events)
+    dt = timed(args.mode, args.steps, args.warmup, events=args.full and not args.no_events)
     total_px = world * B * H * W
     value = total_px * args.steps / dt / 1e6
     slab_ms = []                                    # pass times of the two candidate slabs (extra run below)
 
-    # per-kernel device time from the events recorded inside the timed region (rank 0's GPU)
+    if args.dump_outputs:
+        # what segment_device handed back in the last timed step (`out`, before any extra run reuses it); labels 0..k-1 are
+        # exact in float32. Over the 64 MB budget only the first images of every shard are written (the same ones each run).
+        keep = min(B, int(64e6 // world) // (H * W * 4))
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        name = "labels.npy" if world == 1 else f"labels_rank{rank}.npy"
+        np.save(os.path.join(args.dump_outputs, name), out[:keep].cpu().numpy().astype(np.float32))
+        log(f"rank {rank}: wrote {name} ({keep} of {B} images) to {args.dump_outputs}")
+
     bank = seg.bank
     D = bank.n_features
     px = B * H * W
+    # per-kernel device time from the events recorded inside the timed region (rank 0's GPU; --full only, NaN otherwise)
     g_ms, g_n = tops.mean_ms("gabor")
     a_ms, a_n = tops.mean_ms("assign")
     # Algorithmic bytes. The slab keeps pyramid level L at 1/4^L of the pixels (SPEC.md §3), so the
@@ -339,75 +361,77 @@ def main():
     pass_b = feat_b * (0.75 if split else 1.0)
     a_bytes = (pass_b + 4 / args.n_iter) * px        # per Lloyd pass: pyramid features in; the int32 raster label map is stored by the last pass only
     a_bytes_u16 = (feat_b + 4 / args.n_iter) * px    # the rounds 2-5 definition (every value read at 16 bits)
-    g_ops = sum(2 * bank.ksize ** 2 * (4 * d // 3) * 3 * px / q for d, q in lv)   # int8 MACs x2: 2 digits x {re,im} x F_L rows
-    kernels = {
-        "gabor_mfma_kernel": dict(launches=g_n, launches_per_step=1, avg_ms=round(g_ms, 4), alg_bytes=int(g_bytes),
-                                  unfused_def_bytes=(3 + 2 * D) * px, alg_ops=int(g_ops),
-                                  gbs=round(g_bytes / g_ms / 1e6, 1), tops=round(g_ops / g_ms / 1e9, 1),
-                                  hbm_frac=round(g_bytes / g_ms / 1e6 / HBM_PEAK_GBS, 4),
-                                  mfma_frac=round(g_ops / g_ms / 1e9 / I8_MFMA_PEAK_TOPS, 4),
-                                  note="whole gcs_gabor_features call: pad / pyramid kernels + one MFMA launch per level"),
-        "kmeans_pass_mfma_kernel": dict(launches=a_n, launches_per_step=args.n_iter, avg_ms=round(a_ms, 4),
-                                     alg_bytes=int(a_bytes), unfused_def_bytes=(2 * D + 1) * px,
-                                     gbs=round(a_bytes / a_ms / 1e6, 1),
-                                     hbm_frac=round(a_bytes / a_ms / 1e6 / HBM_PEAK_GBS, 4),
-                                     alg_bytes_u16_def=int(a_bytes_u16),
-                                     hbm_frac_u16_def=round(a_bytes_u16 / a_ms / 1e6 / HBM_PEAK_GBS, 4)),
-    }
-    if g_ms >= a_ms * args.n_iter:    # dominant = larger share of the step (`launches` = launches bracketed by events)
-        kg = kernels["gabor_mfma_kernel"]
-        # arithmetic intensity 60 840 op / 93 B = 654 op/B is above the int8 ridge (5 POP/s / 8 TB/s =
-        # 625 op/B): the MFMA roof bounds this kernel; the HBM fraction is reported next to it.
-        roofline = dict(kernel="gabor_mfma_kernel", bound="mfma", achieved=kg["tops"], peak=I8_MFMA_PEAK_TOPS,
-                        unit="TFLOP/s", frac=kg["mfma_frac"], traffic=None, ops="int8 MAC x2 (TOP/s)",
-                        hbm_gbs=kg["gbs"], hbm_frac=kg["hbm_frac"])
-    else:
-        ka = kernels["kmeans_pass_mfma_kernel"]
-        roofline = dict(kernel="kmeans_pass_mfma_kernel", bound="hbm", achieved=ka["gbs"], peak=HBM_PEAK_GBS,
-                        unit="GB/s", frac=ka["hbm_frac"], traffic=None,
-                        alg_bytes_def=("split slab (ABI 18): 1.5*sum_L D_L/4^L B/px (12 of the 16 bits of every value; the last 4 only "
-                                       "for flagged tiles, ~0 here) + the label map stored by the last pass (4 B/px int32 / n_iter) = "
-                                       "67.9 B/px per launch for the 4x6 bank, n_iter 10; frac_u16_def prices the same launch at the "
-                                       "rounds 2-5 definition (90.4 B/px: bytes this pass no longer reads)" if split else
-                                       "pyramid-resident: 2*sum_L D_L/4^L B/px read by every pass + the label map stored by the "
-                                       "last one (4 B/px int32 / n_iter)"),
-                        frac_u16_def=ka["hbm_frac_u16_def"])
-        # the same fraction from the committed rocprofv3 --kernel-trace --stats summary of this command (tools/profile_round.sh):
-        # the dominant kernel's average over ALL its launches, spin-up included
+    kernels = roofline = None                        # per-kernel and roofline figures: --full only
+    if args.full:
+        g_ops = sum(2 * bank.ksize ** 2 * (4 * d // 3) * 3 * px / q for d, q in lv)   # int8 MACs x2: 2 digits x {re,im} x F_L rows
+        kernels = {
+            "gabor_mfma_kernel": dict(launches=g_n, launches_per_step=1, avg_ms=round(g_ms, 4), alg_bytes=int(g_bytes),
+                                      unfused_def_bytes=(3 + 2 * D) * px, alg_ops=int(g_ops),
+                                      gbs=round(g_bytes / g_ms / 1e6, 1), tops=round(g_ops / g_ms / 1e9, 1),
+                                      hbm_frac=round(g_bytes / g_ms / 1e6 / HBM_PEAK_GBS, 4),
+                                      mfma_frac=round(g_ops / g_ms / 1e9 / I8_MFMA_PEAK_TOPS, 4),
+                                      note="whole gcs_gabor_features call: pad / pyramid kernels + one MFMA launch per level"),
+            "kmeans_pass_mfma_kernel": dict(launches=a_n, launches_per_step=args.n_iter, avg_ms=round(a_ms, 4),
+                                         alg_bytes=int(a_bytes), unfused_def_bytes=(2 * D + 1) * px,
+                                         gbs=round(a_bytes / a_ms / 1e6, 1),
+                                         hbm_frac=round(a_bytes / a_ms / 1e6 / HBM_PEAK_GBS, 4),
+                                         alg_bytes_u16_def=int(a_bytes_u16),
+                                         hbm_frac_u16_def=round(a_bytes_u16 / a_ms / 1e6 / HBM_PEAK_GBS, 4)),
+        }
+        if g_ms >= a_ms * args.n_iter:    # dominant = larger share of the step (`launches` = launches bracketed by events)
+            kg = kernels["gabor_mfma_kernel"]
+            # arithmetic intensity 60 840 op / 93 B = 654 op/B is above the int8 ridge (5 POP/s / 8 TB/s =
+            # 625 op/B): the MFMA roof bounds this kernel; the HBM fraction is reported next to it.
+            roofline = dict(kernel="gabor_mfma_kernel", bound="mfma", achieved=kg["tops"], peak=I8_MFMA_PEAK_TOPS,
+                            unit="TFLOP/s", frac=kg["mfma_frac"], traffic=None, ops="int8 MAC x2 (TOP/s)",
+                            hbm_gbs=kg["gbs"], hbm_frac=kg["hbm_frac"])
+        else:
+            ka = kernels["kmeans_pass_mfma_kernel"]
+            roofline = dict(kernel="kmeans_pass_mfma_kernel", bound="hbm", achieved=ka["gbs"], peak=HBM_PEAK_GBS,
+                            unit="GB/s", frac=ka["hbm_frac"], traffic=None,
+                            alg_bytes_def=("split slab (ABI 18): 1.5*sum_L D_L/4^L B/px (12 of the 16 bits of every value; the last 4 only "
+                                           "for flagged tiles, ~0 here) + the label map stored by the last pass (4 B/px int32 / n_iter) = "
+                                           "67.9 B/px per launch for the 4x6 bank, n_iter 10; frac_u16_def prices the same launch at the "
+                                           "rounds 2-5 definition (90.4 B/px: bytes this pass no longer reads)" if split else
+                                           "pyramid-resident: 2*sum_L D_L/4^L B/px read by every pass + the label map stored by the "
+                                           "last one (4 B/px int32 / n_iter)"),
+                            frac_u16_def=ka["hbm_frac_u16_def"])
+            # the same fraction from the committed rocprofv3 --kernel-trace --stats summary of this command (tools/profile_round.sh):
+            # the dominant kernel's average over ALL its launches, spin-up included
+            try:
+                import csv
+                rows = list(csv.DictReader(open(os.path.join(ROOT, "profiles", "kernel_stats_latest.csv"))))
+                row = max((r for r in rows if "kmeans_pass_mfma_kernel" in r["Name"]), key=lambda r: float(r["TotalDurationNs"]))
+                roofline["frac_rocprof"] = round(a_bytes / (float(row["AverageNs"]) * 1e-9) / 1e9 / HBM_PEAK_GBS, 4)
+                roofline["rocprof_avg_us"] = round(float(row["AverageNs"]) / 1e3, 2)
+                roofline["rocprof_source"] = "profiles/kernel_stats_latest.csv (%s launches of %s)" % (row["Calls"], row["Name"].split("(")[0])
+            except Exception:
+                pass
+
+        # HBM bytes per launch of the dominant kernel from the committed rocprofv3 --pmc summary of this same
+        # command (tools/profile_round.sh; FETCH_SIZE doubled per MI355X_MICROARCH.md). None if no profile matches.
         try:
-            import csv
-            rows = list(csv.DictReader(open(os.path.join(ROOT, "profiles", "kernel_stats_latest.csv"))))
-            row = max((r for r in rows if "kmeans_pass_mfma_kernel" in r["Name"]), key=lambda r: float(r["TotalDurationNs"]))
-            roofline["frac_rocprof"] = round(a_bytes / (float(row["AverageNs"]) * 1e-9) / 1e9 / HBM_PEAK_GBS, 4)
-            roofline["rocprof_avg_us"] = round(float(row["AverageNs"]) / 1e3, 2)
-            roofline["rocprof_source"] = "profiles/kernel_stats_latest.csv (%s launches of %s)" % (row["Calls"], row["Name"].split("(")[0])
+            prof = json.load(open(os.path.join(ROOT, "profiles", "hbm_traffic_latest.json")))
+            cand = [e for e in prof.get(roofline["kernel"], []) if e["launches"] > 0]
+            if roofline["kernel"] == "gabor_mfma_kernel":
+                big = max(e["grid_threads"] for e in cand)
+                roofline["traffic"] = sum(e["hbm_bytes_corrected"] for e in cand if e["grid_threads"] == big) + \
+                    sum(e["hbm_bytes_corrected"] for e in prof.get("gabor_plane_kernel", []))
+            else:
+                roofline["traffic"] = max(cand, key=lambda e: e["grid_threads"])["hbm_bytes_corrected"]
+            roofline["traffic_source"] = "profiles/hbm_traffic_latest.json (separate rocprofv3 --pmc run, batch %d)" % PER_GPU
         except Exception:
             pass
 
-    # HBM bytes per launch of the dominant kernel from the committed rocprofv3 --pmc summary of this same
-    # command (tools/profile_round.sh; FETCH_SIZE doubled per MI355X_MICROARCH.md). None if no profile matches.
-    try:
-        prof = json.load(open(os.path.join(ROOT, "profiles", "hbm_traffic_latest.json")))
-        cand = [e for e in prof.get(roofline["kernel"], []) if e["launches"] > 0]
-        if roofline["kernel"] == "gabor_mfma_kernel":
-            big = max(e["grid_threads"] for e in cand)
-            roofline["traffic"] = sum(e["hbm_bytes_corrected"] for e in cand if e["grid_threads"] == big) + \
-                sum(e["hbm_bytes_corrected"] for e in prof.get("gabor_plane_kernel", []))
-        else:
-            roofline["traffic"] = max(cand, key=lambda e: e["grid_threads"])["hbm_bytes_corrected"]
-        roofline["traffic_source"] = "profiles/hbm_traffic_latest.json (separate rocprofv3 --pmc run, batch %d)" % PER_GPU
-    except Exception:
-        pass
-
     extra = {}
     other = "per_image" if args.mode == "global" else "global"
-    if world == 1 and not args.no_other_mode:
+    if args.full and world == 1 and not args.no_other_mode:
         # the other codebook mode (per_image = the reference's own semantics, script.py:22-38), same batch, same clock
         log(f"timing the {other} codebook mode")
         dt2 = timed(other, max(2, args.steps // 2), 2, events=False)
         extra[f"{other}_mpix_s"] = round(px * max(2, args.steps // 2) / dt2 / 1e6, 1)
 
-    if world == 1 and not args.no_other_mode:
+    if args.full and world == 1 and not args.no_other_mode:
         # what a placement search over two slab allocations would give (Segmenter(slab_candidates=2), off in the library):
         # the same step on the better of two candidate slabs; never `value`
         log("timing the best of two slab allocations")
@@ -425,7 +449,7 @@ def main():
         slab_ms = list(seg2.slab_placement_ms or [])
         del seg2, out2
 
-    if world == 1 and not args.no_host_path:
+    if args.full and world == 1 and not args.no_host_path:
         # the slot as the reference calls it (script.py:25,30): host uint8 array in, host label array out, PCIe both
         # ways. Reported beside `value`, never as `value`.
         cores_, _, _ = usable_cores()
@@ -476,7 +500,7 @@ def main():
             seg(one)
         extra["single_image_latency_ms"] = round((time.perf_counter() - t0) / 20 * 1e3, 3)
 
-    if world == 1 and not args.no_other_mode:
+    if args.full and world == 1 and not args.no_other_mode:
         # BASELINE config 4 (8-scale x 8-orientation bank, D = 192, four pyramid levels) on the same batch: a parity-test
         # configuration, reported beside `value` for the record (never `value`)
         log("timing BASELINE config 4 (8x8 bank)")
@@ -492,7 +516,7 @@ def main():
         extra["config4_8x8_bank_mpix_s"] = round(px * n4 / (time.perf_counter() - t0) / 1e6, 1)
         del seg4
 
-    if world == 1 and not args.no_other_mode:
+    if args.full and world == 1 and not args.no_other_mode:
         # BASELINE config 5's tile: ONE 2048 x 2048 x 3 image on one GPU, unsharded (the row-sharded form over N ranks is
         # tests/test_distributed.py; its cross-rank halo is halo_rows * 2048 * 3 bytes per interior edge and image)
         log("timing BASELINE config 5 (one 2048x2048 tile, unsharded)")
@@ -511,7 +535,7 @@ def main():
         extra["config5_halo_bytes_per_edge"] = halo_rows(bank.n_levels, bank.ksize) * 2048 * 3
         del big, out5
 
-    if world == 1 and not args.no_other_mode:
+    if args.full and world == 1 and not args.no_other_mode:
         # the batched GPU scorer on the 24 packed BSD500 val images (device-resident label maps, ground truth
         # from the 500-id pack) and the segment + score loop of examples/bsd_eval.py --val; images per second, never `value`
         try:
@@ -523,7 +547,7 @@ def main():
             extra["scoring"] = {"skipped": repr(e)}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         ref, cpu = cpu_baseline(B, args.k, args.n_iter, args.mode)
         if not args.no_check:
             # parity of the timed configuration itself: every label of the whole batch, timed mode, vs the C oracle

@@ -93,19 +93,38 @@ def test_packed_groundtruth_reader():
     assert all(s.shape == (481, 321) for s in segs)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/BSD_metrics/data/truth"), reason="reference data not mounted")
-def test_mat_loader_mirror_matches_the_fixture():
-    """groundtruth.get_segment_from_filename mirror on the reference's own .mat files (this container only)."""
+@pytest.fixture(scope="module")
+def mat_truth(tmp_path_factory):
+    """A BSD500-style truth tree (<split>/<id>.mat, a 1 x n cell `groundTruth` of structs with fields `Segmentation`
+    uint16 and `Boundaries` uint8, as the data set ships it) written from the annotator maps of bsd_inputs.npz, one id per
+    split directory plus an empty one, so that the loader has to scan them all. Returns the tree's path with a slash."""
+    from scipy.io import savemat
+    root = tmp_path_factory.mktemp("truth")
+    for split, i in (("train", "100080"), ("test", "100075"), ("val", "100098"), ("empty", None)):
+        os.makedirs(root / split)
+        if i is None:
+            continue
+        cell = np.empty((1, int(INP["nseg_" + i])), dtype=object)
+        for a in range(cell.shape[1]):
+            seg = INP["seg_%s_%d" % (i, a)]
+            cell[0, a] = {"Segmentation": seg.astype(np.uint16), "Boundaries": find_boundaries(seg).astype(np.uint8)}
+        savemat(str(root / split / (i + ".mat")), {"groundTruth": cell}, do_compression=True)
+    return str(root) + "/"
+
+
+def test_mat_loader_mirror_matches_the_fixture(mat_truth):
+    """groundtruth.get_segment_from_filename mirror on .mat files of the data set's layout."""
     from gabor_color_image_segmentation_amd.groundtruth import get_segment_from_filename
-    segs = get_segment_from_filename("100080", path="/root/reference/BSD_metrics/data/truth/")
+    segs = get_segment_from_filename("100080", path=mat_truth)
     assert len(segs) == int(INP["nseg_100080"])
     for a, s in enumerate(segs):
-        assert np.array_equal(s, INP["seg_100080_%d" % a])
+        assert s.dtype == np.uint16 and np.array_equal(s, INP["seg_100080_%d" % a])
+    assert get_segment_from_filename("999999", path=mat_truth) == []
 
 
-def test_whole_dataset_truth_pack_matches_the_fixtures_and_the_mat_loader():
+def test_whole_dataset_truth_pack_matches_the_fixtures_and_the_mat_loader(mat_truth):
     """tests/golden/bsd500_truth.npz (tools/pack_bsd_truth.py: the reference's own loader over all 500 ids) holds the same
-    maps as the per-image fixtures, and as the .mat mirror where the reference tree is present."""
+    maps as the per-image fixtures, and as the .mat mirror reads them back from the data set's file layout."""
     from gabor_color_image_segmentation_amd.groundtruth import PackedTruth, get_segment_from_filename
     pt = PackedTruth(os.path.join(GOLD, "bsd500_truth.npz"))
     assert len(pt) == 500 and int(pt.first[-1]) == 2696
@@ -122,8 +141,6 @@ def test_whole_dataset_truth_pack_matches_the_fixtures_and_the_mat_loader():
     assert img_of.tolist() == [0] * first[1] + [1] * (truth.shape[0] - first[1]) and n_truth[0] == int(truth[0].max()) + 1
     with pytest.raises(ValueError):
         pt.stack(["100075", "100080"])                     # landscape + portrait
-    ref = "/root/reference/BSD_metrics/data/truth/"
-    if os.path.isdir(ref):
-        for i in ("2092", "97010", "100080"):
-            want = get_segment_from_filename(i, ref)
-            assert len(want) == len(pt[i]) and all(np.array_equal(x, y) for x, y in zip(want, pt[i]))
+    for i in ("100075", "100080", "100098"):
+        want = get_segment_from_filename(i, mat_truth)
+        assert len(want) == len(pt[i]) and all(np.array_equal(x, y) for x, y in zip(want, pt[i]))

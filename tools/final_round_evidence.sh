@@ -12,7 +12,7 @@ cd $R
 timeout -k 10 400 python -m pytest tests -m gpu -x -q > $O/${TAG}_final_tests.log 2>&1
 rc=$?; tail -2 $O/${TAG}_final_tests.log
 if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "tests killed (rc=$rc): no further GPU step"; exit $rc; fi
-timeout -k 10 200 python bench.py --steps 20 --warmup 5 > $P/${TAG}_bench_final.json 2> $O/${TAG}_final_bench.err || { echo "bench failed"; exit 1; }
+timeout -k 10 200 python bench.py --steps 20 --warmup 5 --full > $P/${TAG}_bench_final.json 2> $O/${TAG}_final_bench.err || { echo "bench failed"; exit 1; }
 timeout -k 10 300 bash tools/profile_round.sh $TAG > $O/${TAG}_final_prof.log 2>&1 || { echo "profile_round failed"; exit 1; }
 timeout -k 10 300 bash tools/profile_config4.sh $TAG > $O/${TAG}_final_prof_c4.log 2>&1 || { echo "profile_config4 failed"; exit 1; }
 timeout -k 10 300 bash tools/pmc_gabor.sh $TAG > $P/${TAG}_pmc.txt 2> $O/${TAG}_final_pmc.err || { echo "pmc failed"; exit 1; }

@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/prof_$TAG
 rm -rf "$OUT"     # (gpurun merges gpurun_out/ across calls: never mix two runs' counter files)
 mkdir -p $OUT $R/gpurun_out/profiles
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-host-path --no-other-mode > $OUT/bench_trace.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-host-path --no-other-mode > $OUT/bench_trace.log 2>&1
 grep '"metric"' $OUT/bench_trace.log > $R/gpurun_out/profiles/${TAG}_bench_under_rocprof.json || true
 cp $OUT/trace/*/*kernel_stats.csv $R/gpurun_out/profiles/${TAG}_kernel_stats.csv
 cp $R/gpurun_out/profiles/${TAG}_kernel_stats.csv $R/gpurun_out/profiles/kernel_stats_latest.csv   # bench.py: roofline.frac_rocprof
