@@ -10,6 +10,8 @@ tables and the same numbers are printed (evaluate_gpu.all_scores_device).
 `--val`: the data-set form of the same loop on the 24 packed images of the BSD500 val split: batches per image shape through
 the device path, the batched GPU scorer against the packed ground truth of all 500 ids, mean recall / precision / F beside the
 numbers the reference's own metrics class gave for the same label maps (tests/golden/bsd_val_scores.json).
+`--val --agreement`: also the region metrics PRI / VoI / covering (SPEC.md §8) of the same maps, as segmented and as
+4-connected regions, with their means beside the scikit-learn / scikit-image numbers (tests/golden/region_agreement_golden.json).
 """
 import os
 import sys
@@ -21,7 +23,7 @@ from gabor_color_image_segmentation_amd import segment                      # no
 from gabor_color_image_segmentation_amd.evaluate import metrics             # noqa: E402  (script.py:14)
 from gabor_color_image_segmentation_amd.groundtruth import load_packed      # noqa: E402  (script.py:13)
 
-def val_split():
+def val_split(agreement=False):
     import json
     import numpy as np
     import torch
@@ -35,22 +37,38 @@ def val_split():
     seg = Segmenter()
     ids = [str(i) for i in pack["ids"]]
     rows = {}
+    agree = {"stored": {}, "connected": {}}
     for shape in sorted({pack["img_" + i].shape[:2] for i in ids}):
         group = [i for i in ids if pack["img_" + i].shape[:2] == shape]
         labels = seg.segment_device(torch.from_numpy(np.stack([pack["img_" + i] for i in group])).cuda())
         # ground truth resident on the device in the scorer's form (prepared once per shape group; a data-set loop keeps it)
-        for i, s in zip(group, all_scores_batch_device(labels, truth.to_device(group), n_segments=seg.k)):
+        dt = truth.to_device(group)
+        for i, s in zip(group, all_scores_batch_device(labels, dt, n_segments=seg.k, agreement=agreement)):
             rows[i] = s
+            if agreement:
+                agree["stored"][i] = s
             print("%-8s Regions: %d Recall: %.4f Precision: %.4f F-measure: %.4f   (reference class: %.4f)"
                   % (i, s["regions"], s["recall"], s["precision"], s["fmeasure"], ref[i]["v2"]["fmeasure"]))
+        if agreement:                                    # the same maps as connected regions (Segmenter(connectivity=True))
+            conn = Segmenter(connectivity=True).segment_device(
+                torch.from_numpy(np.stack([pack["img_" + i] for i in group])).cuda())
+            for i, s in zip(group, all_scores_batch_device(conn, dt, agreement=True)):
+                agree["connected"][i] = s
     for key in ("recall", "precision", "fmeasure"):
         print("mean %-9s %.4f   reference class on the same maps: %.4f" % (
             key, float(np.mean([rows[i][key] for i in ids])), float(np.mean([ref[i]["v2"][key] for i in ids]))))
+    if agreement:
+        gold_agr = json.load(open(os.path.join(gold, "region_agreement_golden.json")))
+        for kind in ("stored", "connected"):
+            for key, gkey in (("PRI", "PRI"), ("VoI", "VoI"), ("covering", "covering_mean")):
+                print("mean %-8s %-9s %.6f   scikit-learn / scikit-image on the same maps: %.6f" % (
+                    key, kind, float(np.mean([agree[kind][i][key] for i in ids])),
+                    float(np.mean([gold_agr["val/%s/%s" % (i, kind)][gkey] for i in ids]))))
 
 
 if __name__ == '__main__':
     if "--val" in sys.argv:
-        val_split()
+        val_split(agreement="--agreement" in sys.argv)
         sys.exit(0)
     data = load_packed(os.path.join(ROOT, "tests", "golden", "bsd_inputs.npz"))
     for name in sorted(data):

@@ -57,6 +57,8 @@ SIGNATURES = {
     "gcs_bit_planes_bytes": (_sz, [_i, _i, _i]),
     "gcs_truth_prepare": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "gcs_boundary_counts_resident": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "gcs_region_agreement_scratch_bytes": (_sz, [_i, _i, _i]),
+    "gcs_region_agreement": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "gcs_connected_scratch_bytes": (_sz, [_i, _i, _i]),
     "gcs_connected_regions": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
 }

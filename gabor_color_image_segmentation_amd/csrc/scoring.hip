@@ -677,3 +677,211 @@ extern "C" int gcs_score_batch_resident(const int32_t *labels, const void *truth
     GCS_CHECK_LAUNCH("gcs_score_batch_resident");
     return GCS_OK;
 }
+
+// ======================================================================= region agreement (SPEC.md §8)
+// PRI / VoI / covering of the BSDS500 benchmark are functions of the same contingency tables: per annotator map t,
+//   sums[t]  = { N = sum_j b_j, sum_i a_i^2, sum_j b_j^2, sum_ij n_ij^2 }                         (uint64, exact)
+//   terms[t] = { sum a log2 a, sum b log2 b, sum n log2 n, sum_j b_j * n*_j / u*_j }              (double)
+// with a_i / b_j the row / column sums of the table itself and n*_j / u*_j the largest n_ij / (a_i + b_j - n_ij) of column j.
+// ONE workgroup per map, 16 waves; wave w owns rows w, w + 16, ... (lanes across the columns), AG_ROWS of them per step with
+// their loads issued together (one row per step left a wave waiting on one load at a time). The columns go in chunks of
+// AG_CHUNK: per-wave column state [16][AG_CHUNK] in LDS (128 KiB of the CU's 160 KiB: the column sums in sweep 1, the best
+// (n, u) pair in sweep 2), combined in wave order at the end of each chunk. Sweep 1 also leaves the row sums a_i (one lane of the
+// owning wave, added up chunk by chunk) and the column sums b_j in the caller's scratch for sweep 2: every table element is read
+// twice at most, and rows above the image's largest label (seg_max) not at all.
+// Every float sum runs in an order fixed by the row / column INDEX alone (row mod 16 and its step, column mod 64 or mod 1024,
+// chunk), then a fixed shuffle tree and the waves in order: empty rows and columns (a table allocated at a capacity) add
+// nothing, so tables of the same maps at different shapes give the same bits. No float atomics.
+constexpr int AG_WAVES = 16, AG_THREADS = 64 * AG_WAVES, AG_CHUNK = 1024, AG_ROWS = 8;
+
+template <typename V>
+__device__ __forceinline__ V ag_wave_sum(V v) {
+    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
+    return v;
+}
+
+__global__ __launch_bounds__(AG_THREADS) void region_agreement_kernel(const unsigned *__restrict__ hist,
+                                                                      const int32_t *__restrict__ img_of,
+                                                                      const int32_t *__restrict__ seg_max, int n_seg,
+                                                                      int stride, unsigned *__restrict__ scratch,
+                                                                      unsigned long long *__restrict__ sums,
+                                                                      double *__restrict__ terms) {
+    __shared__ unsigned s_w[2][AG_WAVES][AG_CHUNK];            // sweep 1: [0] column sums; sweep 2: [0] best n, [1] best u
+    __shared__ unsigned s_b[AG_CHUNK];
+    __shared__ unsigned long long s_u[AG_WAVES][4];
+    __shared__ double s_d[AG_WAVES][4];
+    const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    static_assert(AG_ROWS <= 64, "one lane per row of a step");
+    int rows = n_seg;
+    if (seg_max) rows = min(n_seg, max(0, seg_max[img_of ? img_of[t] : 0] + 1));
+    const unsigned *h = hist + (size_t)t * n_seg * stride;
+    unsigned *a_s = scratch + (size_t)t * (n_seg + stride), *b_s = a_s + n_seg;
+    unsigned long long n_tot = 0, sa2 = 0, sb2 = 0, sn2 = 0;
+    double sal = 0.0, sbl = 0.0, snl = 0.0, cov = 0.0;
+
+    // ---- sweep 1: a_i, b_j, sum n^2, sum n log2 n
+    for (int c0 = 0; c0 < stride; c0 += AG_CHUNK) {
+        const int cw = min(AG_CHUNK, stride - c0);
+        const bool last = c0 + AG_CHUNK >= stride;
+        unsigned *col = s_w[0][wave];
+        for (int c = lane; c < cw; c += 64) col[c] = 0u;      // the same lane updates these columns below
+        for (int i0 = wave; i0 < rows; i0 += AG_WAVES * AG_ROWS) {   // AG_ROWS rows of this wave with their loads in flight
+            unsigned rs[AG_ROWS] = {};
+            for (int c = lane; c < cw; c += 64) {
+                unsigned v[AG_ROWS];
+#pragma unroll
+                for (int u = 0; u < AG_ROWS; ++u) {
+                    const int i = i0 + u * AG_WAVES;
+                    v[u] = i < rows ? h[(size_t)i * stride + c0 + c] : 0u;
+                }
+                unsigned pend = 0;
+#pragma unroll
+                for (int u = 0; u < AG_ROWS; ++u) {
+                    if (v[u]) {
+                        col[c] += v[u];
+                        rs[u] += v[u];                           // a row sum is at most H * W < 2^31
+                        sn2 += (unsigned long long)v[u] * v[u];
+                        pend |= 1u << u;
+                    }
+                }
+                // the FP64 log2 only for this lane's own non-zeros, in row order: a sparse table (a few non-zeros per row) does
+                // not pay one log2 per row for the whole wave
+                while (pend) {
+                    const int sel = __builtin_ctz(pend);
+                    pend &= pend - 1;
+                    unsigned x = 0;
+#pragma unroll
+                    for (int u = 0; u < AG_ROWS; ++u) x = u == sel ? v[u] : x;
+                    snl += (double)x * log2((double)x);
+                }
+            }
+            // row i0 + 16u belongs to lane u: its row sum, a^2 and a log2 a (the same lane in every chunk and in sweep 2)
+            unsigned r = 0;
+#pragma unroll
+            for (int u = 0; u < AG_ROWS; ++u) {
+                const unsigned t = ag_wave_sum(rs[u]);
+                r = lane == u ? t : r;
+            }
+            const int i = i0 + lane * AG_WAVES;
+            if (lane < AG_ROWS && i < rows) {
+                const unsigned a = r + (c0 ? a_s[i] : 0u);
+                a_s[i] = a;                                      // read back by this same lane only
+                if (last && a) {
+                    sa2 += (unsigned long long)a * a;
+                    sal += (double)a * log2((double)a);
+                }
+            }
+        }
+        __syncthreads();
+        for (int c = tid; c < cw; c += AG_THREADS) {
+            unsigned b = 0;
+            for (int w = 0; w < AG_WAVES; ++w) b += s_w[0][w][c];
+            b_s[c0 + c] = b;                                   // read back by this same thread in sweep 2
+            if (b) {
+                n_tot += b;
+                sb2 += (unsigned long long)b * b;
+                sbl += (double)b * log2((double)b);
+            }
+        }
+        __syncthreads();
+    }
+
+    // ---- sweep 2: per column the largest n / (a + b - n), compared exactly (n < 2^31, u < 2^32: 64-bit products)
+    for (int c0 = 0; c0 < stride; c0 += AG_CHUNK) {
+        const int cw = min(AG_CHUNK, stride - c0);
+        for (int c = tid; c < cw; c += AG_THREADS) s_b[c] = b_s[c0 + c];
+        unsigned *bn = s_w[0][wave], *bu = s_w[1][wave];
+        for (int c = lane; c < cw; c += 64) {
+            bn[c] = 0u;
+            bu[c] = 1u;
+        }
+        __syncthreads();
+        for (int i0 = wave; i0 < rows; i0 += AG_WAVES * AG_ROWS) {
+            const int ia = i0 + lane * AG_WAVES;                 // lane u wrote a_i of row i0 + 16u in sweep 1
+            const unsigned mine = lane < AG_ROWS && ia < rows ? a_s[ia] : 0u;
+            unsigned a[AG_ROWS];
+#pragma unroll
+            for (int u = 0; u < AG_ROWS; ++u) a[u] = __shfl(mine, u);
+            for (int c = lane; c < cw; c += 64) {
+                unsigned v[AG_ROWS];
+#pragma unroll
+                for (int u = 0; u < AG_ROWS; ++u) {
+                    const int i = i0 + u * AG_WAVES;
+                    v[u] = i < rows ? h[(size_t)i * stride + c0 + c] : 0u;
+                }
+                const unsigned b = s_b[c];
+                unsigned n = bn[c], d = bu[c];
+#pragma unroll
+                for (int u = 0; u < AG_ROWS; ++u) {               // rows in index order: the first of equal ratios stays
+                    if (v[u]) {
+                        const unsigned uu = a[u] + b - v[u];       // >= n >= 1
+                        if ((unsigned long long)v[u] * d > (unsigned long long)n * uu) {
+                            n = v[u];
+                            d = uu;
+                        }
+                    }
+                }
+                bn[c] = n;
+                bu[c] = d;
+            }
+        }
+        __syncthreads();
+        for (int c = tid; c < cw; c += AG_THREADS) {
+            unsigned n = s_w[0][0][c], u = s_w[1][0][c];
+            for (int w = 1; w < AG_WAVES; ++w) {
+                const unsigned n2 = s_w[0][w][c], u2 = s_w[1][w][c];
+                if ((unsigned long long)n2 * u > (unsigned long long)n * u2) {
+                    n = n2;
+                    u = u2;
+                }
+            }
+            if (n) cov += (double)s_b[c] * ((double)n / (double)u);
+        }
+        __syncthreads();
+    }
+
+    // ---- fixed-order reduction: shuffle tree per wave, then the waves in index order
+    n_tot = ag_wave_sum(n_tot);
+    sa2 = ag_wave_sum(sa2);
+    sb2 = ag_wave_sum(sb2);
+    sn2 = ag_wave_sum(sn2);
+    sal = ag_wave_sum(sal);
+    sbl = ag_wave_sum(sbl);
+    snl = ag_wave_sum(snl);
+    cov = ag_wave_sum(cov);
+    if (lane == 0) {
+        s_u[wave][0] = n_tot; s_u[wave][1] = sa2; s_u[wave][2] = sb2; s_u[wave][3] = sn2;
+        s_d[wave][0] = sal;   s_d[wave][1] = sbl; s_d[wave][2] = snl; s_d[wave][3] = cov;
+    }
+    __syncthreads();
+    if (tid < 8) {
+        const int k = tid & 3;
+        if (tid < 4) {
+            unsigned long long v = 0;
+            for (int w = 0; w < AG_WAVES; ++w) v += s_u[w][k];
+            sums[(size_t)t * 4 + k] = v;
+        } else {
+            double v = 0.0;
+            for (int w = 0; w < AG_WAVES; ++w) v += s_d[w][k];
+            terms[(size_t)t * 4 + k] = v;
+        }
+    }
+}
+
+extern "C" size_t gcs_region_agreement_scratch_bytes(int T, int n_segments, int n_truth_labels) {
+    if (T <= 0 || n_segments <= 0 || n_truth_labels <= 0) return 0;
+    return (size_t)T * ((size_t)n_segments + n_truth_labels) * sizeof(uint32_t);
+}
+
+extern "C" int gcs_region_agreement(const uint32_t *hist, const int32_t *img_of, const int32_t *seg_max, int T, int n_segments,
+                                    int n_truth_labels, void *scratch, uint64_t *sums, double *terms, gcs_stream_t stream) {
+    if (!hist || !scratch || !sums || !terms) return gcs_fail(GCS_EINVAL, "gcs_region_agreement: NULL pointer");
+    if (seg_max && !img_of) return gcs_fail(GCS_EINVAL, "gcs_region_agreement: seg_max_dev needs img_of_dev");
+    if (T <= 0 || T > 1000000 || n_segments <= 0 || n_truth_labels <= 0 ||
+        (long long)T * n_segments * n_truth_labels > 0x3fffffffLL)
+        return gcs_fail(GCS_EINVAL, "gcs_region_agreement: bad shape");
+    hipLaunchKernelGGL(region_agreement_kernel, dim3(T), dim3(AG_THREADS), 0, stream, hist, img_of, seg_max, n_segments,
+                       n_truth_labels, static_cast<unsigned *>(scratch), reinterpret_cast<unsigned long long *>(sums), terms);
+    GCS_CHECK_LAUNCH("gcs_region_agreement");
+    return GCS_OK;
+}

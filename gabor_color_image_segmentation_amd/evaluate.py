@@ -144,3 +144,71 @@ def boundary_scores(labels, segments_truth) -> dict:
     m.set_boundary_precision()
     m.set_fmeasure()
     return {"recall": m.recall, "precision": m.precision, "fmeasure": m.fmeasure}
+
+
+# ---- region agreement: PRI, VoI, segmentation covering (SPEC.md §8; not part of the reference's ``metrics``)
+
+def agreement_sums(labels, truth):
+    """The integer sums and float terms of SPEC.md §8 for ONE annotator map, from its contingency table (bincount):
+    sums = [N, sum a^2, sum b^2, sum n^2] (Python ints), terms = [sum a log2 a, sum b log2 b, sum n log2 n,
+    sum_j b_j n*_j / u*_j] (floats) - what gcs_region_agreement writes per map."""
+    s = np.asarray(labels).astype(np.int64).ravel()
+    g = np.asarray(truth).astype(np.int64).ravel()
+    if s.shape != g.shape:
+        raise ValueError("annotator map and label map differ in shape")
+    if s.size and (s.min() < 0 or g.min() < 0):
+        raise ValueError("labels must be non-negative")
+    n_g = int(g.max()) + 1 if g.size else 1
+    n_s = int(s.max()) + 1 if s.size else 1
+    hist = np.bincount(s * n_g + g, minlength=n_s * n_g).reshape(n_s, n_g).astype(np.int64)
+    a, b = hist.sum(axis=1), hist.sum(axis=0)
+    nz = lambda v: v[v > 0].astype(np.float64)
+    xlog = lambda v: float(np.sum(nz(v) * np.log2(nz(v))))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(hist > 0, hist / (a[:, None] + b[None, :] - hist), 0.0)
+    best = ratio.max(axis=0)
+    sums = [int(b.sum()), int(np.sum(a * a)), int(np.sum(b * b)), int(np.sum(hist * hist))]
+    terms = [xlog(a), xlog(b), xlog(hist), float(np.sum(b.astype(np.float64) * best))]
+    return sums, terms
+
+
+def agreement_from_sums(sums, terms, first, n_pixels) -> list:
+    """SPEC.md §8 from the per-map sums / terms ([T][4] each; maps first[i] .. first[i+1]-1 belong to image i): one dict
+    {"PRI", "VoI", "covering"} per image, annotator means in annotator order. The ONE finishing step of the host definition
+    and every device path, so the integer-derived PRI is the same float everywhere. Raises if a table did not count every
+    pixel (N_t != n_pixels: a label outside the table)."""
+    n = int(n_pixels)
+    if n < 2:
+        raise ValueError(f"region agreement needs at least 2 pixels, got {n}")
+    pairs = n * (n - 1)
+    out = []
+    first = [int(f) for f in first]
+    for i in range(len(first) - 1):
+        t0, t1 = first[i], first[i + 1]
+        if t1 <= t0:
+            raise ZeroDivisionError("an image has no annotator maps")
+        pri = voi = cov = 0.0
+        for t in range(t0, t1):
+            n_t, sa2, sb2, sn2 = (int(x) for x in sums[t])
+            if n_t != n:
+                raise ValueError(f"contingency table of map {t} counts {n_t} pixels, the image has {n} "
+                                 "(a label outside the table)")
+            hal, hbl, hnl, cv = (float(x) for x in terms[t])
+            pri += 1.0 - (sa2 + sb2 - 2 * sn2) / pairs             # exact integers, one rounding
+            voi += (hal + hbl - 2.0 * hnl) / n
+            cov += cv / n
+        k = t1 - t0
+        out.append({"PRI": pri / k, "VoI": voi / k, "covering": cov / k})
+    return out
+
+
+def region_agreement(labels, segments_truth) -> dict:
+    """PRI, VoI (bits) and segmentation covering of one label map against its annotator maps (SPEC.md §8).
+    {"PRI", "VoI", "covering"}; labels / maps: (H,W) non-negative integer arrays."""
+    labels = np.asarray(labels)
+    if len(segments_truth) == 0:
+        raise ZeroDivisionError("no annotator maps")
+    if labels.size < 2:
+        raise ValueError(f"region agreement needs at least 2 pixels, got {labels.size}")
+    st = [agreement_sums(labels, g) for g in segments_truth]
+    return agreement_from_sums([s for s, _ in st], [t for _, t in st], [0, len(st)], labels.size)[0]

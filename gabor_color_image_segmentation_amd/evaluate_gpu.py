@@ -14,6 +14,7 @@ import numpy as np
 from math import pi
 
 from . import _lib
+from .evaluate import agreement_from_sums
 
 
 def boundary_counts_device(labels, truths):
@@ -123,6 +124,47 @@ def region_scores_from_counts(hist, area, perim, n_truth, nx, ny) -> dict:
     return {"underseg": float(under), "undersegNP": float(under_np), "compactness": float(compactness)}
 
 
+def _agreement_launch(hist, img_of_d, seg_max_d, t, n_seg, stride, sums_ptr, terms_ptr, stream, device):
+    """gcs_region_agreement on device tables hist [t][n_seg][stride] (its scratch goes back to the stream-ordered allocator)."""
+    import torch
+    lib = _lib.load()
+    scratch = torch.empty(lib.gcs_region_agreement_scratch_bytes(t, n_seg, stride), dtype=torch.uint8, device=device)
+    _lib.check(lib.gcs_region_agreement(hist.data_ptr(), img_of_d.data_ptr() if img_of_d is not None else None,
+                                        seg_max_d.data_ptr() if seg_max_d is not None else None, t, n_seg, stride,
+                                        scratch.data_ptr(), sums_ptr, terms_ptr, stream), "gcs_region_agreement")
+
+
+def region_agreement_device(labels, segments_truth) -> dict:
+    """``evaluate.region_agreement`` (PRI, VoI, covering; SPEC.md §8) of one (H,W) int32 device label map: the contingency
+    tables by gcs_region_counts, their reduction by gcs_region_agreement, 64 bytes per annotator map downloaded."""
+    import torch
+    if len(segments_truth) == 0:
+        raise ZeroDivisionError("no annotator maps")
+    if labels.dtype != torch.int32 or labels.dim() != 2:
+        raise ValueError("labels must be an (H,W) int32 tensor")
+    t, truths = _truth_stack(segments_truth, labels.device)
+    h, w = labels.shape
+    if h * w < 2:
+        raise ValueError(f"region agreement needs at least 2 pixels, got {h * w}")
+    a = len(t)
+    n_seg = int(labels.max().item()) + 1
+    stride = int(t.max()) + 1
+    dev = labels.device
+    labels = labels.contiguous()
+    hist = torch.empty((a, n_seg, stride), dtype=torch.int32, device=dev)
+    area = torch.empty(n_seg, dtype=torch.int32, device=dev)
+    perim = torch.empty(n_seg, dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    lib = _lib.load()
+    _lib.check(lib.gcs_region_counts(labels.data_ptr(), truths.data_ptr(), a, h, w, n_seg, stride, hist.data_ptr(),
+                                     area.data_ptr(), perim.data_ptr(), stream), "gcs_region_counts")
+    out = torch.empty(a * 8, dtype=torch.int64, device=dev)        # sums uint64 [a][4] | terms double [a][4]
+    _agreement_launch(hist, None, None, a, n_seg, stride, out.data_ptr(), out.data_ptr() + a * 32, stream, dev)
+    raw = out.cpu().numpy()
+    return agreement_from_sums(raw[:a * 4].view(np.uint64).reshape(a, 4), raw[a * 4:].view(np.float64).reshape(a, 4),
+                               [0, a], h * w)[0]
+
+
 def all_scores_device(labels, segments_truth) -> dict:
     """Every number of ``evaluate.metrics.get_metrics()`` (= metrics.py:246-255 plus F) for a device label map:
     stencils, masked sums and histograms on the GPU, the reference's float arithmetic on the host."""
@@ -141,17 +183,18 @@ def all_scores_device(labels, segments_truth) -> dict:
     return out
 
 
-def all_scores_batch_device(labels, truth, first=None, img_of=None, n_truth=None, n_segments=None) -> list:
+def all_scores_batch_device(labels, truth, first=None, img_of=None, n_truth=None, n_segments=None, agreement=False) -> list:
     """Every number of ``evaluate.metrics.get_metrics()`` for a whole batch of device label maps in THREE launches
     (boundary maps, boundary counts, region tables) and one device-to-host copy per table, instead of a scoring call
     and two host round trips per image (metrics.py:58-201 loops over images in script.py:22).
 
     labels: (B,H,W) int32 device tensor; truth / first / img_of / n_truth: ``PackedTruth.stack(ids)`` (or the same
     layout built by hand): all annotator maps of image 0, then of image 1, ...; n_segments: max label + 1 over the
-    batch (default: read from the labels; metrics.py:51 per image is the image's own max + 1, applied below)."""
+    batch (default: read from the labels; metrics.py:51 per image is the image's own max + 1, applied below).
+    agreement=True: each dict also gets "PRI", "VoI" and "covering" (SPEC.md §8) from one more launch on the same tables."""
     import torch
     if isinstance(truth, DeviceTruth):                       # resident ground truth (round 5): nothing of it is uploaded or re-derived
-        return all_scores_batch_resident(labels, truth, n_segments)
+        return all_scores_batch_resident(labels, truth, n_segments, agreement=agreement)
     lib = _lib.load()
     if labels.dtype != torch.int32 or labels.dim() != 3:
         raise ValueError("labels must be a (B,H,W) int32 tensor")
@@ -164,7 +207,7 @@ def all_scores_batch_device(labels, truth, first=None, img_of=None, n_truth=None
         raise ZeroDivisionError("an image has no annotator maps (metrics.py:74 divides by len(img_truth))")
     dev = labels.device
     labels = labels.contiguous()
-    seg_max = labels.reshape(b, -1).max(dim=1).values                   # per-image max label, one small copy below
+    seg_max_dev = seg_max = labels.reshape(b, -1).max(dim=1).values     # per-image max label, one small copy below
     truth_d = torch.from_numpy(truth.view(np.int16)).to(dev)
     first_d = torch.from_numpy(np.ascontiguousarray(first, np.int32)).to(dev)
     img_of_d = torch.from_numpy(np.ascontiguousarray(img_of, np.int32)).to(dev)
@@ -183,6 +226,15 @@ def all_scores_batch_device(labels, truth, first=None, img_of=None, n_truth=None
     _lib.check(lib.gcs_region_counts_batch(labels.data_ptr(), truth_d.data_ptr(), first_d.data_ptr(), b, t, a_max, h, w,
                                            n_seg, stride, hist.data_ptr(), area.data_ptr(), perim.data_ptr(), stream),
                "gcs_region_counts_batch")
+    if agreement:
+        if h * w < 2:
+            raise ValueError(f"region agreement needs at least 2 pixels, got {h * w}")
+        agr = torch.empty(t * 8, dtype=torch.int64, device=dev)           # sums uint64 [t][4] | terms double [t][4]
+        seg_max_d = seg_max_dev.to(torch.int32).contiguous()
+        _agreement_launch(hist, img_of_d, seg_max_d, t, n_seg, stride, agr.data_ptr(), agr.data_ptr() + t * 32, stream, dev)
+        raw = agr.cpu().numpy()
+        agree = agreement_from_sums(raw[:t * 4].view(np.uint64).reshape(t, 4), raw[t * 4:].view(np.float64).reshape(t, 4),
+                                    first, h * w)
     counts = counts.cpu().numpy().astype(np.uint64)
     hist, area, perim = hist.cpu().numpy(), area.cpu().numpy(), perim.cpu().numpy()
     out = []
@@ -194,6 +246,8 @@ def all_scores_batch_device(labels, truth, first=None, img_of=None, n_truth=None
         res.update(scores_from_counts(c))
         res.update(region_scores_from_counts(hist[t0:t1, :n_i], area[i, :n_i], perim[i, :n_i], n_truth[t0:t1], h, w))
         res["density"] = float(c[0]) / float(h * w)
+        if agreement:
+            res.update(agree[i])
         out.append(res)
     return out
 
@@ -245,7 +299,7 @@ class DeviceTruth:
         self._out = None                                       # (capacity, device result block, pinned host block, views, ...)
         self._scratch = None
 
-    def _buffers(self, n_seg):
+    def _buffers(self, n_seg, agreement=False):
         """ONE device block for everything a call returns (counts | under | under_np | seg_max | area | perim) and its pinned
         mirror: one device-to-host copy of a few KB and one synchronisation per call instead of five; the contingency tables
         stay on the device (gcs_region_reduce takes the two sums metrics.py:128-140 needs out of them).
@@ -254,7 +308,9 @@ class DeviceTruth:
         connected-region maps, whose label count differs from batch to batch, reuses it and reallocates - dropping the old
         blocks - only when a batch needs more (the kernels take the capacity as their table stride; segments that do not occur
         have area 0 and perimeter 0 and add nothing to any score). Returns (capacity, device block, pinned block, offsets,
-        bit-plane scratch, contingency tables)."""
+        bit-plane scratch, contingency tables, agreement scratch). agreement=True appends the per-map sums / terms of
+        gcs_region_agreement (SPEC.md §8) to the END of the block (the offsets before them do not move) and keeps its scratch;
+        a call without agreement copies only the part before them."""
         import torch
         cap = 8                                                 # (k-means maps of the default k stay at their exact size)
         while cap < n_seg:
@@ -263,11 +319,13 @@ class DeviceTruth:
             self._scratch = torch.empty(_lib.load().gcs_bit_planes_bytes(self.b, self.h, self.w), dtype=torch.uint8,
                                         device=self.device)
         ent = self._out
-        if ent is None or ent[0] < cap:
+        if ent is None or ent[0] < cap or (agreement and ent[6] is None):
             self._out = ent = None                              # the old blocks go back to the allocator first
             b, t = self.b, self.t
             sizes = [("counts", (b + 3 * t) * 8), ("under", t * 8), ("under_np", t * 8), ("seg_max", b * 4),
                      ("area", b * cap * 4), ("perim", b * cap * 4)]
+            if agreement:
+                sizes += [("agr_sums", t * 32), ("agr_terms", t * 32)]
             offs, o = {}, 0
             for name, nbytes in sizes:
                 offs[name] = (o, nbytes)
@@ -275,7 +333,11 @@ class DeviceTruth:
             dev_blk = torch.empty(o, dtype=torch.uint8, device=self.device)
             host_blk = torch.empty(o, dtype=torch.uint8, pin_memory=True)
             hist = torch.empty(t * cap * self.stride, dtype=torch.int32, device=self.device)       # never leaves the device
-            ent = self._out = (cap, dev_blk, host_blk, offs, self._scratch, hist)
+            agr_scratch = None
+            if agreement:
+                agr_scratch = torch.empty(_lib.load().gcs_region_agreement_scratch_bytes(t, cap, self.stride), dtype=torch.uint8,
+                                          device=self.device)
+            ent = self._out = (cap, dev_blk, host_blk, offs, self._scratch, hist, agr_scratch)
         return ent
 
 
@@ -314,8 +376,9 @@ class _PendingScores:
     reference's float arithmetic. Submitting the next batch before collecting this one lets its kernels run under that
     arithmetic (``all_scores_batch_resident`` = submit + result)."""
 
-    def __init__(self, truth, b, h, w, n_seg, host_blk, offs, event, cap=None):
+    def __init__(self, truth, b, h, w, n_seg, host_blk, offs, event, cap=None, agreement=False):
         self._a = (truth, b, h, w, n_seg, host_blk, offs, event, cap or n_seg)
+        self._agreement = agreement
 
     def result(self) -> list:
         truth, b, h, w, n_seg, host_blk, offs, event, cap = self._a
@@ -329,6 +392,9 @@ class _PendingScores:
         area = view("area", np.int32).reshape(b, cap)[:, :n_seg]     # tables are laid out at the capacity; columns >= n_seg are zero
         perim = view("perim", np.int32).reshape(b, cap)[:, :n_seg]
         reg = _region_scores_batch(view("under", np.uint64), view("under_np", np.uint64), area, perim, truth.first, h, w)
+        if self._agreement:
+            agree = agreement_from_sums(view("agr_sums", np.uint64).reshape(-1, 4), view("agr_terms", np.float64).reshape(-1, 4),
+                                        truth.first, h * w)
         out = []
         cf = counts.astype(np.float64).tolist()                      # counts < 2^53: exact; Python floats from here on
         first = truth.first.tolist()
@@ -347,14 +413,18 @@ class _PendingScores:
                    "fmeasure": 0.0 if sm == 0 else 2.0 * precision * recall / sm}
             res.update(reg[i])
             res["density"] = g / float(h * w)
+            if self._agreement:
+                res.update(agree[i])
             out.append(res)
         return out
 
 
-def submit_scores_batch_resident(labels, truth: DeviceTruth, n_segments=None) -> _PendingScores:
+def submit_scores_batch_resident(labels, truth: DeviceTruth, n_segments=None, agreement=False) -> _PendingScores:
     """Enqueue the scoring of a (B,H,W) int32 device label batch against resident ground truth; ``.result()`` returns what
     ``all_scores_batch_device`` returns. One result block per DeviceTruth: collect a submission before submitting the
-    next batch against the SAME DeviceTruth."""
+    next batch against the SAME DeviceTruth. agreement=True: one more launch on the contingency tables the scorer leaves on the
+    device (gcs_region_agreement, rows bounded by the labels' maxima) and "PRI", "VoI", "covering" in every dict, from the same
+    single copy."""
     import torch
     lib = _lib.load()
     if labels.dtype != torch.int32 or labels.dim() != 3:
@@ -364,7 +434,9 @@ def submit_scores_batch_resident(labels, truth: DeviceTruth, n_segments=None) ->
         raise ValueError("label batch does not match the resident truth (images, shape or device)")
     labels = labels.contiguous()
     n_seg = int(n_segments) if n_segments is not None else int(labels.max().item()) + 1
-    cap, dev_blk, host_blk, offs, scratch, hist_d = truth._buffers(n_seg)
+    if agreement and h * w < 2:
+        raise ValueError(f"region agreement needs at least 2 pixels, got {h * w}")
+    cap, dev_blk, host_blk, offs, scratch, hist_d, agr_scratch = truth._buffers(n_seg, agreement)
     base = dev_blk.data_ptr()
     ptr = {k: base + o for k, (o, _) in offs.items()}
     with torch.cuda.device(truth.device):
@@ -375,14 +447,25 @@ def submit_scores_batch_resident(labels, truth: DeviceTruth, n_segments=None) ->
                                                 scratch.data_ptr(), hist_d.data_ptr(), ptr["counts"], ptr["seg_max"], ptr["area"],
                                                 ptr["perim"], ptr["under"], ptr["under_np"], stream.cuda_stream),
                    "gcs_score_batch_resident")
-        host_blk.copy_(dev_blk, non_blocking=True)
+        if agreement:
+            _lib.check(lib.gcs_region_agreement(hist_d.data_ptr(), truth.img_of_d.data_ptr(), ptr["seg_max"], truth.t, cap,
+                                                truth.stride, agr_scratch.data_ptr(), ptr["agr_sums"], ptr["agr_terms"],
+                                                stream.cuda_stream), "gcs_region_agreement")
+            host_blk.copy_(dev_blk, non_blocking=True)
+        else:                                                   # the block may carry agreement slots of an earlier call
+            used = offs["perim"][0] + offs["perim"][1]
+            used = (used + 15) // 16 * 16
+            if used == dev_blk.numel():
+                host_blk.copy_(dev_blk, non_blocking=True)
+            else:
+                host_blk[:used].copy_(dev_blk[:used], non_blocking=True)
         event = torch.cuda.Event()
         event.record(stream)
-    return _PendingScores(truth, b, h, w, n_seg, host_blk, offs, event, cap)
+    return _PendingScores(truth, b, h, w, n_seg, host_blk, offs, event, cap, agreement)
 
 
-def all_scores_batch_resident(labels, truth: DeviceTruth, n_segments=None) -> list:
+def all_scores_batch_resident(labels, truth: DeviceTruth, n_segments=None, agreement=False) -> list:
     """``all_scores_batch_device`` on resident ground truth: kernels on bit planes and uint8 maps, the tables reduced on the
     device, ONE device-to-host copy of a few KB. ``n_segments``: an upper bound of max label + 1 over the batch (the
     Segmenter's k); None reads it from the labels (one more synchronisation)."""
-    return submit_scores_batch_resident(labels, truth, n_segments).result()
+    return submit_scores_batch_resident(labels, truth, n_segments, agreement).result()

@@ -256,6 +256,25 @@ int gcs_score_batch_resident(const int32_t *labels_dev, const void *truth_planes
                              uint32_t *hist_dev, uint64_t *counts_dev, int32_t *seg_max_dev, uint32_t *area_dev, uint32_t *perim_dev,
                              uint64_t *under_dev, uint64_t *under_np_dev, gcs_stream_t stream);
 
+/* ---- region agreement: PRI, VoI, segmentation covering (SPEC.md §8) ----------------------------- */
+
+/* The three region metrics of the BSDS500 benchmark out of the contingency tables the calls above leave on the device
+ * (gcs_region_counts[_batch[_u8]], gcs_score_batch_resident): hist_dev uint32 [T][n_segments][n_truth_labels], one table per
+ * annotator map t, n_ij = pixels with label i and annotator label j. With a_i = sum_j n_ij and b_j = sum_i n_ij taken from
+ * the table itself, writes per map t
+ *   sums_dev  uint64 [T][4] = { N_t = sum_j b_j, sum_i a_i^2, sum_j b_j^2, sum_ij n_ij^2 }                  (exact)
+ *   terms_dev double [T][4] = { sum a_i log2 a_i, sum b_j log2 b_j, sum n_ij log2 n_ij,
+ *                               sum_j b_j * n*_j / u*_j }  (over non-zero entries; n*_j / u*_j = the largest
+ *                               n_ij / (a_i + b_j - n_ij) of column j, compared exactly)
+ * The host checks N_t == H * W (a label outside the table was not counted) and finishes PRI / VoI / covering (SPEC.md §8).
+ * seg_max_dev int32 [B] (may be NULL; needs img_of_dev int32 [T] = image of map t): rows above seg_max[img_of[t]] are not
+ * read (tables allocated at a capacity of segments). scratch_dev: gcs_region_agreement_scratch_bytes(T, n_segments,
+ * n_truth_labels) bytes. Float sums run in an order fixed by the table indices alone: the same maps give the same bits at any
+ * table shape, from run to run. */
+size_t gcs_region_agreement_scratch_bytes(int T, int n_segments, int n_truth_labels);
+int gcs_region_agreement(const uint32_t *hist_dev, const int32_t *img_of_dev, const int32_t *seg_max_dev, int T, int n_segments,
+                         int n_truth_labels, void *scratch_dev, uint64_t *sums_dev, double *terms_dev, gcs_stream_t stream);
+
 /* ---- connected regions (SPEC.md §7) -------------------------------------- */
 
 /* labels_dev int32 [B][H][W] -> out_dev int32 [B][H][W]: 4-connected components of equal labels,
