@@ -12,6 +12,9 @@ the device path, the batched GPU scorer against the packed ground truth of all 5
 numbers the reference's own metrics class gave for the same label maps (tests/golden/bsd_val_scores.json).
 `--val --agreement`: also the region metrics PRI / VoI / covering (SPEC.md §8) of the same maps, as segmented and as
 4-connected regions, with their means beside the scikit-learn / scikit-image numbers (tests/golden/region_agreement_golden.json).
+`--min-region-size N[,N...]`: the same 24 images through Segmenter(min_region_size=N) (SPEC.md §9: regions below N pixels
+merged into their largest neighbour), one row per N of mean recall / precision / F / PRI / VoI / covering and the range of
+regions per image, all from the GPU path.
 """
 import os
 import sys
@@ -66,7 +69,35 @@ def val_split(agreement=False):
                     float(np.mean([gold_agr["val/%s/%s" % (i, kind)][gkey] for i in ids]))))
 
 
+def merge_table(sizes):
+    import numpy as np
+    import torch
+    from gabor_color_image_segmentation_amd import Segmenter
+    from gabor_color_image_segmentation_amd.evaluate_gpu import all_scores_batch_device
+    from gabor_color_image_segmentation_amd.groundtruth import PackedTruth
+    gold = os.path.join(ROOT, "tests", "golden")
+    pack = np.load(os.path.join(gold, "bsd_val_images.npz"))
+    truth = PackedTruth(os.path.join(gold, "bsd500_truth.npz"))
+    ids = [str(i) for i in pack["ids"]]
+    groups = [[i for i in ids if pack["img_" + i].shape[:2] == shape] for shape in sorted({pack["img_" + i].shape[:2] for i in ids})]
+    keys = ("recall", "precision", "fmeasure", "PRI", "VoI", "covering")
+    print("| m | R | P | F | PRI | VoI | covering | regions / image |")
+    print("|---|---|---|---|---|---|---|---|")
+    for m in sizes:
+        seg = Segmenter(min_region_size=m)
+        rows = []
+        for group in groups:
+            labels = seg.segment_device(torch.from_numpy(np.stack([pack["img_" + i] for i in group])).cuda())
+            rows += all_scores_batch_device(labels, truth.to_device(group), agreement=True)
+        mean = [float(np.mean([r[k] for r in rows])) for k in keys]
+        regions = [r["regions"] for r in rows]
+        print("| %d | %s | %d - %d |" % (m, " | ".join("%.4f" % v for v in mean), min(regions), max(regions)))
+
+
 if __name__ == '__main__':
+    if "--min-region-size" in sys.argv:
+        merge_table([int(v) for v in sys.argv[sys.argv.index("--min-region-size") + 1].split(",")])
+        sys.exit(0)
     if "--val" in sys.argv:
         val_split(agreement="--agreement" in sys.argv)
         sys.exit(0)

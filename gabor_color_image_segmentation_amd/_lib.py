@@ -61,6 +61,8 @@ SIGNATURES = {
     "gcs_region_agreement": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "gcs_connected_scratch_bytes": (_sz, [_i, _i, _i]),
     "gcs_connected_regions": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "gcs_merge_scratch_bytes": (_sz, [_i, _i, _i, _i]),
+    "gcs_merge_small_regions": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
 }
 
 

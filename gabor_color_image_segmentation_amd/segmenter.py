@@ -339,6 +339,14 @@ class HipOps:
                                                   out.data_ptr(), self._stream()), "gcs_connected_regions")
 
     @_on_device
+    def merge_small_regions(self, labels_i32, min_size, out):
+        """SPEC.md §9 on an int32 (B,H,W) device tensor into ``out`` (not the same memory)."""
+        b, h, w = labels_i32.shape
+        scratch = self.empty_bytes(self.lib.gcs_merge_scratch_bytes(b, h, w, int(min_size)))
+        _lib.check(self.lib.gcs_merge_small_regions(labels_i32.data_ptr(), b, h, w, int(min_size), scratch.data_ptr(),
+                                                    out.data_ptr(), self._stream()), "gcs_merge_small_regions")
+
+    @_on_device
     def labels_widen(self, labels, b, h, w, out):
         _lib.check(self.lib.gcs_labels_widen(labels.data_ptr(), b, h, w, out.data_ptr(), self._stream()),
                    "gcs_labels_widen")
@@ -442,14 +450,17 @@ class Segmenter:
 
     def __init__(self, n_scales=4, n_orient=6, k=8, n_iter=10, ksize=13, f_max=0.4,
                  ratio=math.sqrt(2.0), bandwidth=1.0, connectivity=False, device="cuda:0", ops=None,
-                 slab_candidates=1):
+                 slab_candidates=1, min_region_size=0):
         if not (1 <= k <= _lib.K_MAX):
             raise ValueError(f"k must be in 1..{_lib.K_MAX}")
         if n_iter < 1:
             raise ValueError("n_iter must be >= 1")
+        if int(min_region_size) != min_region_size or min_region_size < 0:
+            raise ValueError("min_region_size must be a non-negative integer")
         self.k, self.n_iter = int(k), int(n_iter)
         self.debug = DebugSwitches(os.environ.get("GCS_DEBUG", ""))     # measurement / test switches (see the class)
         self.connectivity = bool(connectivity)     # SPEC.md §7 post-pass
+        self.min_region_size = int(min_region_size)  # SPEC.md §9 post-pass (> 0: connected regions, small ones merged)
         self.bank = make_bank(n_scales, n_orient, ksize, f_max, ratio, bandwidth)
         self.ops = ops if ops is not None else HipOps(self.bank, device)
         # feature-slab allocations to time at first use of a large workspace shape (see _place_slab). 1 = take the first
@@ -580,7 +591,11 @@ class Segmenter:
                       ws["cent"], ws["sums"], dist_group, raster=out[g0:g0 + n] if direct else None, debug=self.debug)
                 if not direct:
                     self.ops.labels_widen(ws["labels"], n, h, w, out[g0:g0 + n])
-            if self.connectivity:
+            if self.min_region_size > 0:
+                regions = torch.empty_like(out)
+                self.ops.merge_small_regions(out, self.min_region_size, regions)
+                out.copy_(regions)
+            elif self.connectivity:
                 regions = torch.empty_like(out)
                 self.ops.connected_regions(out, regions)
                 out.copy_(regions)
@@ -607,6 +622,8 @@ class Segmenter:
         the unsharded result. Needs torch.distributed initialised when the image is split.
         """
         torch = _torch()
+        if self.min_region_size > 0:
+            raise ValueError("min_region_size is not supported on row strips (regions would cross strip boundaries)")
         strip = strip.contiguous()
         b, hs, w, _ = strip.shape
         if hs < 8 or w < 8:
@@ -660,6 +677,8 @@ class Segmenter:
         (r0, r1) = ``shard_rows(height, world, rank, n_levels, ksize)[:2]``. Every rank must own at least the halo
         (``halo_rows(n_levels, ksize)`` rows), so that a halo comes from ONE neighbour. Returns the (B, r1-r0, W) int32 labels."""
         torch = _torch()
+        if self.min_region_size > 0:
+            raise ValueError("min_region_size is not supported on row strips (regions would cross strip boundaries)")
         import torch.distributed as td
         if not (td.is_available() and td.is_initialized()):
             raise RuntimeError("segment_owned_rows_device needs torch.distributed (one rank per row strip)")
@@ -710,7 +729,7 @@ class Segmenter:
         """(B,H,W,3) uint8 host array -> fresh (B,H,W) host label array (the calling convention of script.py:25,30).
 
         ``out_dtype``: np.int32 (default, SPEC.md §1) or np.uint8 (a quarter of the bytes; metrics.py:43 casts the map
-        with ``.astype('int')`` anyway; not with ``connectivity=True``, whose region ids exceed 255).
+        with ``.astype('int')`` anyway; not with ``connectivity=True`` or ``min_region_size > 0``, whose region ids exceed 255).
         The image upload goes through a cached pinned staging buffer, cut into chunks so that the copy of chunk n+1
         (its own stream) overlaps the Gabor stage of chunk n; the labels are copied straight into a fresh pinned
         buffer that the returned array owns."""
@@ -728,6 +747,8 @@ class Segmenter:
             raise ValueError("out_dtype must be int32 or uint8")
         if self.connectivity and out_dtype == np.uint8:
             raise ValueError("connectivity=True needs int32 labels")
+        if self.min_region_size > 0 and out_dtype == np.uint8:
+            raise ValueError("min_region_size > 0 needs int32 labels")
         b, h, w, _ = imgs.shape
         if h < 8 or w < 8:
             raise ValueError("images must be at least 8x8")
@@ -735,7 +756,7 @@ class Segmenter:
         if mode == "global":
             import torch.distributed as td
             dist_on = td.is_available() and td.is_initialized()
-        if not self.native or self.connectivity or dist_on or self.debug.force_collectives \
+        if not self.native or self.connectivity or self.min_region_size > 0 or dist_on or self.debug.force_collectives \
                 or self.group_size(b, h, w, mode) < b:
             dev = torch.from_numpy(np.asarray(imgs)).to(self.ops.device)   # plain path (test stand-ins, post-passes, collectives)
             return self.segment_device(dev, mode).cpu().numpy().astype(out_dtype, copy=False)
@@ -796,7 +817,7 @@ class Segmenter:
         if mode == "global":
             import torch.distributed as td
             dist_on = td.is_available() and td.is_initialized()
-        if not self.native or self.connectivity or dist_on or self.debug.force_collectives:
+        if not self.native or self.connectivity or self.min_region_size > 0 or dist_on or self.debug.force_collectives:
             for imgs in batches:                                   # no pipeline for post-passes / collectives / stand-ins
                 yield self.segment_batch(imgs, mode, out_dtype)
             return
@@ -920,7 +941,9 @@ class Segmenter:
             raise ValueError("out_dtype must be int32 or uint8")
         groups, ready, nxt = {}, {}, 0
         pipes, tags = {}, {}                   # per shape: the pipeline of its FULL batches and the image indices in flight
-        piped = self.native and not self.connectivity and not self.debug.force_collectives
+        if self.min_region_size > 0 and out_dtype == np.uint8:
+            raise ValueError("min_region_size > 0 needs int32 labels")
+        piped = self.native and not self.connectivity and self.min_region_size == 0 and not self.debug.force_collectives
 
         def emit(idx, labels):
             for i, lab in zip(idx, labels):

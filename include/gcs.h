@@ -285,6 +285,17 @@ size_t gcs_connected_scratch_bytes(int B, int H, int W);
 int gcs_connected_regions(const int32_t *labels_dev, int B, int H, int W, void *scratch_dev,
                           int32_t *out_dev, gcs_stream_t stream);
 
+/* ---- small-region merging (SPEC.md §9) ------------------------------------------------------ */
+
+/* labels_dev int32 [B][H][W] -> out_dev int32 [B][H][W]: the connected regions of §7, then rounds in which every region
+ * of fewer than min_size pixels that has a neighbour joins its largest neighbour (ties: the earlier first pixel), until
+ * none is left; numbered 0,1,2,... in raster order of first pixel, per image. min_size <= 1 gives gcs_connected_regions
+ * bit for bit. Stream-ordered, no host synchronisation. scratch_dev: gcs_merge_scratch_bytes() bytes (about 20 per pixel;
+ * 0 for a bad shape or min_size < 0). out_dev may not alias labels_dev. */
+size_t gcs_merge_scratch_bytes(int B, int H, int W, int min_size);
+int gcs_merge_small_regions(const int32_t *labels_dev, int B, int H, int W, int min_size, void *scratch_dev,
+                            int32_t *out_dev, gcs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
