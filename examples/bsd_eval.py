@@ -15,6 +15,8 @@ numbers the reference's own metrics class gave for the same label maps (tests/go
 `--min-region-size N[,N...]`: the same 24 images through Segmenter(min_region_size=N) (SPEC.md §9: regions below N pixels
 merged into their largest neighbour), one row per N of mean recall / precision / F / PRI / VoI / covering and the range of
 regions per image, all from the GPU path.
+`--smoothing K[,K...]`: the same through Segmenter(smoothing=K) (SPEC.md §10: the Gabor magnitudes smoothed with a Gaussian of
+K half-periods before k-means); with `--min-region-size N` as well, every K is combined with every N.
 """
 import os
 import sys
@@ -69,7 +71,7 @@ def val_split(agreement=False):
                     float(np.mean([gold_agr["val/%s/%s" % (i, kind)][gkey] for i in ids]))))
 
 
-def merge_table(sizes):
+def merge_table(sizes, smoothings=(0.0,)):
     import numpy as np
     import torch
     from gabor_color_image_segmentation_amd import Segmenter
@@ -81,22 +83,24 @@ def merge_table(sizes):
     ids = [str(i) for i in pack["ids"]]
     groups = [[i for i in ids if pack["img_" + i].shape[:2] == shape] for shape in sorted({pack["img_" + i].shape[:2] for i in ids})]
     keys = ("recall", "precision", "fmeasure", "PRI", "VoI", "covering")
-    print("| m | R | P | F | PRI | VoI | covering | regions / image |")
-    print("|---|---|---|---|---|---|---|---|")
-    for m in sizes:
-        seg = Segmenter(min_region_size=m)
+    print("| K | m | R | P | F | PRI | VoI | covering | regions / image |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    for K, m in [(K, m) for K in smoothings for m in sizes]:
+        seg = Segmenter(min_region_size=m, smoothing=K)
         rows = []
         for group in groups:
             labels = seg.segment_device(torch.from_numpy(np.stack([pack["img_" + i] for i in group])).cuda())
             rows += all_scores_batch_device(labels, truth.to_device(group), agreement=True)
         mean = [float(np.mean([r[k] for r in rows])) for k in keys]
         regions = [r["regions"] for r in rows]
-        print("| %d | %s | %d - %d |" % (m, " | ".join("%.4f" % v for v in mean), min(regions), max(regions)))
+        print("| %g | %d | %s | %d - %d |" % (K, m, " | ".join("%.4f" % v for v in mean), min(regions), max(regions)))
 
 
 if __name__ == '__main__':
-    if "--min-region-size" in sys.argv:
-        merge_table([int(v) for v in sys.argv[sys.argv.index("--min-region-size") + 1].split(",")])
+    if "--min-region-size" in sys.argv or "--smoothing" in sys.argv:
+        def arg(name, conv, default):
+            return [conv(v) for v in sys.argv[sys.argv.index(name) + 1].split(",")] if name in sys.argv else default
+        merge_table(arg("--min-region-size", int, [0]), arg("--smoothing", float, [0.0]))
         sys.exit(0)
     if "--val" in sys.argv:
         val_split(agreement="--agreement" in sys.argv)

@@ -98,3 +98,36 @@ def split_digits(tapq: np.ndarray):
     if hi.min() < -128 or hi.max() > 127:
         raise AssertionError("high digit out of int8 range")
     return lo.astype(np.int8), hi.astype(np.int8)
+
+
+SMOOTH_RADIUS_MAX = 24  # largest smoothing radius (SPEC.md §10): the HIP kernel's apron
+SMOOTH_TAPS = 2 * SMOOTH_RADIUS_MAX + 1
+SMOOTH_ONE = 4096       # the taps of a scale sum to this
+
+
+def smoothing_taps(K, n_scales=4, n_orient=6, f_max=0.4, ratio=math.sqrt(2.0)):
+    """SPEC.md §10 taps of smoothing ``K`` (> 0): ``(taps, radius)``, int32 ``[n_scales][49]`` centred (tap i of scale s at
+    ``[s][24 + i]``) and int32 ``[n_scales]``. sigma_s = K / (2 f_base(s)) level pixels, R_s = ceil(3 sigma_s) in 1..24, integer
+    taps that sum to 4096 exactly. Raises ValueError for a K that is not finite and positive or gives a radius outside 1..24."""
+    K = float(K)
+    if not math.isfinite(K) or K <= 0.0:
+        raise ValueError(f"smoothing K must be finite and > 0 to have taps, got {K}")
+    if not (1 <= n_scales <= N_SCALES_MAX) or n_orient < 1:
+        raise ValueError("bad bank shape")
+    taps = np.zeros((n_scales, SMOOTH_TAPS), np.int32)
+    radius = np.zeros(n_scales, np.int32)
+    for s in range(n_scales):
+        f_base = f_max / ratio ** s * 2.0 ** (s // 2)
+        sigma = K / (2.0 * f_base)
+        r = math.ceil(3.0 * sigma)
+        if not (1 <= r <= SMOOTH_RADIUS_MAX):
+            raise ValueError(f"smoothing K = {K} gives radius {r} on scale {s}; SPEC.md §10 allows 1..{SMOOTH_RADIUS_MAX}")
+        i = np.arange(-r, r + 1, dtype=np.float64)
+        g = np.exp(-i * i / (2.0 * sigma * sigma))
+        w = np.rint(SMOOTH_ONE * g / g.sum()).astype(np.int64)
+        w[r] = 0
+        w[r] = SMOOTH_ONE - w.sum()
+        taps[s, SMOOTH_RADIUS_MAX - r:SMOOTH_RADIUS_MAX + r + 1] = w
+        radius[s] = r
+    return taps, radius
+

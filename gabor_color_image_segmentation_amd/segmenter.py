@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 from . import _lib
-from .bank import GaborBank, make_bank
+from .bank import GaborBank, make_bank, smoothing_taps
 
 # Feature-slab bytes per group of a per-image batch. Large on purpose: measured in round 4 with the current kernels
 # (tools/cache_resident_pass.py, profiles/r4_notes.md "Infinity-Cache-resident groups"): a pass that re-reads a slab small enough
@@ -189,7 +189,7 @@ def _on_device(fn):
 class HipOps:
     """Thin pointer-passer over the C ABI for one device. Stateless apart from the bank."""
 
-    def __init__(self, bank: GaborBank, device):
+    def __init__(self, bank: GaborBank, device, smoothing=0.0):
         torch = _torch()
         if not torch.cuda.is_available():
             raise _lib.GcsError("no HIP device visible: the segmenter has no CPU fallback")
@@ -209,6 +209,13 @@ class HipOps:
         self.packed = torch.from_numpy(packed).to(self.device)
         self.bias = torch.from_numpy(bias).to(self.device)
         self._gabor_ws = None
+        # SPEC.md §10: the smoothing taps of every scale on the device (K = 0: none, and smooth_features is never called)
+        self.smoothing = _check_smoothing(smoothing, bank)
+        self._smooth_ws = self.smooth_taps = self.smooth_radius = None
+        if self.smoothing > 0:
+            taps, radius = smoothing_taps(self.smoothing, ns, no, bank.f_max, bank.ratio)
+            self.smooth_taps = torch.from_numpy(taps).to(self.device)
+            self.smooth_radius = torch.from_numpy(radius).to(self.device)
 
     # ---- allocation helpers (bytes buffers; layouts are opaque, see gcs.h)
     def empty_bytes(self, n):
@@ -257,6 +264,27 @@ class HipOps:
                                                self.bank.ksize, self.bank.shift, scratch.data_ptr(),
                                                feats.data_ptr(), self._stream()),
                    "gcs_gabor_features")
+
+    def smooth_scratch(self, b, h, w):
+        """A private smoothing workspace for one (batch, shape): the level planes (see ``smooth_features``)."""
+        return self.empty_bytes(self.lib.gcs_smooth_workspace_bytes(b, h, w, *self._bk))
+
+    @_on_device
+    def smooth_features(self, feats, b, h, w, scratch=None):
+        """SPEC.md §10 in place on a slab that ``gabor_features`` has filled, with this plan's ``smoothing``. ``scratch``: as in
+        ``gabor_features`` (a captured graph must own its workspace; eager calls may share the growing one of this HipOps)."""
+        if self.smooth_taps is None:
+            raise ValueError("smooth_features needs HipOps(smoothing=K) with K > 0")
+        need = self.lib.gcs_smooth_workspace_bytes(b, h, w, *self._bk)
+        if scratch is None:
+            if self._smooth_ws is None or self._smooth_ws.numel() < need:
+                self._smooth_ws = self.empty_bytes(need)
+            scratch = self._smooth_ws
+        elif scratch.numel() < need or scratch.device != self.device:
+            raise ValueError("smoothing scratch too small or on another device")
+        _lib.check(self.lib.gcs_smooth_features(feats.data_ptr(), b, h, w, *self._bk, self.smooth_taps.data_ptr(),
+                                                self.smooth_radius.data_ptr(), scratch.data_ptr(), self._stream()),
+                   "gcs_smooth_features")
 
     @_on_device
     def features_unpack(self, feats, b, h, w):
@@ -371,6 +399,19 @@ def _collective(fn, t, **kw):
         fn(t, **kw)
 
 
+def _check_smoothing(smoothing, bank) -> float:
+    """SPEC.md §10 parameter: a finite K >= 0 (0 = off) whose radius is at most 24 on every scale of ``bank``."""
+    try:
+        K = float(smoothing)
+    except (TypeError, ValueError):
+        raise ValueError(f"smoothing must be a number, got {smoothing!r}") from None
+    if not math.isfinite(K) or K < 0.0:
+        raise ValueError(f"smoothing must be finite and >= 0, got {smoothing!r}")
+    if K > 0.0:
+        smoothing_taps(K, bank.n_scales, bank.n_orient, bank.f_max, bank.ratio)      # raises for a radius outside 1..24
+    return K
+
+
 def lloyd(ops, feats, b, h, w, k, n_iter, mode, labels, partials, cent, sums, dist_group=None,
           rows=None, init=None, raster=None, debug=_ENV_DEBUG):
     """SPEC.md §4 schedule on one feature slab. ``mode``: 'per_image' or 'global'.
@@ -450,7 +491,7 @@ class Segmenter:
 
     def __init__(self, n_scales=4, n_orient=6, k=8, n_iter=10, ksize=13, f_max=0.4,
                  ratio=math.sqrt(2.0), bandwidth=1.0, connectivity=False, device="cuda:0", ops=None,
-                 slab_candidates=1, min_region_size=0):
+                 slab_candidates=1, min_region_size=0, smoothing=0.0):
         if not (1 <= k <= _lib.K_MAX):
             raise ValueError(f"k must be in 1..{_lib.K_MAX}")
         if n_iter < 1:
@@ -462,7 +503,10 @@ class Segmenter:
         self.connectivity = bool(connectivity)     # SPEC.md §7 post-pass
         self.min_region_size = int(min_region_size)  # SPEC.md §9 post-pass (> 0: connected regions, small ones merged)
         self.bank = make_bank(n_scales, n_orient, ksize, f_max, ratio, bandwidth)
-        self.ops = ops if ops is not None else HipOps(self.bank, device)
+        self.smoothing = _check_smoothing(smoothing, self.bank)     # SPEC.md §10, between the Gabor stage and k-means
+        self.ops = ops if ops is not None else HipOps(self.bank, device, self.smoothing)
+        if self.smoothing > 0 and getattr(self.ops, "smoothing", 0.0) != self.smoothing:
+            raise ValueError("Segmenter(smoothing=K, ops=...) needs ops built with the same smoothing")
         # feature-slab allocations to time at first use of a large workspace shape (see _place_slab). 1 = take the first
         # one (the library default: no extra memory, no host synchronisation, graph-capturable); bench.py asks for 2.
         self.slab_candidates = int(self.debug.slab_candidates or slab_candidates)
@@ -499,6 +543,8 @@ class Segmenter:
             ws = dict(feats=self.ops.feature_slab(g, h, w), labels=self.ops.label_slab(g, h, w),
                       partials=self.ops.partial_slab(g, h, w, self.k),
                       cent=self.ops.new_centroids(n_sets, self.k), sums=self.ops.new_sums(n_sets, self.k))
+            if self.smoothing > 0:
+                ws["smooth"] = self.ops.smooth_scratch(g, h, w)
             self._place_slab(ws, g, h, w, n_sets)
             # keep the eight most recent (batch, shape, mode) triples resident (a data set alternating landscape and
             # portrait batches, each with a remainder batch at its end, beside a global-codebook run, would otherwise
@@ -585,7 +631,7 @@ class Segmenter:
             for g0 in range(0, b, g):
                 n = min(g, b - g0)
                 ws = self._workspace(n, h, w, mode) if n == g else self._tail_workspace(n, h, w, mode)
-                self.ops.gabor_features(imgs[g0:g0 + n], ws["feats"])
+                self._features(imgs[g0:g0 + n], ws, n, h, w)
                 direct = hasattr(self.ops, "assign_raster")      # the last pass writes the raster map itself
                 lloyd(self.ops, ws["feats"], n, h, w, self.k, self.n_iter, mode, ws["labels"], ws["partials"],
                       ws["cent"], ws["sums"], dist_group, raster=out[g0:g0 + n] if direct else None, debug=self.debug)
@@ -603,9 +649,18 @@ class Segmenter:
 
     def _tail_workspace(self, n, h, w, mode):
         n_sets = n if mode == "per_image" else 1
-        return dict(feats=self.ops.feature_slab(n, h, w), labels=self.ops.label_slab(n, h, w),
-                    partials=self.ops.partial_slab(n, h, w, self.k),
-                    cent=self.ops.new_centroids(n_sets, self.k), sums=self.ops.new_sums(n_sets, self.k))
+        ws = dict(feats=self.ops.feature_slab(n, h, w), labels=self.ops.label_slab(n, h, w),
+                  partials=self.ops.partial_slab(n, h, w, self.k),
+                  cent=self.ops.new_centroids(n_sets, self.k), sums=self.ops.new_sums(n_sets, self.k))
+        if self.smoothing > 0:
+            ws["smooth"] = self.ops.smooth_scratch(n, h, w)
+        return ws
+
+    def _features(self, imgs, ws, b, h, w):
+        """The Gabor stage into ``ws["feats"]``, then the smoothing of SPEC.md §10 when it is on."""
+        self.ops.gabor_features(imgs, ws["feats"])
+        if self.smoothing > 0:
+            self.ops.smooth_features(ws["feats"], b, h, w, scratch=ws["smooth"])
 
     def shard_rows(self, height, world, rank):
         """``shard_rows`` for THIS plan's bank (its pyramid depth and kernel size decide alignment and halo)."""
@@ -624,6 +679,8 @@ class Segmenter:
         torch = _torch()
         if self.min_region_size > 0:
             raise ValueError("min_region_size is not supported on row strips (regions would cross strip boundaries)")
+        if self.smoothing > 0:
+            raise ValueError("smoothing is not supported on row strips (the halo would have to grow by the smoothing radius)")
         strip = strip.contiguous()
         b, hs, w, _ = strip.shape
         if hs < 8 or w < 8:
@@ -679,6 +736,8 @@ class Segmenter:
         torch = _torch()
         if self.min_region_size > 0:
             raise ValueError("min_region_size is not supported on row strips (regions would cross strip boundaries)")
+        if self.smoothing > 0:
+            raise ValueError("smoothing is not supported on row strips (the halo would have to grow by the smoothing radius)")
         import torch.distributed as td
         if not (td.is_available() and td.is_initialized()):
             raise RuntimeError("segment_owned_rows_device needs torch.distributed (one rank per row strip)")
@@ -717,11 +776,14 @@ class Segmenter:
         return self.segment_rows_sharded_device(strip, r0, r1, s0, height, dist_group)
 
     def features_device(self, imgs):
-        """Canonical (B,D,H,W) uint16 features as an int16 tensor (tests / debugging)."""
+        """Canonical (B,D,H,W) uint16 features as an int16 tensor (tests / debugging): what the Lloyd passes consume, smoothed
+        when ``smoothing`` is on."""
         imgs = imgs.contiguous()
         b, h, w, _ = imgs.shape
         feats = self.ops.feature_slab(b, h, w)
         self.ops.gabor_features(imgs, feats)
+        if self.smoothing > 0:
+            self.ops.smooth_features(feats, b, h, w)
         return self.ops.features_unpack(feats, b, h, w)
 
     # ---- host API: the slot
@@ -788,6 +850,8 @@ class Segmenter:
                     st["ev"][i].record(st["copy"])
                 cur.wait_event(st["ev"][i])
                 ops.gabor_features(st["dev_in"][g0:g1], ws["feats"][g0 * per_img:])
+            if self.smoothing > 0:                                 # every chunk's Gabor stage is in front of it on `cur`
+                ops.smooth_features(ws["feats"], b, h, w, scratch=ws["smooth"])
             dev_out = st["dev_out"] if out_dtype == np.uint8 else st["dev_out32"]
             lloyd(ops, ws["feats"], b, h, w, self.k, self.n_iter, mode, ws["labels"], ws["partials"],
                   ws["cent"], ws["sums"], raster=dev_out, debug=self.debug)
@@ -849,6 +913,7 @@ class Segmenter:
                 # entry and lives exactly as long as the graph does (the shared scratch of HipOps is replaced, and its
                 # block recycled, whenever a later call needs a larger one)
                 scratch = self.ops.gabor_scratch(b, h, w)
+                smooth = ws.get("smooth")                  # (allocated with the workspace, outside the capture)
 
                 # (the closure must not capture `self`: the entry lives in self._graphs, and a Segmenter inside a reference
                 # cycle is freed - with its graphs, streams, pinned and device buffers - only when the cyclic collector
@@ -857,6 +922,8 @@ class Segmenter:
 
                 def step():
                     ops.gabor_features(dev_in, ws["feats"], scratch=scratch)
+                    if smooth is not None:
+                        ops.smooth_features(ws["feats"], b, h, w, scratch=smooth)
                     lloyd(ops, ws["feats"], b, h, w, k, n_iter, mode, ws["labels"], ws["partials"], ws["cent"],
                           ws["sums"], raster=dev_out, debug=debug)
                 dev_in.zero_()
@@ -1079,6 +1146,8 @@ class _StreamPipe:
             if n >= n_slots:
                 cur.wait_event(st["ev_down"][i])                   # dev_out[i] has been downloaded
             ops.gabor_features(st["dev_in"][i], ws["feats"])
+            if seg.smoothing > 0:
+                ops.smooth_features(ws["feats"], b, h, w, scratch=ws["smooth"])
             lloyd(ops, ws["feats"], b, h, w, seg.k, seg.n_iter, self.mode, ws["labels"], ws["partials"], ws["cent"],
                   ws["sums"], raster=st["dev_out"][i], debug=seg.debug)
             st["ev_done"][i].record(cur)

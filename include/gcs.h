@@ -296,6 +296,20 @@ size_t gcs_merge_scratch_bytes(int B, int H, int W, int min_size);
 int gcs_merge_small_regions(const int32_t *labels_dev, int B, int H, int W, int min_size, void *scratch_dev,
                             int32_t *out_dev, gcs_stream_t stream);
 
+/* ---- smoothing of the feature levels (SPEC.md §10) --------------------------------------------- */
+
+/* In place on a feature slab that gcs_gabor_features has filled (either format: split or wide): every plane of every level
+ * becomes h = (sum_{dy,dx} w_dy w_dx g[r(y+dy), r(x+dx)] + 2^23) >> 24 at the level's own resolution (reflect border), with the
+ * taps of the plane's filter scale; the flag words of a split slab are rewritten to match. taps_dev int32 [n_scales][49], tap i of
+ * scale s at [s][24 + i], i = -R_s .. R_s (the rest is not read); radius_dev int32 [n_scales]. Both are read on the device: a
+ * scale whose radius is outside 1..24 or whose taps are negative or do not sum to 4096 is left unsmoothed (the host validates
+ * before it uploads; bank.smoothing_taps). Stream-ordered, two launches, no host synchronisation, no allocation (capturable).
+ * workspace_dev: gcs_smooth_workspace_bytes() bytes (the level planes, 2 bytes per value; 0 for a bad shape), contents undefined
+ * before and after. Requires H, W >= 8. */
+size_t gcs_smooth_workspace_bytes(int B, int H, int W, int n_scales, int n_orient);
+int gcs_smooth_features(uint16_t *feats_dev, int B, int H, int W, int n_scales, int n_orient, const int32_t *taps_dev,
+                        const int32_t *radius_dev, void *workspace_dev, gcs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
