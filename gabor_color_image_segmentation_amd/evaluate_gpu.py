@@ -9,6 +9,8 @@ batches be scored without a device->host round trip of the label maps.
 """
 from __future__ import annotations
 
+import weakref
+
 import numpy as np
 
 from math import pi
@@ -298,13 +300,20 @@ class DeviceTruth:
             torch.cuda.current_stream(dev).synchronize()       # t16 may go (uint8 case): the kernels that read it are done
         self._out = None                                       # (capacity, device result block, pinned host block, views, ...)
         self._scratch = None
+        self._pending = None                                   # weak reference to the submission that owns the result block
+
+    def _uncollected(self):
+        """The submission whose numbers still sit in this truth's ONE result block, or None (collected, or dropped)."""
+        p = self._pending() if self._pending is not None else None
+        return p if p is not None and not p._collected else None
 
     def _buffers(self, n_seg, agreement=False):
         """ONE device block for everything a call returns (counts | under | under_np | seg_max | area | perim) and its pinned
         mirror: one device-to-host copy of a few KB and one synchronisation per call instead of five; the contingency tables
         stay on the device (gcs_region_reduce takes the two sums metrics.py:128-140 needs out of them).
 
-        ONE entry per DeviceTruth, sized to a CAPACITY of segments (the next power of two, at least 8): a data-set loop over
+        ONE entry per DeviceTruth (so one submission at a time: submit_scores_batch_resident refuses a second one while the
+        first is uncollected), sized to a CAPACITY of segments (the next power of two, at least 8): a data-set loop over
         connected-region maps, whose label count differs from batch to batch, reuses it and reallocates - dropping the old
         blocks - only when a batch needs more (the kernels take the capacity as their table stride; segments that do not occur
         have area 0 and perimeter 0 and add nothing to any score). Returns (capacity, device block, pinned block, offsets,
@@ -373,16 +382,29 @@ def _region_scores_batch(under, under_np, area, perim, first, nx, ny):
 
 class _PendingScores:
     """Scores of one batch on their way: kernels and the result copy are enqueued, ``result()`` waits for the copy and does the
-    reference's float arithmetic. Submitting the next batch before collecting this one lets its kernels run under that
-    arithmetic (``all_scores_batch_resident`` = submit + result)."""
+    reference's float arithmetic (``all_scores_batch_resident`` = submit + result). The numbers wait in the pinned result block of
+    their DeviceTruth, and there is ONE such block per DeviceTruth: collect this submission (or drop it) before submitting the
+    next batch against the SAME DeviceTruth. Submitting a batch against ANOTHER DeviceTruth before collecting this one is the
+    intended pipelining: its kernels run under this one's host arithmetic."""
 
     def __init__(self, truth, b, h, w, n_seg, host_blk, offs, event, cap=None, agreement=False):
         self._a = (truth, b, h, w, n_seg, host_blk, offs, event, cap or n_seg)
         self._agreement = agreement
+        self._collected = False
 
     def result(self) -> list:
+        """The scores, once: the result block belongs to the next submission from here on (also when this raises what the
+        reference raises for a degenerate image)."""
+        if self._collected:
+            raise RuntimeError("this submission has been collected already: its result block may hold a later batch by now")
+        self._a[7].synchronize()                                     # the event recorded behind the result copy
+        try:
+            return self._finish()
+        finally:
+            self._collected = True
+
+    def _finish(self) -> list:
         truth, b, h, w, n_seg, host_blk, offs, event, cap = self._a
-        event.synchronize()
         raw = host_blk.numpy()
         view = lambda k, dt: raw[offs[k][0]:offs[k][0] + offs[k][1]].view(dt)
         counts = view("counts", np.uint64)
@@ -421,8 +443,10 @@ class _PendingScores:
 
 def submit_scores_batch_resident(labels, truth: DeviceTruth, n_segments=None, agreement=False) -> _PendingScores:
     """Enqueue the scoring of a (B,H,W) int32 device label batch against resident ground truth; ``.result()`` returns what
-    ``all_scores_batch_device`` returns. One result block per DeviceTruth: collect a submission before submitting the
-    next batch against the SAME DeviceTruth. agreement=True: one more launch on the contingency tables the scorer leaves on the
+    ``all_scores_batch_device`` returns. One result block per DeviceTruth: collect a submission (``.result()``), or drop it,
+    before submitting the next batch against the SAME DeviceTruth - a second submission while the first is uncollected raises
+    RuntimeError instead of overwriting the first one's numbers. Submissions against different DeviceTruth objects pipeline
+    freely. agreement=True: one more launch on the contingency tables the scorer leaves on the
     device (gcs_region_agreement, rows bounded by the labels' maxima) and "PRI", "VoI", "covering" in every dict, from the same
     single copy."""
     import torch
@@ -436,6 +460,9 @@ def submit_scores_batch_resident(labels, truth: DeviceTruth, n_segments=None, ag
     n_seg = int(n_segments) if n_segments is not None else int(labels.max().item()) + 1
     if agreement and h * w < 2:
         raise ValueError(f"region agreement needs at least 2 pixels, got {h * w}")
+    if truth._uncollected() is not None:
+        raise RuntimeError("one result block per DeviceTruth: collect the earlier submission with .result() (or drop it) before "
+                           "submitting the next batch against the same DeviceTruth")
     cap, dev_blk, host_blk, offs, scratch, hist_d, agr_scratch = truth._buffers(n_seg, agreement)
     base = dev_blk.data_ptr()
     ptr = {k: base + o for k, (o, _) in offs.items()}
@@ -461,7 +488,9 @@ def submit_scores_batch_resident(labels, truth: DeviceTruth, n_segments=None, ag
                 host_blk[:used].copy_(dev_blk[:used], non_blocking=True)
         event = torch.cuda.Event()
         event.record(stream)
-    return _PendingScores(truth, b, h, w, n_seg, host_blk, offs, event, cap, agreement)
+    pending = _PendingScores(truth, b, h, w, n_seg, host_blk, offs, event, cap, agreement)
+    truth._pending = weakref.ref(pending)
+    return pending
 
 
 def all_scores_batch_resident(labels, truth: DeviceTruth, n_segments=None, agreement=False) -> list:

@@ -62,3 +62,43 @@ def test_segmentation_with_connectivity_full_size(built):
         ref = so.connected_regions(plain[b])
         assert np.array_equal(got[b], ref)
         assert got[b].max() + 1 >= 8           # at least one region per cluster that occurs
+
+
+# ---- the shapes that change the launch (tests/launch_shape_maps.py): P = 1, single rows / columns, P around the 1 024 threads of
+# cc_rank_kernel, and P > 262 144, where the grid-stride loops of every cc_* kernel take a second step
+from launch_shape_maps import LARGE_SHAPE, SMALL_SHAPES, few_valued, maps  # noqa: E402
+
+
+def _expected(name, lab):
+    if name == "own":                                    # every pixel its own region: SPEC.md §7 numbers them in raster order
+        return np.arange(lab.size).reshape(lab.shape)
+    return so.connected_regions(lab)
+
+
+@pytest.mark.parametrize("h,w", SMALL_SHAPES)
+def test_small_launch_shapes_one_by_one_and_in_batches_of_five(built, h, w):
+    ms = maps(h, w)
+    names = list(ms)
+    want = {n: _expected(n, ms[n]) for n in names}
+    assert np.array_equal(want["own"], so.connected_regions(ms["own"]))        # (cheap here: the direct form is the oracle's)
+    for n in names:
+        assert np.array_equal(_run(ms[n][None])[0], want[n]), n
+    for batch in (names[:5], names[5:], names[::-1][:5]):                       # B = 5, different content per image
+        got = _run(np.stack([ms[n] for n in batch]))
+        for b, n in enumerate(batch):
+            assert np.array_equal(got[b], want[n]), (batch, n)
+
+
+def test_large_launch_shape_second_step_of_the_grid_stride_loops(built):
+    h, w = LARGE_SHAPE
+    assert h * w > 1024 * 256
+    ms = dict(few_valued(h, w), own=maps(h, w)["own"])
+    want = {n: _expected(n, m) for n, m in ms.items()}
+    for n, m in ms.items():                                                     # B = 1
+        got = _run(m[None])[0]
+        assert np.array_equal(got, want[n]), (n, int((got != want[n]).sum()))
+    for pair in (("noise4", "comb_bottom"), ("own", "constant"), ("checker", "noise2"), ("comb_top", "rows1"),
+                 ("cols1", "noise4"), ("patch", "own")):                         # B = 2
+        got = _run(np.stack([ms[n] for n in pair]))
+        for b, n in enumerate(pair):
+            assert np.array_equal(got[b], want[n]), (pair, n)

@@ -167,3 +167,40 @@ def test_resident_scorer_on_merged_maps(built):
             assert g["regions"] == lab.max() + 1
             n += 1
     assert n == 24
+
+
+# ---- the shapes that change the launch (tests/launch_shape_maps.py): P = 1, single rows / columns, P around the 1 024 threads of
+# cc_rank_kernel, and P > 262 144, where the grid-stride loops of every cc_* / mr_* kernel take a second step
+from launch_shape_maps import LARGE_SHAPE, SMALL_SHAPES, few_valued, maps  # noqa: E402
+
+
+@pytest.mark.parametrize("m", [2, 7, 64])
+@pytest.mark.parametrize("h,w", SMALL_SHAPES)
+def test_small_launch_shapes_one_by_one_and_in_batches_of_five(built, h, w, m):
+    ms = maps(h, w)
+    names = list(ms)
+    want = {n: merge_small_regions(ms[n], m) for n in names}
+    for n in names:
+        assert np.array_equal(_run(ms[n][None], m)[0], want[n]), n
+    for batch in (names[:5], names[5:], names[::-1][:5]):                       # B = 5, different content per image
+        got = _run(np.stack([ms[n] for n in batch]), m)
+        for b, n in enumerate(batch):
+            assert np.array_equal(got[b], want[n]), (batch, n)
+
+
+@pytest.mark.parametrize("m", [2, 7, 64])
+def test_large_launch_shape_second_step_of_the_grid_stride_loops(built, m):
+    """Maps of few label values only: the restatement's connected_regions loops over the distinct values (the checkerboard is
+    the every-pixel-a-region case here)."""
+    h, w = LARGE_SHAPE
+    assert h * w > 1024 * 256
+    ms = few_valued(h, w)
+    want = {n: merge_small_regions(v, m) for n, v in ms.items()}
+    for n, v in ms.items():                                                     # B = 1
+        got = _run(v[None], m)[0]
+        assert np.array_equal(got, want[n]), (n, int((got != want[n]).sum()))
+    for pair in (("noise4", "comb_bottom"), ("checker", "constant"), ("comb_top", "noise2"), ("rows1", "cols1"),
+                 ("constant", "patch")):                                         # B = 2
+        got = _run(np.stack([ms[n] for n in pair]), m)
+        for b, n in enumerate(pair):
+            assert np.array_equal(got[b], want[n]), (pair, n)
