@@ -54,7 +54,7 @@ static inline int mtiles(int F) { return (F + 3) / 4; }   // 32-row MFMA tiles o
 //                 unchanged, and 481 x 321 takes 2 426 blocks (2 400 + 11 + 15) instead of 2 501. Deeper banks keep
 //                 main blocks only (a strip block's 8 level-2 parents do not fit a block's 2x2 level-2 slots).
 //
-// SPLIT slab (round 6: banks of at most two levels with D <= 79, i.e. every 4x6-style bank). SPEC.md §3 allows g <= 46 163, but
+// SPLIT slab (round 6: banks of at most two levels with D <= 79, i.e. every 4x6-style bank). SPEC.md §3 allows g <= 46 340, but
 // values of 4096 and more are 5.6e-5 of what BSD500 produces and 2e-7 of the synthetic bench batch (tools/design/
 // narrow_slab_study.py, profiles/r6_notes.md), while every Lloyd pass streamed 16 bits for each. A value is therefore stored
 // as three pieces in three planar arrays per image, tile-major and plane-major as above (a tile = S slots, level L starting at

@@ -4,7 +4,7 @@
 //   smooth_planes_kernel  slab -> level planes: one workgroup per 64 x 16 tile of one plane of one level. It decodes the tile and
 //                         an R-wide apron from the slab (SPEC.md §3 reflect rule at any distance; the TOP nibble only where the
 //                         source tile's flag for the level is set, as the Lloyd pass does), runs the row sums in LDS (32 bits:
-//                         sum w g < 4096 * 46163 < 2^28) and the column sums on the 16-bit halves of the row sums (each below
+//                         sum w g <= 4096 * 46340 < 2^28) and the column sums on the 16-bit halves of the row sums (each below
 //                         2^28 in 32 bits, joined once in 64 bits), rounds and writes h to the plane-major scratch
 //                         [B][D_L][H_L][W_L] u16 of its level.
 //   smooth_pack_kernel    level planes -> slab: one workgroup per slab tile, which owns every byte of the tile. Split slab: LO

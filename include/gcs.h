@@ -95,7 +95,9 @@ size_t gcs_gabor_workspace_bytes(int B, int H, int W, int n_scales);
 
 /* SPEC.md §3: img_dev [B][H][W][3] uint8 -> feats_dev slab (pyramid + filter bank + magnitude).
  * Fills the slot's first stage (script.py:30). Requires H, W >= 8; ksize and shift are those of the packed bank
- * (ksize <= 13 and shift == 8, i.e. every default-style Q15 bank, take the shorter kernels). workspace_dev:
+ * (ksize <= 13 and shift == 8, i.e. every default-style Q15 bank, take the shorter kernels). shift is in 0..23; at shift == 8 the
+ * bounds of gcs_bank_pack keep every response a 16-bit value and re^2 + im^2 < 2^31 (features <= 36 635); with any smaller shift
+ * the caller guarantees that domain for its bank and images (SPEC.md §3 "Value range": features <= 46 340). workspace_dev:
  * gcs_gabor_workspace_bytes() bytes of device scratch, contents undefined before and after. */
 int gcs_gabor_features(const uint8_t *img_dev, int B, int H, int W, const int8_t *packed_dev,
                        const int32_t *bias_dev, int n_scales, int n_orient, int ksize, int shift, void *workspace_dev,

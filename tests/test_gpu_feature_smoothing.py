@@ -10,6 +10,7 @@ import pytest
 import smooth_ref as sr
 from oracle import c_oracle as co
 from oracle import spec_oracle as so
+from slab_layout import flag_bytes as _flags, tile_of_pixels as _tile_of_pixels
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -117,31 +118,6 @@ def _with_patch(img, y0, x0, size=16):
     y0, x0 = min(y0, img.shape[0] - size), min(x0, img.shape[1] - size)
     out[y0:y0 + size, x0:x0 + size] = _grating(size, size)
     return out
-
-
-def _tile_of_pixels(h, w):
-    """Slab tile of every pixel for banks of at most two levels (csrc/common.h)."""
-    pack_r = h >= 8 and w >= 8 and (w & 7) in (1, 2)
-    pack_b = h >= 8 and w >= 8 and (h & 7) in (1, 2)
-    bx_n = w // 8 if pack_r else (w + 7) // 8
-    by_n = h // 8 if pack_b else (h + 7) // 8
-    wm = 8 * bx_n if pack_r else 1 << 29
-    hm = 8 * by_n if pack_b else 1 << 29
-    n_r = ((h + 1) // 2 + 15) // 16 if pack_r else 0
-    nmain = bx_n * by_n
-    y, x = np.mgrid[0:h, 0:w]
-    blk = (y >> 3) * bx_n + (x >> 3)
-    blk = np.where(x >= wm, nmain + ((y >> 1) >> 4), np.where(y >= hm, nmain + n_r + ((x >> 1) >> 4), blk))
-    return blk >> 2
-
-
-def _flags(seg, feats, b, h, w):
-    lib = seg.ops.lib
-    img_bytes = lib.gcs_feature_slab_bytes(1, h, w, 4, 6)
-    s = 36 * 256 + 36 * 64
-    ntiles = img_bytes // (2 * s)
-    raw = feats.cpu().numpy().view(np.uint8)[:b * img_bytes].reshape(b, img_bytes)
-    return raw[:, 2 * s * ntiles:2 * s * ntiles + 4 * ntiles].reshape(b, ntiles, 4), ntiles
 
 
 @pytest.mark.parametrize("h,w", [(64, 96), (81, 121), (321, 481)])
