@@ -31,6 +31,12 @@ class GaborBank:
     exponent: int            # E: tapq = rint(tap * 2**E)
     shift: int               # E - FEATURE_Q
     tapq: np.ndarray
+    color_weight: float = 0.0     # w of SPEC.md §11 (0: a plain Gabor bank)
+    n_gabor_orient: int = 0       # Gabor orientations per scale; 0 = n_orient (a colour bank: n_orient - 1, the last slot is low-pass)
+
+    def __post_init__(self):
+        if self.n_gabor_orient == 0:
+            object.__setattr__(self, "n_gabor_orient", self.n_orient)
 
     @property
     def n_filters(self) -> int:
@@ -49,6 +55,11 @@ class GaborBank:
 def gabor_taps(n_scales=4, n_orient=6, ksize=13, f_max=0.4, ratio=math.sqrt(2.0),
                bandwidth=1.0) -> np.ndarray:
     """Float64 taps ``[F, 2, ksize, ksize]`` (SPEC.md §2, before quantisation)."""
+    return _taps_and_envelopes(n_scales, n_orient, ksize, f_max, ratio, bandwidth)[0]
+
+
+def _taps_and_envelopes(n_scales, n_orient, ksize, f_max, ratio, bandwidth):
+    """``gabor_taps`` and the normalised envelope of every scale, float64 ``[n_scales, ksize, ksize]``."""
     if ksize % 2 != 1 or not (1 <= ksize <= KSIZE_MAX):
         raise ValueError(f"ksize must be odd and <= {KSIZE_MAX}, got {ksize}")
     if n_scales < 1 or n_orient < 1:
@@ -60,34 +71,60 @@ def gabor_taps(n_scales=4, n_orient=6, ksize=13, f_max=0.4, ratio=math.sqrt(2.0)
     kappa = math.sqrt(math.log(2.0) / 2.0) / math.pi * \
         (2.0 ** bandwidth + 1.0) / (2.0 ** bandwidth - 1.0)
     taps = np.empty((n_scales * n_orient, 2, ksize, ksize), np.float64)
+    envs = np.empty((n_scales, ksize, ksize), np.float64)
     for s in range(n_scales):
         freq = f_max / ratio ** s * 2.0 ** (s // 2)      # f_base: cycles per pixel of pyramid level s // 2
         sigma = kappa / freq
         env = np.exp(-(dx * dx + dy * dy) / (2.0 * sigma * sigma))
         env /= env.sum()
+        envs[s] = env
         for o in range(n_orient):
             theta = o * math.pi / n_orient
             phase = 2.0 * math.pi * freq * (dx * math.cos(theta) + dy * math.sin(theta))
             taps[s * n_orient + o, 0] = env * np.cos(phase)
             taps[s * n_orient + o, 1] = env * np.sin(phase)
-    return taps
+    return taps, envs
+
+
+def check_color_weight(color_weight) -> float:
+    """SPEC.md §11 parameter: 0 (off) or a finite 0 < w <= 1."""
+    try:
+        w = float(color_weight)
+    except (TypeError, ValueError):
+        raise ValueError(f"color_weight must be a number, got {color_weight!r}") from None
+    if not (math.isfinite(w) and 0.0 <= w <= 1.0):
+        raise ValueError(f"color_weight must be 0 (off) or in (0, 1], got {color_weight!r}")
+    return w
 
 
 def make_bank(n_scales=4, n_orient=6, ksize=13, f_max=0.4, ratio=math.sqrt(2.0),
-              bandwidth=1.0) -> GaborBank:
-    """Quantise the bank to Q15 taps (SPEC.md §2): shift = 8, i.e. the response's Q7 value is bytes 1..2 of v."""
-    taps = gabor_taps(n_scales, n_orient, ksize, f_max, ratio, bandwidth)
+              bandwidth=1.0, color_weight=0.0) -> GaborBank:
+    """Quantise the bank to Q15 taps (SPEC.md §2): shift = 8, i.e. the response's Q7 value is bytes 1..2 of v.
+
+    ``color_weight`` = w > 0 (SPEC.md §11): every scale gets one more filter behind its ``n_orient`` Gabor filters, the scale's
+    envelope times w with zero imaginary taps. The bank returned then has ``n_orient + 1`` slots per scale and says so in its
+    ``n_orient`` field - that is the shape the C ABI, the slab layout and every kernel see -, with the Gabor orientation count
+    in ``n_gabor_orient``. The exponent comes from the Gabor taps alone: the Gabor slots equal the plain bank's bit for bit."""
+    w = check_color_weight(color_weight)
+    taps, envs = _taps_and_envelopes(n_scales, n_orient, ksize, f_max, ratio, bandwidth)
     exponent = min(TAP_Q, int(math.floor(math.log2(TAPQ_MAX / np.abs(taps).max()))))
     tapq = np.rint(taps * 2.0 ** exponent).astype(np.int64)
+    n_slots = n_orient
+    if w > 0.0:
+        n_slots = n_orient + 1
+        full = np.zeros((n_scales, n_slots, 2, ksize, ksize), np.int64)
+        full[:, :n_orient] = tapq.reshape(n_scales, n_orient, 2, ksize, ksize)
+        full[:, n_orient, 0] = np.rint(w * envs * 2.0 ** exponent).astype(np.int64)
+        tapq = full.reshape(n_scales * n_slots, 2, ksize, ksize)
     if np.abs(tapq).max() > TAPQ_MAX:
         raise AssertionError("tap quantisation overflowed the two-digit range")
     if exponent < FEATURE_Q:
         raise ValueError("bank too peaked for Q7 features")
     if np.any(tapq[:, 1].sum(axis=(1, 2)) != 0):
         raise AssertionError("imaginary taps must sum to zero (odd symmetry)")
-    return GaborBank(n_scales, n_orient, ksize, float(f_max), float(ratio),
+    return GaborBank(n_scales, n_slots, ksize, float(f_max), float(ratio),
                      float(bandwidth), exponent, exponent - FEATURE_Q,
-                     tapq.astype(np.int16))
+                     tapq.astype(np.int16), w, n_orient)
 
 
 def split_digits(tapq: np.ndarray):

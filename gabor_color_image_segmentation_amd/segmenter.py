@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 from . import _lib
-from .bank import GaborBank, make_bank, smoothing_taps
+from .bank import GaborBank, check_color_weight, make_bank, smoothing_taps
 
 # Feature-slab bytes per group of a per-image batch. Large on purpose: measured in round 4 with the current kernels
 # (tools/cache_resident_pass.py, profiles/r4_notes.md "Infinity-Cache-resident groups"): a pass that re-reads a slab small enough
@@ -189,7 +189,7 @@ def _on_device(fn):
 class HipOps:
     """Thin pointer-passer over the C ABI for one device. Stateless apart from the bank."""
 
-    def __init__(self, bank: GaborBank, device, smoothing=0.0):
+    def __init__(self, bank: GaborBank, device, smoothing=0.0, chroma_gain=0):
         torch = _torch()
         if not torch.cuda.is_available():
             raise _lib.GcsError("no HIP device visible: the segmenter has no CPU fallback")
@@ -209,6 +209,7 @@ class HipOps:
         self.packed = torch.from_numpy(packed).to(self.device)
         self.bias = torch.from_numpy(bias).to(self.device)
         self._gabor_ws = None
+        self.chroma_gain = _check_chroma_gain(chroma_gain)        # SPEC.md §11 (0: colour_opponent is never called)
         # SPEC.md §10: the smoothing taps of every scale on the device (K = 0: none, and smooth_features is never called)
         self.smoothing = _check_smoothing(smoothing, bank)
         self._smooth_ws = self.smooth_taps = self.smooth_radius = None
@@ -264,6 +265,23 @@ class HipOps:
                                                self.bank.ksize, self.bank.shift, scratch.data_ptr(),
                                                feats.data_ptr(), self._stream()),
                    "gcs_gabor_features")
+
+    def colour_scratch(self, b, h, w):
+        """The (B,H,W,3) uint8 buffer ``colour_opponent`` writes the transformed batch to (a captured graph must own it)."""
+        return self.torch.empty((b, h, w, 3), dtype=self.torch.uint8, device=self.device)
+
+    @_on_device
+    def colour_opponent(self, imgs, out):
+        """SPEC.md §11: ``out`` = T_g of ``imgs`` with this plan's ``chroma_gain``; both contiguous uint8 tensors of the same
+        number of whole pixels (any byte alignment: slices of a batch qualify), not the same memory."""
+        if self.chroma_gain == 0:
+            raise ValueError("colour_opponent needs HipOps(chroma_gain=g) with g > 0")
+        torch = self.torch
+        if imgs.dtype != torch.uint8 or out.dtype != torch.uint8 or imgs.numel() != out.numel() or imgs.numel() % 3 \
+                or not imgs.is_contiguous() or not out.is_contiguous():
+            raise ValueError("colour_opponent needs two contiguous uint8 tensors of the same number of RGB pixels")
+        _lib.check(self.lib.gcs_colour_opponent(imgs.data_ptr(), imgs.numel() // 3, self.chroma_gain, out.data_ptr(),
+                                                self._stream()), "gcs_colour_opponent")
 
     def smooth_scratch(self, b, h, w):
         """A private smoothing workspace for one (batch, shape): the level planes (see ``smooth_features``)."""
@@ -399,6 +417,18 @@ def _collective(fn, t, **kw):
         fn(t, **kw)
 
 
+def _check_chroma_gain(chroma_gain) -> int:
+    """SPEC.md §11 parameter: the integer 0 (off) or 1..16."""
+    try:
+        g = int(chroma_gain)
+        ok = g == chroma_gain and not isinstance(chroma_gain, bool)
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok or not (0 <= g <= 16):
+        raise ValueError(f"chroma_gain must be the integer 0 (off) or 1..16, got {chroma_gain!r}")
+    return g
+
+
 def _check_smoothing(smoothing, bank) -> float:
     """SPEC.md §10 parameter: a finite K >= 0 (0 = off) whose radius is at most 24 on every scale of ``bank``."""
     try:
@@ -491,7 +521,7 @@ class Segmenter:
 
     def __init__(self, n_scales=4, n_orient=6, k=8, n_iter=10, ksize=13, f_max=0.4,
                  ratio=math.sqrt(2.0), bandwidth=1.0, connectivity=False, device="cuda:0", ops=None,
-                 slab_candidates=1, min_region_size=0, smoothing=0.0):
+                 slab_candidates=1, min_region_size=0, smoothing=0.0, color_weight=0.0, chroma_gain=0):
         if not (1 <= k <= _lib.K_MAX):
             raise ValueError(f"k must be in 1..{_lib.K_MAX}")
         if n_iter < 1:
@@ -502,11 +532,19 @@ class Segmenter:
         self.debug = DebugSwitches(os.environ.get("GCS_DEBUG", ""))     # measurement / test switches (see the class)
         self.connectivity = bool(connectivity)     # SPEC.md §7 post-pass
         self.min_region_size = int(min_region_size)  # SPEC.md §9 post-pass (> 0: connected regions, small ones merged)
-        self.bank = make_bank(n_scales, n_orient, ksize, f_max, ratio, bandwidth)
+        self.color_weight = check_color_weight(color_weight)        # SPEC.md §11: a low-pass slot behind every scale's filters
+        self.chroma_gain = _check_chroma_gain(chroma_gain)          # SPEC.md §11: T_g in front of the Gabor stage
+        self.bank = make_bank(n_scales, n_orient, ksize, f_max, ratio, bandwidth, self.color_weight)
         self.smoothing = _check_smoothing(smoothing, self.bank)     # SPEC.md §10, between the Gabor stage and k-means
-        self.ops = ops if ops is not None else HipOps(self.bank, device, self.smoothing)
+        self.ops = ops if ops is not None else HipOps(self.bank, device, self.smoothing, self.chroma_gain)
         if self.smoothing > 0 and getattr(self.ops, "smoothing", 0.0) != self.smoothing:
             raise ValueError("Segmenter(smoothing=K, ops=...) needs ops built with the same smoothing")
+        if getattr(self.ops, "chroma_gain", 0) != self.chroma_gain:
+            raise ValueError("Segmenter(chroma_gain=g, ops=...) needs ops built with the same chroma_gain")
+        ops_bank = getattr(self.ops, "bank", None)
+        if getattr(ops_bank, "color_weight", 0.0) != self.color_weight or \
+                (self.color_weight > 0 and (ops_bank.n_scales, ops_bank.n_orient) != (self.bank.n_scales, self.bank.n_orient)):
+            raise ValueError("Segmenter(color_weight=w, ops=...) needs ops built for the same colour bank")
         # feature-slab allocations to time at first use of a large workspace shape (see _place_slab). 1 = take the first
         # one (the library default: no extra memory, no host synchronisation, graph-capturable); bench.py asks for 2.
         self.slab_candidates = int(self.debug.slab_candidates or slab_candidates)
@@ -545,6 +583,8 @@ class Segmenter:
                       cent=self.ops.new_centroids(n_sets, self.k), sums=self.ops.new_sums(n_sets, self.k))
             if self.smoothing > 0:
                 ws["smooth"] = self.ops.smooth_scratch(g, h, w)
+            if self.chroma_gain > 0:
+                ws["colour"] = self.ops.colour_scratch(g, h, w)
             self._place_slab(ws, g, h, w, n_sets)
             # keep the eight most recent (batch, shape, mode) triples resident (a data set alternating landscape and
             # portrait batches, each with a remainder batch at its end, beside a global-codebook run, would otherwise
@@ -654,13 +694,21 @@ class Segmenter:
                   cent=self.ops.new_centroids(n_sets, self.k), sums=self.ops.new_sums(n_sets, self.k))
         if self.smoothing > 0:
             ws["smooth"] = self.ops.smooth_scratch(n, h, w)
+        if self.chroma_gain > 0:
+            ws["colour"] = self.ops.colour_scratch(n, h, w)
         return ws
 
     def _features(self, imgs, ws, b, h, w):
-        """The Gabor stage into ``ws["feats"]``, then the smoothing of SPEC.md §10 when it is on."""
-        self.ops.gabor_features(imgs, ws["feats"])
+        """The transform of SPEC.md §11 when ``chroma_gain`` is on, the Gabor stage into ``ws["feats"]``, then the smoothing of
+        SPEC.md §10 when it is on."""
+        self.ops.gabor_features(self._opponent(imgs, ws["colour"]) if self.chroma_gain > 0 else imgs, ws["feats"])
         if self.smoothing > 0:
             self.ops.smooth_features(ws["feats"], b, h, w, scratch=ws["smooth"])
+
+    def _opponent(self, imgs, colour):
+        """T_g of ``imgs`` (SPEC.md §11) into the plan-owned buffer ``colour``; returns it. The caller's tensor is not changed."""
+        self.ops.colour_opponent(imgs, colour)
+        return colour
 
     def shard_rows(self, height, world, rank):
         """``shard_rows`` for THIS plan's bank (its pyramid depth and kernel size decide alignment and halo)."""
@@ -694,7 +742,8 @@ class Segmenter:
         if (r0 - s0 < halo and s0 > 0) or (s0 + hs - r1 < halo and s0 + hs < height):
             raise ValueError(f"interior strip edges need {halo} halo rows (use shard_rows)")
         ws = self._tail_workspace(b, hs, w, "global")
-        self.ops.gabor_features(strip, ws["feats"])
+        # (T_g is per pixel: a strip with its halo rows transforms on its own)
+        self.ops.gabor_features(self._opponent(strip, ws["colour"]) if self.chroma_gain > 0 else strip, ws["feats"])
         k, dfeat = self.k, self.bank.n_features
         import torch.distributed as td
         use_dist = td.is_available() and td.is_initialized() and td.get_world_size(dist_group) > 1
@@ -781,6 +830,8 @@ class Segmenter:
         imgs = imgs.contiguous()
         b, h, w, _ = imgs.shape
         feats = self.ops.feature_slab(b, h, w)
+        if self.chroma_gain > 0:
+            imgs = self._opponent(imgs, self.ops.colour_scratch(b, h, w))
         self.ops.gabor_features(imgs, feats)
         if self.smoothing > 0:
             self.ops.smooth_features(feats, b, h, w)
@@ -849,7 +900,10 @@ class Segmenter:
                     st["dev_in"][g0:g1].copy_(st["pin_in"][g0:g1], non_blocking=True)
                     st["ev"][i].record(st["copy"])
                 cur.wait_event(st["ev"][i])
-                ops.gabor_features(st["dev_in"][g0:g1], ws["feats"][g0 * per_img:])
+                chunk = st["dev_in"][g0:g1]
+                if self.chroma_gain > 0:                           # (a chunk of 481 x 321 images starts at any byte)
+                    chunk = self._opponent(chunk, ws["colour"][g0:g1])
+                ops.gabor_features(chunk, ws["feats"][g0 * per_img:])
             if self.smoothing > 0:                                 # every chunk's Gabor stage is in front of it on `cur`
                 ops.smooth_features(ws["feats"], b, h, w, scratch=ws["smooth"])
             dev_out = st["dev_out"] if out_dtype == np.uint8 else st["dev_out32"]
@@ -914,6 +968,7 @@ class Segmenter:
                 # block recycled, whenever a later call needs a larger one)
                 scratch = self.ops.gabor_scratch(b, h, w)
                 smooth = ws.get("smooth")                  # (allocated with the workspace, outside the capture)
+                colour = ws.get("colour")                  # (the same: SPEC.md §11's transformed batch)
 
                 # (the closure must not capture `self`: the entry lives in self._graphs, and a Segmenter inside a reference
                 # cycle is freed - with its graphs, streams, pinned and device buffers - only when the cyclic collector
@@ -921,7 +976,9 @@ class Segmenter:
                 ops, k, n_iter, debug = self.ops, self.k, self.n_iter, self.debug
 
                 def step():
-                    ops.gabor_features(dev_in, ws["feats"], scratch=scratch)
+                    if colour is not None:
+                        ops.colour_opponent(dev_in, colour)
+                    ops.gabor_features(dev_in if colour is None else colour, ws["feats"], scratch=scratch)
                     if smooth is not None:
                         ops.smooth_features(ws["feats"], b, h, w, scratch=smooth)
                     lloyd(ops, ws["feats"], b, h, w, k, n_iter, mode, ws["labels"], ws["partials"], ws["cent"],
@@ -1145,7 +1202,8 @@ class _StreamPipe:
             cur.wait_event(st["ev_up"][i])
             if n >= n_slots:
                 cur.wait_event(st["ev_down"][i])                   # dev_out[i] has been downloaded
-            ops.gabor_features(st["dev_in"][i], ws["feats"])
+            ops.gabor_features(seg._opponent(st["dev_in"][i], ws["colour"]) if seg.chroma_gain > 0 else st["dev_in"][i],
+                               ws["feats"])
             if seg.smoothing > 0:
                 ops.smooth_features(ws["feats"], b, h, w, scratch=ws["smooth"])
             lloyd(ops, ws["feats"], b, h, w, seg.k, seg.n_iter, self.mode, ws["labels"], ws["partials"], ws["cent"],

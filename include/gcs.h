@@ -312,6 +312,17 @@ size_t gcs_smooth_workspace_bytes(int B, int H, int W, int n_scales, int n_orien
 int gcs_smooth_features(uint16_t *feats_dev, int B, int H, int W, int n_scales, int n_orient, const int32_t *taps_dev,
                         const int32_t *radius_dev, void *workspace_dev, gcs_stream_t stream);
 
+/* ---- opponent colours (SPEC.md §11) ------------------------------------------------------------- */
+
+/* img_dev uint8 [n_pixels][3] interleaved RGB -> out_dev uint8 [n_pixels][3] interleaved (Y, Co, Cg) of T_gain (SPEC.md §11:
+ * Y = (R + 2G + B + 2) >> 2, Co = clamp(128 + ((gain (R - B)) >> 1), 0, 255), Cg = clamp(128 + ((gain (2G - R - B)) >> 2), 0, 255),
+ * arithmetic shifts). Both pointers may have ANY byte alignment (a sub-batch of 481 x 321 images starts at any byte) and n_pixels
+ * may be any count >= 1: exactly the bytes [0, 3 n_pixels) of img_dev are read and of out_dev written. Stream-ordered, one
+ * launch, no allocation, no host synchronisation (capturable). GCS_EINVAL, with nothing launched, for a NULL pointer, a gain
+ * outside 1..16, n_pixels == 0 and for an out_dev range that overlaps the img_dev range (not in place).
+ * Added within ABI 18: a new entry point changes no existing call, so GCS_ABI_VERSION did not move. */
+int gcs_colour_opponent(const uint8_t *img_dev, size_t n_pixels, int gain, uint8_t *out_dev, gcs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
