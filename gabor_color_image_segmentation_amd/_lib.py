@@ -39,6 +39,8 @@ SIGNATURES = {
     "gcs_kmeans_reduce": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "gcs_kmeans_finalize": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "gcs_kmeans_reduce_finalize": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "gcs_kmeans_fused_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "gcs_kmeans_pass_fused": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "gcs_download": (_i, [_vp, _vp, _sz, _vp]),
     "gcs_labels_widen": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "gcs_selftest_isqrt": (_i, [C.c_uint, _vp, _vp]),

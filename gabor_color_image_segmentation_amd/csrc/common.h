@@ -270,6 +270,20 @@ __device__ __forceinline__ unsigned gcs_slab_value(const unsigned char *feats, c
 // lines (16 consecutive elements of ITS row: no line is shared between workgroups - with the element-major layout of
 // round 1 every 8-byte store was a partial-line write and the stores of a pass cost 4 us); the reduce kernel reads a
 // chunk's rows as one contiguous block. The padding elements of the last chunk are never written and never used.
+//
+// SELF-UPDATING passes (round 7: gcs_kmeans_pass_fused, the single-rank loop of the 4x6-style banks with k <= 8) keep no private
+// rows: a workgroup adds its k (D + 1) sums with 64-bit vector atomics into one of `rows` shared rows of its codebook set,
+//     sums [3][n_sets][rows][k (D + 1)] uint64   (three buffers in rotation, see GcsFold)
+// and the NEXT pass folds the `rows` rows and applies the SPEC.md §4 update in its own prologue. Integer sums: any order, same bits.
+struct GcsFold {
+    unsigned long long *prev;         // the sums pass t - 1 accumulated, all sets (NULL on pass 0: the centroids are the §4 init pixels)
+    unsigned long long *clear;        // the buffer pass t + 1 accumulates into: cleared by this pass (last read by pass t - 1)
+    uint16_t *cent_new;               // [n_sets][k][D]: the centroids this pass uses, written by one workgroup per set (pass t + 1 reads
+                                      // them back for its empty clusters: two arrays in ping-pong, `cent` of the launch is the other)
+    uint16_t *cent_out;               // the caller's copy of the same
+    unsigned *ticket;                 // last pass only: counts finished workgroups; the last one clears `prev` and the ticket
+    int rows;                         // shared rows per set; a workgroup adds into row (flat workgroup index) % rows
+};
 constexpr int KP_PCH = 16;
 __host__ __device__ __forceinline__ int partial_chunks(int row_len) { return (row_len + KP_PCH - 1) / KP_PCH; }
 __device__ __forceinline__ size_t partial_index(int per_image, int b, int part, int parts, int nb, int i, int row_len) {

@@ -7,7 +7,9 @@
 //                            replicated over their 2^L x 2^L blocks while they are staged into LDS. 4x6-style banks
 //                            (at most two levels, D <= 79) read the SPLIT slab: 12 of the 16 bits of every value, the
 //                            last 4 for flagged tiles only (template flag SPLIT); with k <= 8 their level 1 stays COMPACT
-//                            in LDS (CL1: block rows held as even | odd pixels, no replication).
+//                            in LDS (CL1: block rows held as even | odd pixels, no replication). The CL1 kernels also exist as
+//                            SELF-UPDATING passes (template flag FUSED, entry gcs_kmeans_pass_fused): the single-rank loop is then
+//                            n_iter launches of this kernel and nothing else - no init, no reduce.
 //   kmeans_pass_native_kernel  the pass for deep banks (BASELINE config 4): every level at its own resolution.
 //   kmeans_assign_kernel     generic pass for D >= 208: exact integer argmin via fp32 byte-digit FMAs (all partial
 //                            sums < 2^24, hence exact), LDS-replicated u32 accumulators.
@@ -17,6 +19,7 @@
 // (csrc/common.h: main blocks and packed edge strips) is the passes' own business.
 // Nothing here allocates, frees or synchronises; every entry point enqueues on the caller's stream.
 #include "common.h"
+#include <stdlib.h>
 #include <type_traits>
 
 #define LAYOUT_OR_FAIL(lo, who)                                        \
@@ -331,13 +334,19 @@ extern "C" int gcs_debug_kp_phases(unsigned long long *out) {
 // tile = 16 low bytes + 8 bytes of MID nibbles (+ 8 bytes of TOP nibbles when the tile's flag word says that one of them is set),
 // unpacked into the same LDS image as the wide slab's: 16 pixels of a level-0 plane row, or the 4 x 4 parents of one block of a
 // level-1 plane, replicated over the block's 64 pixels.
-template <int KT, int NST, int DSTEPS, int WAVES, bool SPLIT = false, int L0T = 0>
+// FUSED (round 7, the CL1 kernels only): the self-updating pass of gcs_kmeans_pass_fused (GcsFold, csrc/common.h). The prologue makes
+// the centroids itself - the SPEC.md §4 init pixels on pass 0, else the fold of the previous pass's shared rows and the §4 update -,
+// the epilogue adds the workgroup's sums into a shared row with vector atomics instead of storing a private row, and every
+// workgroup clears its slice of the buffer the NEXT pass adds into. `cent` = the previous pass's centroids (an empty cluster keeps
+// its own), `partials` = row 0 of the buffer this pass adds into (NULL on the last pass). A compile-time mode: the other
+// instantiations never look at `fz`.
+template <int KT, int NST, int DSTEPS, int WAVES, bool SPLIT = false, int L0T = 0, bool FUSED = false>
 __global__ __launch_bounds__(64 * WAVES, (WAVES == 8 ? 2
                                           : DSTEPS == KP_DSTEPS_NARROW && KT == 1 && NST <= (SPLIT ? 3 : 6) ? GCS_KP_WAVES
                                           : DSTEPS == KP_DSTEPS_NARROW ? 2 : 1)) void kmeans_pass_mfma_kernel(
     const unsigned char *__restrict__ feats, const uint16_t *__restrict__ cent, GcsLayout lo, int K, int per_image,
     int parts, int reverse, int row_lo, int row_hi, uint64_t *__restrict__ partials, void *__restrict__ raster,
-    int raster_u8, int nt_flag) {                      // (nt_flag: the split slab's nt_limit, see lloyd_pass; unused by the wide kernels)
+    int raster_u8, int nt_flag, GcsFold fz) {          // (nt_flag: the split slab's nt_limit, see lloyd_pass; unused by the wide kernels)
     constexpr int KP_ROWS = 16 * DSTEPS, KP_DSTEPS = DSTEPS, KP_NT = 2 * DSTEPS;
     constexpr int NTHR = 64 * WAVES;                         // threads per workgroup
     constexpr int NT_OWN = WAVES == 8 ? (KP_NT + 1) / 2 : KP_NT;   // update plane tiles a wave accumulates
@@ -351,6 +360,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 8 ? 2
     constexpr int KP_FLAGS = 320;                            // tiles of one workgroup whose flag is kept (more: read as set, always exact)
     __shared__ unsigned char s_flag[SPLIT ? KP_FLAGS : 4];
     static_assert(!SPLIT || (DSTEPS == KP_DSTEPS_NARROW && WAVES == 4), "the split slab is the narrow pass's");
+    static_assert(!FUSED || (SPLIT && KT == 1), "the self-updating pass exists for the CL1 kernels");
 
     // either output may be absent (host contract): raster == NULL on the passes whose assignment nobody reads (every
     // pass but the last), partials == NULL on the last pass, whose sums nobody reads (no update phase, no fold)
@@ -375,6 +385,53 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 8 ? 2
     // ---- centroids -> LDS scratch (borrowed from the tile buffer): [8*KT clusters][KP_ROWS planes] u16 in PHYSICAL
     //      plane order, stored offset-binary (c ^ 0x8080: low byte = digit cl, high byte = digit ch), zero outside K x D.
     uint16_t *cs = reinterpret_cast<uint16_t *>(s_tile);
+    if constexpr (FUSED) {
+        const int D1 = D + 1, row_len = K * D1;
+        const int set = per_image ? b : 0;
+        const int wg = b * (int)gridDim.x + part, nwg = (int)(gridDim.x * gridDim.y);
+        {   // this workgroup's slice of the buffer the next pass adds into
+            const long long total = (long long)(per_image ? (int)gridDim.y : 1) * fz.rows * row_len;
+            for (long long i = (long long)wg * NTHR + tid; i < total; i += (long long)nwg * NTHR) fz.clear[i] = 0ull;
+        }
+        // the set's sums of the previous pass: its shared rows folded, in the tile buffer behind the centroid scratch
+        unsigned long long *fsum = reinterpret_cast<unsigned long long *>(s_tile + 8 * KT * KP_ROWS * 2);
+        static_assert(8 * KT * KP_ROWS * 2 % 16 == 0 && 8 * KT * KP_ROWS * 2 + 8 * (8 * KT * KP_ROWS) <= KP_ROWS * KP_PITCH,
+                      "the folded sums do not fit behind the centroid scratch");
+        const bool later = fz.prev != nullptr;
+        if (later) {
+            const unsigned long long *pv = fz.prev + (size_t)set * fz.rows * row_len;
+            for (int i = tid; i < row_len; i += NTHR) {
+                unsigned long long s = 0;
+                for (int r = 0; r < fz.rows; ++r) s += pv[(size_t)r * row_len + i];
+                fsum[i] = s;
+            }
+            __syncthreads();
+        }
+        const bool writer = part == 0 && (per_image || b == 0);          // one workgroup per set publishes the centroids
+        const long long P = (long long)lo.H * lo.W;
+        for (int i = tid; i < 8 * KT * KP_ROWS; i += NTHR) {
+            const int j = i / KP_ROWS, r = i % KP_ROWS;
+            int e = 0;                                               // logical feature of physical plane r (kp_logical_of: levels unrolled)
+            if (r >= lo.row0[0] && r < lo.row0[0] + lo.DL[0]) e = kp_logical_of<0>(lo, r - lo.row0[0]);
+            if (lo.n_levels > 1 && r >= lo.row0[1] && r < lo.row0[1] + lo.DL[1]) e = kp_logical_of<1>(lo, r - lo.row0[1]);
+            unsigned v = 0;
+            if (j < K && r < D) {
+                if (later) {
+                    const unsigned long long c = fsum[j * D1 + D], s = fsum[j * D1 + e];
+                    v = c > 0 ? (unsigned)((2 * s + c) / (2 * c)) : (unsigned)cset[j * D + e];
+                } else {
+                    const long long p = ((2LL * j + 1) * P) / (2LL * K);
+                    v = gcs_slab_value(feats, lo, set, r, (int)(p / lo.W), (int)(p % lo.W));
+                }
+                if (writer) {
+                    fz.cent_new[((size_t)set * K + j) * D + e] = (uint16_t)v;
+                    fz.cent_out[((size_t)set * K + j) * D + e] = (uint16_t)v;
+                }
+                v ^= 0x8080u;
+            }
+            cs[i] = (uint16_t)v;
+        }
+    } else
     for (int i = tid; i < 8 * KT * KP_ROWS; i += NTHR) {
         const int j = i / KP_ROWS, r = i % KP_ROWS;
         int e = 0;                                               // logical feature of physical plane r (kp_logical_of: levels unrolled)
@@ -1068,6 +1125,21 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 8 ? 2
     }
     KP_PHASE_STORE;
 
+    if constexpr (FUSED) {
+        // the last pass leaves the buffers as a call finds them: the one it read is cleared by the workgroup that finishes last
+        // (a ticket taken at the very end, never waited for: every workgroup has read `prev` long before any takes one)
+        if (!do_acc && fz.prev != nullptr) {
+            __shared__ int s_last;
+            const int nwg = (int)(gridDim.x * gridDim.y);
+            if (tid == 0) s_last = atomicAdd(fz.ticket, 1u) == (unsigned)(nwg - 1);
+            __syncthreads();
+            if (s_last) {
+                const long long total = (long long)(per_image ? (int)gridDim.y : 1) * fz.rows * K * (D + 1);
+                for (long long i = tid; i < total; i += NTHR) fz.prev[i] = 0ull;
+                if (tid == 0) *fz.ticket = 0u;
+            }
+        }
+    }
     if (!do_acc) return;
     if constexpr (UPD2) {
         // ---- fold (UPD2): rows = (cluster, byte), columns = planes
@@ -1098,6 +1170,13 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 8 ? 2
                 { const int q = kp_plane_on_level<3>(lo, c, f); pe = q >= 0 ? q : pe; }
                 out = (folded(j, 0, pe) + 128 * nj) + 256 * (folded(j, 1, pe) + 128 * nj);
             }
+            if constexpr (FUSED) {
+                // (vector atomic, result unused; a zero - an empty cluster's row - adds nothing)
+                const int wg = b * (int)gridDim.x + part;
+                unsigned long long *row = reinterpret_cast<unsigned long long *>(partials) +
+                                          ((size_t)(per_image ? b : 0) * fz.rows + (size_t)(wg % fz.rows)) * (K * D1);
+                if (out != 0) atomicAdd(&row[i], (unsigned long long)out);
+            } else
             partials[partial_index(per_image, b, part, parts, (int)gridDim.y, i, K * D1)] = (uint64_t)out;
         }
     }
@@ -1764,7 +1843,7 @@ static int lloyd_pass(const uint16_t *feats, const uint16_t *cent, int B, int H,
 #define GCS_KP_LAUNCHW(KT_, NST_, DS_, WV_)                                                                              \
     hipLaunchKernelGGL((kmeans_pass_mfma_kernel<KT_, NST_, DS_, WV_>), dim3(parts, B), dim3(64 * WV_), 0, stream,         \
                        reinterpret_cast<const unsigned char *>(feats), cent, lo, k, n_sets == B ? 1 : 0, parts,          \
-                       reverse ? 1 : 0, row_lo, row_hi, partials, lab_out, lab_u8, nt_flag)
+                       reverse ? 1 : 0, row_lo, row_hi, partials, lab_out, lab_u8, nt_flag, GcsFold{})
 #define GCS_KP_LAUNCH(KT_, NST_, DS_) GCS_KP_LAUNCHW(KT_, NST_, DS_, 4)
         const int nchunk = lo.tile_bytes / 16;
         const int nst = (nchunk + 255) / 256;                         // staging chunks per thread (4-wave workgroups)
@@ -1776,7 +1855,7 @@ static int lloyd_pass(const uint16_t *feats, const uint16_t *cent, int B, int H,
 #define GCS_KP_LAUNCHS(KT_, NR_, ...)                                                                                          \
     hipLaunchKernelGGL((kmeans_pass_mfma_kernel<KT_, NR_, KP_DSTEPS_NARROW, 4, true __VA_OPT__(,) __VA_ARGS__>), dim3(parts, B), dim3(256), 0, stream, \
                        reinterpret_cast<const unsigned char *>(feats), cent, lo, k, n_sets == B ? 1 : 0, parts,             \
-                       reverse ? 1 : 0, row_lo, row_hi, partials, lab_out, lab_u8, nt_limit)
+                       reverse ? 1 : 0, row_lo, row_hi, partials, lab_out, lab_u8, nt_limit, GcsFold{})
             // (measured and dropped, profiles/r6_notes.md: eight waves per workgroup at two workgroups per CU - 0.28 against 0.15 ms
             //  per pass -, the assign A fragments in LDS, the second sub-tile's transposed reads under the first one's epilogue)
             if (k <= 8 && rounds <= 3 && lo.DL[0] >= 32) { GCS_KP_LAUNCHS(1, 3, 2); }
@@ -1869,6 +1948,83 @@ extern "C" int gcs_kmeans_assign_raster(const uint16_t *feats, const uint16_t *c
     if (!out) return gcs_fail(GCS_EINVAL, "gcs_kmeans_assign_raster: NULL pointer");
     return lloyd_pass(feats, cent, B, H, W, n_scales, n_orient, k, n_sets, 0, H, reverse, scratch_labels, nullptr, out,
                       out_u8 ? 1 : 0, stream);
+}
+
+// ------------------------------------------------------------------- self-updating passes (single rank, whole images)
+// The Lloyd loop as n_iter launches: no init kernel, no reduce launches (GcsFold in csrc/common.h, FUSED in kmeans_pass_mfma_kernel).
+// Which banks: those that take the CL1 kernels with three staging rounds - the split slab (at most two pyramid levels, D <= 79),
+// k <= 8, a tile of at most 12 288 slots: every 4x6-style bank. Everything else keeps the init / pass / reduce launches.
+//
+// Shared rows per set: a workgroup adds into row (its index) % rows. ONE row is the measured optimum (profiles/r7_notes.md: 768
+// workgroups behind every address cost the fold nothing that shows, while every further row is one more dependent read in every
+// workgroup's prologue: the 10-pass loop takes 1.25 ms with 1 row, 1.28 with 8, 1.42 with 32, 1.61 with 64 - against 1.32 ms for
+// init / pass / reduce). GCS_KP_FOLD_ROWS in the environment (1 .. 64, read once; one global codebook only) repeats that sweep.
+#ifndef KP_FOLD_ROWS
+#define KP_FOLD_ROWS 1
+#endif
+static int fold_rows(int B, int parts, int n_sets) {
+    if (n_sets == B && B > 1) return 1;
+    static const int env = [] {
+        const char *e = getenv("GCS_KP_FOLD_ROWS");
+        const int v = e ? atoi(e) : 0;
+        return v >= 1 && v <= 64 ? v : KP_FOLD_ROWS;
+    }();
+    const long long wgs = (long long)B * parts;
+    return (int)(wgs < env ? wgs : env);
+}
+static bool fused_bank(const GcsLayout &lo, int k) {
+    return lo.split && k >= 1 && k <= 8 && ((lo.S >> 4) + 255) / 256 <= 3;
+}
+// workspace: [3 sum buffers][2 centroid arrays][ticket], every piece a multiple of 256 bytes
+static size_t fused_sum_bytes(const GcsLayout &lo, int k, int n_sets, int rows) {
+    return ((size_t)n_sets * rows * k * (lo.D + 1) * 8 + 255) & ~(size_t)255;
+}
+static size_t fused_cent_bytes(const GcsLayout &lo, int k, int n_sets) {
+    return ((size_t)n_sets * k * lo.D * 2 + 255) & ~(size_t)255;
+}
+extern "C" size_t gcs_kmeans_fused_workspace_bytes(int B, int H, int W, int n_scales, int n_orient, int k, int n_sets) {
+    GcsLayout lo;
+    if (B <= 0 || B > 65535 || !gcs_make_layout(H, W, n_scales, n_orient, &lo) || (n_sets != 1 && n_sets != B) || !fused_bank(lo, k))
+        return 0;
+    const int rows = fold_rows(B, (int)gcs_kmeans_parts_per_image(B, H, W), n_sets);
+    return 3 * fused_sum_bytes(lo, k, n_sets, rows) + 2 * fused_cent_bytes(lo, k, n_sets) + 256;
+}
+
+extern "C" int gcs_kmeans_pass_fused(const uint16_t *feats, int B, int H, int W, int n_scales, int n_orient, int k, int n_sets,
+                                     int reverse, int pass, int last, void *workspace, uint16_t *cent, void *out, int out_u8,
+                                     gcs_stream_t stream) {
+    if (!feats || !workspace || !cent || (last && !out))
+        return gcs_fail(GCS_EINVAL, "gcs_kmeans_pass_fused: NULL pointer (the last pass needs its label map)");
+    LAYOUT_OR_FAIL(lo, "gcs_kmeans_pass_fused");
+    if (pass < 0) return gcs_fail(GCS_EINVAL, "gcs_kmeans_pass_fused: pass must be >= 0");
+    if (gcs_kmeans_fused_workspace_bytes(B, H, W, n_scales, n_orient, k, n_sets) == 0)
+        return gcs_fail(GCS_EINVAL, "gcs_kmeans_pass_fused: no self-updating pass for this bank / k / n_sets (gcs_kmeans_fused_workspace_bytes == 0)");
+    if ((long long)B * lo.ntiles > 0x1fffffffLL || (unsigned long long)lo.img_bytes >= (1ull << 32))
+        return gcs_fail(GCS_EINVAL, "gcs_kmeans_pass_fused: batch or image too large for one launch");
+    const int parts = (int)gcs_kmeans_parts_per_image(B, H, W);
+    const int rows = fold_rows(B, parts, n_sets);
+    const size_t sb = fused_sum_bytes(lo, k, n_sets, rows), cb = fused_cent_bytes(lo, k, n_sets);
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    auto sums = [&](int t) { return reinterpret_cast<unsigned long long *>(ws + (size_t)(t % 3) * sb); };
+    auto cents = [&](int t) { return reinterpret_cast<uint16_t *>(ws + 3 * sb + (size_t)(t & 1) * cb); };
+    GcsFold fz;
+    fz.prev = pass > 0 ? sums(pass - 1) : nullptr;
+    fz.clear = sums(pass + 1);
+    fz.cent_new = cents(pass);
+    fz.cent_out = cent;
+    fz.ticket = reinterpret_cast<unsigned *>(ws + 3 * sb + 2 * cb);
+    fz.rows = rows;
+    uint64_t *acc = last ? nullptr : reinterpret_cast<uint64_t *>(sums(pass));
+    const int nt_limit = kp_nt_limit(lo, B, n_sets, lo.tile_bytes / 4 * 3);
+#define GCS_KP_LAUNCHF(L0T_)                                                                                                   \
+    hipLaunchKernelGGL((kmeans_pass_mfma_kernel<1, 3, KP_DSTEPS_NARROW, 4, true, L0T_, true>), dim3(parts, B), dim3(256), 0, stream, \
+                       reinterpret_cast<const unsigned char *>(feats), cents(pass + 1), lo, k, n_sets == B ? 1 : 0, parts,     \
+                       reverse ? 1 : 0, 0, H, acc, last ? out : nullptr, out_u8 ? 1 : 0, nt_limit, fz)
+    if (lo.DL[0] >= 32) { GCS_KP_LAUNCHF(2); }
+    else { GCS_KP_LAUNCHF(0); }
+#undef GCS_KP_LAUNCHF
+    GCS_CHECK_LAUNCH("gcs_kmeans_pass_fused");
+    return GCS_OK;
 }
 
 // sums[set][e] = sum over the set's rows of element e (layout: partial_index in common.h). Integer sums: any order gives

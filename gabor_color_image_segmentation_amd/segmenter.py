@@ -217,6 +217,9 @@ class HipOps:
             taps, radius = smoothing_taps(self.smoothing, ns, no, bank.f_max, bank.ratio)
             self.smooth_taps = torch.from_numpy(taps).to(self.device)
             self.smooth_radius = torch.from_numpy(radius).to(self.device)
+        # the self-updating Lloyd passes: only with a library that exports them (tools/ab.py loads older builds in one process)
+        self.has_fused = all(n in _lib.SIGNATURES and hasattr(self.lib, n)
+                             for n in ("gcs_kmeans_fused_workspace_bytes", "gcs_kmeans_pass_fused"))
 
     # ---- allocation helpers (bytes buffers; layouts are opaque, see gcs.h)
     def empty_bytes(self, n):
@@ -230,6 +233,12 @@ class HipOps:
 
     def partial_slab(self, b, h, w, k):
         return self.empty_bytes(self.lib.gcs_kmeans_partial_bytes(b, h, w, self.bank.n_features, k))
+
+    def fused_workspace(self, b, h, w, k, n_sets):
+        """The workspace of the self-updating Lloyd passes (``lloyd(fold=...)``), zeroed as gcs.h asks, or None when the library
+        or this bank / k has no such pass."""
+        n = self.lib.gcs_kmeans_fused_workspace_bytes(b, h, w, *self._bk, k, n_sets) if self.has_fused else 0
+        return self.torch.zeros(int(n), dtype=self.torch.uint8, device=self.device) if n else None
 
     def _stream(self):
         return self.torch.cuda.current_stream(self.device).cuda_stream
@@ -317,10 +326,23 @@ class HipOps:
         _lib.check(self.lib.gcs_kmeans_init(feats.data_ptr(), b, h, w, *self._bk, k, n_sets,
                                             cent.data_ptr(), self._stream()), "gcs_kmeans_init")
 
+    def _pass_fused(self, feats, cent, b, h, w, k, n_sets, fused, reverse, out=None):
+        fold, t = fused
+        self._check_dev(fold)
+        _lib.check(self.lib.gcs_kmeans_pass_fused(
+            feats.data_ptr(), b, h, w, *self._bk, k, n_sets, 1 if reverse else 0, t, 0 if out is None else 1,
+            fold.data_ptr(), cent.data_ptr(), None if out is None else out.data_ptr(),
+            1 if out is not None and out.dtype == self.torch.uint8 else 0, self._stream()), "gcs_kmeans_pass_fused")
+
     @_on_device
-    def assign_accumulate(self, feats, cent, b, h, w, k, n_sets, labels, partials, rows=None, reverse=False):
+    def assign_accumulate(self, feats, cent, b, h, w, k, n_sets, labels, partials, rows=None, reverse=False, fused=None):
         """One Lloyd pass. ``labels=None``: the assignment is not stored (every pass but the last); ``partials=None``:
-        no sums are accumulated (the last pass)."""
+        no sums are accumulated (the last pass). ``fused=(workspace, t)``: pass ``t`` of a self-updating loop (not the last:
+        ``assign_raster``) - the sums stay in the workspace, ``cent`` receives the centroids the pass made for itself."""
+        if fused is not None:
+            if labels is not None or partials is not None or rows is not None:
+                raise ValueError("a self-updating pass takes whole images and has no label or partial output")
+            return self._pass_fused(feats, cent, b, h, w, k, n_sets, fused, reverse)
         lo, hi = rows if rows is not None else (0, h)
         _lib.check(self.lib.gcs_kmeans_assign_accumulate(
             feats.data_ptr(), cent.data_ptr(), b, h, w, *self._bk, k, n_sets, lo, hi,
@@ -329,11 +351,14 @@ class HipOps:
             "gcs_kmeans_assign_accumulate")
 
     @_on_device
-    def assign_raster(self, feats, cent, b, h, w, k, n_sets, out, scratch_labels=None, reverse=False):
-        """The last Lloyd pass with the label map written in raster order: ``out`` (B,H,W) int32 or uint8 device tensor."""
+    def assign_raster(self, feats, cent, b, h, w, k, n_sets, out, scratch_labels=None, reverse=False, fused=None):
+        """The last Lloyd pass with the label map written in raster order: ``out`` (B,H,W) int32 or uint8 device tensor.
+        ``fused=(workspace, t)``: as the last pass of a self-updating loop (see ``assign_accumulate``)."""
         torch = self.torch
         if out.dtype not in (torch.int32, torch.uint8) or tuple(out.shape) != (b, h, w) or not out.is_contiguous():
             raise ValueError("out must be a contiguous (B,H,W) int32 or uint8 tensor")
+        if fused is not None:
+            return self._pass_fused(feats, cent, b, h, w, k, n_sets, fused, reverse, out=out)
         _lib.check(self.lib.gcs_kmeans_assign_raster(
             feats.data_ptr(), cent.data_ptr(), b, h, w, *self._bk, k, n_sets, 1 if reverse else 0, out.data_ptr(),
             1 if out.dtype == torch.uint8 else 0, None if scratch_labels is None else scratch_labels.data_ptr(),
@@ -443,7 +468,7 @@ def _check_smoothing(smoothing, bank) -> float:
 
 
 def lloyd(ops, feats, b, h, w, k, n_iter, mode, labels, partials, cent, sums, dist_group=None,
-          rows=None, init=None, raster=None, debug=_ENV_DEBUG):
+          rows=None, init=None, raster=None, debug=_ENV_DEBUG, fold=None):
     """SPEC.md §4 schedule on one feature slab. ``mode``: 'per_image' or 'global'.
 
     In 'global' mode with torch.distributed initialised, the init centroids come from
@@ -454,6 +479,9 @@ def lloyd(ops, feats, b, h, w, k, n_iter, mode, labels, partials, cent, sums, di
     ``debug``: the plan's ``DebugSwitches`` (``force_collectives``, ``no_reverse``).
     ``raster``: (B,H,W) int32 / uint8 device tensor: the last pass writes the label map there itself (whole images only,
     ops that have ``assign_raster``) instead of filling the label slab for a separate raster kernel.
+    ``fold``: the workspace of ``ops.fused_workspace`` (None: the ops or the library have none for this bank). With it, a
+    single-rank loop over whole images that ends in ``raster`` is ``n_iter`` launches: every pass makes its own centroids from the
+    sums the previous one left in ``fold`` (no init kernel, no reduce launches; same labels, same ``cent`` afterwards).
     """
     n_sets = b if mode == "per_image" else 1
     dist = None
@@ -461,6 +489,14 @@ def lloyd(ops, feats, b, h, w, k, n_iter, mode, labels, partials, cent, sums, di
         import torch.distributed as td
         if td.is_available() and td.is_initialized() and (td.get_world_size(dist_group) > 1 or debug.force_collectives):
             dist = td
+    if fold is not None and dist is None and rows is None and init is None and raster is not None and n_iter >= 1:
+        for t in range(n_iter):
+            rev = not (t & 1) and not debug.no_reverse
+            if t == n_iter - 1:
+                ops.assign_raster(feats, cent, b, h, w, k, n_sets, raster, scratch_labels=labels, reverse=rev, fused=(fold, t))
+            else:
+                ops.assign_accumulate(feats, cent, b, h, w, k, n_sets, None, None, reverse=rev, fused=(fold, t))
+        return
     if init is not None:
         init(cent)
     else:
@@ -581,6 +617,8 @@ class Segmenter:
             ws = dict(feats=self.ops.feature_slab(g, h, w), labels=self.ops.label_slab(g, h, w),
                       partials=self.ops.partial_slab(g, h, w, self.k),
                       cent=self.ops.new_centroids(n_sets, self.k), sums=self.ops.new_sums(n_sets, self.k))
+            if hasattr(self.ops, "fused_workspace"):
+                ws["fold"] = self.ops.fused_workspace(g, h, w, self.k, n_sets)
             if self.smoothing > 0:
                 ws["smooth"] = self.ops.smooth_scratch(g, h, w)
             if self.chroma_gain > 0:
@@ -674,7 +712,8 @@ class Segmenter:
                 self._features(imgs[g0:g0 + n], ws, n, h, w)
                 direct = hasattr(self.ops, "assign_raster")      # the last pass writes the raster map itself
                 lloyd(self.ops, ws["feats"], n, h, w, self.k, self.n_iter, mode, ws["labels"], ws["partials"],
-                      ws["cent"], ws["sums"], dist_group, raster=out[g0:g0 + n] if direct else None, debug=self.debug)
+                      ws["cent"], ws["sums"], dist_group, raster=out[g0:g0 + n] if direct else None, debug=self.debug,
+                      fold=ws.get("fold"))
                 if not direct:
                     self.ops.labels_widen(ws["labels"], n, h, w, out[g0:g0 + n])
             if self.min_region_size > 0:
@@ -692,6 +731,8 @@ class Segmenter:
         ws = dict(feats=self.ops.feature_slab(n, h, w), labels=self.ops.label_slab(n, h, w),
                   partials=self.ops.partial_slab(n, h, w, self.k),
                   cent=self.ops.new_centroids(n_sets, self.k), sums=self.ops.new_sums(n_sets, self.k))
+        if hasattr(self.ops, "fused_workspace"):
+            ws["fold"] = self.ops.fused_workspace(n, h, w, self.k, n_sets)
         if self.smoothing > 0:
             ws["smooth"] = self.ops.smooth_scratch(n, h, w)
         if self.chroma_gain > 0:
@@ -908,7 +949,7 @@ class Segmenter:
                 ops.smooth_features(ws["feats"], b, h, w, scratch=ws["smooth"])
             dev_out = st["dev_out"] if out_dtype == np.uint8 else st["dev_out32"]
             lloyd(ops, ws["feats"], b, h, w, self.k, self.n_iter, mode, ws["labels"], ws["partials"],
-                  ws["cent"], ws["sums"], raster=dev_out, debug=self.debug)
+                  ws["cent"], ws["sums"], raster=dev_out, debug=self.debug, fold=ws.get("fold"))
             # The result is a FRESH pinned host buffer per call, handed to the caller as the base of the returned
             # array (torch's caching host allocator recycles it once the caller drops the array): the device-to-host
             # copy lands directly in caller-owned memory, with no pageable copy and no first-touch page faults.
@@ -982,7 +1023,7 @@ class Segmenter:
                     if smooth is not None:
                         ops.smooth_features(ws["feats"], b, h, w, scratch=smooth)
                     lloyd(ops, ws["feats"], b, h, w, k, n_iter, mode, ws["labels"], ws["partials"], ws["cent"],
-                          ws["sums"], raster=dev_out, debug=debug)
+                          ws["sums"], raster=dev_out, debug=debug, fold=ws.get("fold"))
                 dev_in.zero_()
                 step()                                     # eager once: first-use work (side-stream creation) outside the capture
                 # (a STREAM wait - the step joins its side stream back into this one: a device-wide synchronize is refused while
@@ -1207,7 +1248,7 @@ class _StreamPipe:
             if seg.smoothing > 0:
                 ops.smooth_features(ws["feats"], b, h, w, scratch=ws["smooth"])
             lloyd(ops, ws["feats"], b, h, w, seg.k, seg.n_iter, self.mode, ws["labels"], ws["partials"], ws["cent"],
-                  ws["sums"], raster=st["dev_out"][i], debug=seg.debug)
+                  ws["sums"], raster=st["dev_out"][i], debug=seg.debug, fold=ws.get("fold"))
             st["ev_done"][i].record(cur)
             land = torch.empty((b, h, w), dtype=self.t_dtype, pin_memory=True)   # caller-owned; torch recycles it once dropped
             with torch.cuda.stream(st["down"]):

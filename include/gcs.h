@@ -160,6 +160,24 @@ int gcs_kmeans_reduce_finalize(const uint64_t *partials_dev, int B, int H, int W
                                int n_sets, int64_t *sums_dev, uint16_t *centroids_dev,
                                gcs_stream_t stream);
 
+/* Self-updating Lloyd passes (single rank, whole images): the loop is n_iter calls of gcs_kmeans_pass_fused and nothing else -
+ * no gcs_kmeans_init, no reduce. Pass t makes its own centroids (t == 0: the SPEC.md §4 init pixels; else the §4 update from the
+ * sums pass t - 1 left in the workspace), assigns, and - unless `last` - adds its sums into the workspace with 64-bit integer
+ * atomics (any order gives the same bits). Same labels and centroids as init / assign_accumulate / reduce_finalize.
+ *   gcs_kmeans_fused_workspace_bytes  bytes of the workspace, or 0 when this bank / k / n_sets has no such pass (then use the
+ *                                     entry points above): today the split-slab banks (at most two pyramid levels, D <= 79, a
+ *                                     tile of at most 12 288 slots) with k <= 8. A pure host function.
+ *   workspace_dev                     ZEROED once by the caller when it is allocated; every complete loop (passes 0 .. n - 1, the
+ *                                     last with last != 0) leaves it as it found it, whatever n, so loops may follow one another
+ *                                     (also as replays of one captured graph). One loop at a time per workspace.
+ *   pass                              t, counted from 0; `reverse` as in gcs_kmeans_assign_accumulate.
+ *   centroids_dev                     uint16 [n_sets][k][D], WRITTEN: the centroids pass t used (nothing is read from it).
+ *   out_dev, out_u8                   the raster label map of the last pass, as in gcs_kmeans_assign_raster; ignored otherwise. */
+size_t gcs_kmeans_fused_workspace_bytes(int B, int H, int W, int n_scales, int n_orient, int k, int n_sets);
+int gcs_kmeans_pass_fused(const uint16_t *feats_dev, int B, int H, int W, int n_scales, int n_orient, int k, int n_sets,
+                          int reverse, int pass, int last, void *workspace_dev, uint16_t *centroids_dev, void *out_dev,
+                          int out_u8, gcs_stream_t stream);
+
 /* uint8 label map [B][H][W] -> int32 [B][H][W] (the dtype handed to metrics.py:43). Both pointers 4-byte aligned. */
 int gcs_labels_widen(const uint8_t *labels_dev, int B, int H, int W, int32_t *out_dev,
                      gcs_stream_t stream);

@@ -15,7 +15,9 @@ hip_rt = os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so")
 if os.path.exists(hip_rt):
     ctypes.CDLL(hip_rt, mode=ctypes.RTLD_GLOBAL)
 _lib.LIB_PATH = lib
-_lib.ABI_VERSION = ctypes.CDLL(lib).gcs_abi_version()
+raw = ctypes.CDLL(lib)
+_lib.ABI_VERSION = raw.gcs_abi_version()
+_lib.SIGNATURES = {k: v for k, v in _lib.SIGNATURES.items() if hasattr(raw, k)}   # an older build lacks the newest entry points
 sys.argv = [os.path.join(ROOT, "bench.py")] + sys.argv[2:]
 import bench
 bench.main()
