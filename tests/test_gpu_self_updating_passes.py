@@ -7,6 +7,7 @@ workspace (the state a loop leaves is the state it found), the captured graph, a
 import numpy as np
 import pytest
 
+import fused_workspace as fw
 import hot_banks as hb
 from oracle import c_oracle as co
 
@@ -74,16 +75,18 @@ def _oracle(seg, imgs, mode, n_iter=None):
 
 def _workspace_is_as_found(seg):
     """White box (include/gcs.h: 'every complete loop leaves the workspace as it found it'): the three sum buffers and the ticket
-    are zero again; only the two centroid arrays behind the sums (each a multiple of 256 bytes) hold data."""
+    are zero again; only the two centroid arrays behind the sums (each a multiple of 256 bytes) hold data. The layout is that of
+    tests/fused_workspace.py."""
     n = 0
     for (g, h, w, mode), ws in seg._ws.items():
         fold = ws["fold"]
         assert fold is not None
         n_sets = g if mode == "per_image" else 1
-        cb = -(-n_sets * seg.k * seg.bank.n_features * 2 // 256) * 256
-        raw = fold.cpu().numpy()
-        assert not raw[:len(raw) - 2 * cb - 256].any(), "a sum buffer was left dirty"
-        assert not raw[len(raw) - 256:].any(), "the ticket was left set"
+        rows = fw.fold_rows(g, seg.ops.lib.gcs_kmeans_parts_per_image(g, h, w), n_sets, fw.env_fold_rows())
+        v = fw.views(fold.cpu().numpy(), n_sets, rows, seg.k, seg.bank.n_features)
+        for i in range(3):
+            assert not v.sum_raw[i].any(), "a sum buffer was left dirty"
+        assert not v.ticket_raw.any(), "the ticket was left set"
         n += 1
     assert n > 0
 

@@ -23,6 +23,7 @@ import hot_banks as hb
 import smooth_ref as sr
 from oracle import c_oracle as co
 from oracle import spec_oracle as so
+from lloyd_ref import _caller_codebook, _pass_reference, _update_cases
 from slab_layout import flag_bytes, tile_of_pixels
 
 pytestmark = pytest.mark.gpu
@@ -219,31 +220,6 @@ PASS_CASES = [
 ]
 
 
-def _caller_codebook(x, k):
-    """(k, D) int64 rows a caller might hand in, from the features x (P, D): pixels that hold values >= 32768, TWO IDENTICAL rows
-    (the lowest index wins the tie, the other cluster stays empty), the features' rounded mean, an all-zero and an all-46339 row."""
-    hot = np.argsort(-x.max(axis=1), kind="stable")
-    mean = (2 * x.sum(axis=0) + len(x)) // (2 * len(x))
-    rows = [x[hot[0]], x[hot[0]], mean, np.zeros_like(mean), np.full_like(mean, hb.G_MAX)]
-    rows += [x[hot[(len(hot) * i) // 40]] for i in range(1, 12)]
-    return np.stack(rows[:k]).astype(np.int64)
-
-
-def _pass_reference(x, cent, vote):
-    """x (B, P, D) int64, cent (n_sets, k, D), vote (B, P) bool -> labels (B, P), sums (n_sets, k, D), counts (n_sets, k)."""
-    b, n_sets, k = x.shape[0], cent.shape[0], cent.shape[1]
-    lab = np.stack([so.kmeans_assign(x[i], cent[i if n_sets > 1 else 0]) for i in range(b)])
-    sums = np.zeros((n_sets, k, x.shape[2]), np.int64)
-    cnt = np.zeros((n_sets, k), np.int64)
-    for i in range(b):
-        s = i if n_sets > 1 else 0
-        for j in range(k):
-            m = (lab[i] == j) & vote[i]
-            sums[s, j] += x[i][m].sum(axis=0)
-            cnt[s, j] += m.sum()
-    return lab, sums, cnt
-
-
 @pytest.mark.parametrize("case", [c for c, _ in PASS_CASES], ids=[i for _, i in PASS_CASES])
 def test_one_lloyd_pass(torch_cuda, case):
     """gcs_kmeans_assign_accumulate + gcs_kmeans_reduce (and gcs_kmeans_reduce_finalize, gcs_kmeans_assign_raster) on hot features:
@@ -313,26 +289,6 @@ def test_one_lloyd_pass(torch_cuda, case):
 
 
 # ------------------------------------------------------------------------------------------ finalize / reduce_finalize alone
-def _update_cases(d, k):
-    """sums (k, d + 1) as Python-int lists and the expected centroids from a previous codebook `old`: S/n at 0, 0.5-ties (round
-    half up), 32767.5, 46339, n = 1 and n = 64 * 481 * 321, and empty clusters between full ones."""
-    n_big = 64 * 481 * 321
-    rng = np.random.default_rng(3)
-    old = rng.integers(0, hb.G_MAX + 1, (k, d)).tolist()
-    sums, want = [], []
-    for j in range(k):
-        n = [1, 0, 2, n_big, 0, n_big - 1, 3, 1 << 20][j % 8]
-        row = []
-        for e in range(d):
-            kind = (e + j) % 8
-            v = [0, n // 2, (32767 * 2 + 1) * n // 2, hb.G_MAX * n, n - 1 if n else 0, 32768 * n, (hb.G_MAX * 2 - 1) * n // 2,
-                 int(rng.integers(0, hb.G_MAX + 1)) * n + int(rng.integers(0, n + 1))][kind]
-            row.append(min(v, hb.G_MAX * n))
-        sums.append(row + [n])
-        want.append([(2 * s + n) // (2 * n) for s in row] if n else old[j])
-    return old, sums, want
-
-
 @pytest.mark.parametrize("d,k", [(72, 16), (3, 4), (192, 8), (210, 5)])
 def test_finalize_on_written_sums(torch_cuda, d, k):
     """gcs_kmeans_finalize alone: floor((2 S + n) / (2 n)) in Python integers; 2 S + n reaches 9.2e11 (n = 64 x 481 x 321 pixels of
