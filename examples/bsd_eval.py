@@ -20,6 +20,9 @@ K half-periods before k-means); with `--min-region-size N` as well, every K is c
 `--color-weight W[,W...]`, `--chroma-gain G[,G...]`, `--n-orient N`: the same table through Segmenter(n_orient=N, color_weight=W,
 chroma_gain=G) (SPEC.md §11: a low-pass slot per scale, clustering in opponent colours), every W with every G (and every K and m);
 `--val --n-orient 5 --color-weight 0.125 --chroma-gain 4` is the recommended colour setting.
+`--position-weight MU[,MU...]`: the same table through Segmenter(position_weight=MU) (SPEC.md §12: a coordinate slot per scale),
+every MU with every other option; `--n-orient 4 --color-weight 0.125 --chroma-gain 4 --position-weight 6` is the recommended
+setting.
 """
 import os
 import sys
@@ -74,7 +77,7 @@ def val_split(agreement=False):
                     float(np.mean([gold_agr["val/%s/%s" % (i, kind)][gkey] for i in ids]))))
 
 
-def merge_table(sizes, smoothings=(0.0,), weights=(0.0,), gains=(0,), n_orient=None):
+def merge_table(sizes, smoothings=(0.0,), weights=(0.0,), gains=(0,), n_orient=None, positions=(0,)):
     import numpy as np
     import torch
     from gabor_color_image_segmentation_amd import Segmenter
@@ -86,28 +89,29 @@ def merge_table(sizes, smoothings=(0.0,), weights=(0.0,), gains=(0,), n_orient=N
     ids = [str(i) for i in pack["ids"]]
     groups = [[i for i in ids if pack["img_" + i].shape[:2] == shape] for shape in sorted({pack["img_" + i].shape[:2] for i in ids})]
     keys = ("recall", "precision", "fmeasure", "PRI", "VoI", "covering")
-    colour = n_orient is not None or tuple(weights) != (0.0,) or tuple(gains) != (0,)      # the colour columns, when asked for
+    position = tuple(positions) != (0,)                                                    # the mu column, when asked for
+    colour = n_orient is not None or tuple(weights) != (0.0,) or tuple(gains) != (0,) or position    # the colour columns, when asked for
     n_orient = 6 if n_orient is None else n_orient
-    print(("| n_orient | w | g " if colour else "") + "| K | m | R | P | F | PRI | VoI | covering | regions / image |")
-    print(("|---|---|---" if colour else "") + "|---|---|---|---|---|---|---|---|---|")
-    for cw, g, K, m in [(cw, g, K, m) for cw in weights for g in gains for K in smoothings for m in sizes]:
-        seg = Segmenter(n_orient=n_orient, min_region_size=m, smoothing=K, color_weight=cw, chroma_gain=g)
+    print(("| n_orient | w | g " if colour else "") + ("| mu " if position else "") + "| K | m | R | P | F | PRI | VoI | covering | regions / image |")
+    print(("|---|---|---" if colour else "") + ("|---" if position else "") + "|---|---|---|---|---|---|---|---|---|")
+    for cw, g, mu, K, m in [(cw, g, mu, K, m) for cw in weights for g in gains for mu in positions for K in smoothings for m in sizes]:
+        seg = Segmenter(n_orient=n_orient, min_region_size=m, smoothing=K, color_weight=cw, chroma_gain=g, position_weight=mu)
         rows = []
         for group in groups:
             labels = seg.segment_device(torch.from_numpy(np.stack([pack["img_" + i] for i in group])).cuda())
             rows += all_scores_batch_device(labels, truth.to_device(group), agreement=True)
         mean = [float(np.mean([r[k] for r in rows])) for k in keys]
         regions = [r["regions"] for r in rows]
-        print(("| %d | %g | %d " % (n_orient, cw, g) if colour else "") +
+        print(("| %d | %g | %d " % (n_orient, cw, g) if colour else "") + ("| %d " % mu if position else "") +
               "| %g | %d | %s | %d - %d |" % (K, m, " | ".join("%.4f" % v for v in mean), min(regions), max(regions)))
 
 
 if __name__ == '__main__':
-    if any(o in sys.argv for o in ("--min-region-size", "--smoothing", "--color-weight", "--chroma-gain", "--n-orient")):
+    if any(o in sys.argv for o in ("--min-region-size", "--smoothing", "--color-weight", "--chroma-gain", "--n-orient", "--position-weight")):
         def arg(name, conv, default):
             return [conv(v) for v in sys.argv[sys.argv.index(name) + 1].split(",")] if name in sys.argv else default
         merge_table(arg("--min-region-size", int, [0]), arg("--smoothing", float, [0.0]), arg("--color-weight", float, [0.0]),
-                    arg("--chroma-gain", int, [0]), arg("--n-orient", int, [None])[0])
+                    arg("--chroma-gain", int, [0]), arg("--n-orient", int, [None])[0], arg("--position-weight", int, [0]))
         sys.exit(0)
     if "--val" in sys.argv:
         val_split(agreement="--agreement" in sys.argv)

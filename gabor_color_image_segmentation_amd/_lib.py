@@ -68,6 +68,7 @@ SIGNATURES = {
     "gcs_smooth_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "gcs_smooth_features": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "gcs_colour_opponent": (_i, [_vp, _sz, _i, _vp, _vp]),
+    "gcs_position_features": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
 }
 
 

@@ -32,7 +32,8 @@ class GaborBank:
     shift: int               # E - FEATURE_Q
     tapq: np.ndarray
     color_weight: float = 0.0     # w of SPEC.md §11 (0: a plain Gabor bank)
-    n_gabor_orient: int = 0       # Gabor orientations per scale; 0 = n_orient (a colour bank: n_orient - 1, the last slot is low-pass)
+    n_gabor_orient: int = 0       # Gabor orientations per scale; 0 = n_orient (make_bank: n_orient minus the colour and the coordinate slot)
+    position_weight: int = 0      # mu of SPEC.md §12 (0: no coordinate slot; else the LAST slot of every scale, zero taps)
 
     def __post_init__(self):
         if self.n_gabor_orient == 0:
@@ -97,15 +98,40 @@ def check_color_weight(color_weight) -> float:
     return w
 
 
+POSITION_WEIGHT_MAX = 255
+FEATURE_MAX = 46340     # SPEC.md §3 value range: the squared distance of two features stays below 2^31
+
+
+def check_position_weight(position_weight) -> int:
+    """SPEC.md §12 parameter: the integer 0 (off) or 1..255. Bools and floats (6.0 included) are refused: mu is an exact integer."""
+    import numbers
+    if isinstance(position_weight, bool) or not isinstance(position_weight, numbers.Integral) \
+            or not (0 <= int(position_weight) <= POSITION_WEIGHT_MAX):
+        raise ValueError(f"position_weight must be the integer 0 (off) or 1..{POSITION_WEIGHT_MAX}, got {position_weight!r}")
+    return int(position_weight)
+
+
+def check_position_range(position_weight, height, width) -> None:
+    """SPEC.md §12 domain: mu * (max(height, width) - 1) <= 46 340, with the FULL image's row count for a row strip."""
+    if position_weight > 0 and position_weight * (max(int(height), int(width)) - 1) > FEATURE_MAX:
+        raise ValueError(f"position_weight = {position_weight} on a {height} x {width} image exceeds the feature range: "
+                         f"mu * (max(height, width) - 1) must be <= {FEATURE_MAX} (SPEC.md §12)")
+
+
 def make_bank(n_scales=4, n_orient=6, ksize=13, f_max=0.4, ratio=math.sqrt(2.0),
-              bandwidth=1.0, color_weight=0.0) -> GaborBank:
+              bandwidth=1.0, color_weight=0.0, position_weight=0) -> GaborBank:
     """Quantise the bank to Q15 taps (SPEC.md §2): shift = 8, i.e. the response's Q7 value is bytes 1..2 of v.
 
     ``color_weight`` = w > 0 (SPEC.md §11): every scale gets one more filter behind its ``n_orient`` Gabor filters, the scale's
     envelope times w with zero imaginary taps. The bank returned then has ``n_orient + 1`` slots per scale and says so in its
     ``n_orient`` field - that is the shape the C ABI, the slab layout and every kernel see -, with the Gabor orientation count
-    in ``n_gabor_orient``. The exponent comes from the Gabor taps alone: the Gabor slots equal the plain bank's bit for bit."""
+    in ``n_gabor_orient``. The exponent comes from the Gabor taps alone: the Gabor slots equal the plain bank's bit for bit.
+
+    ``position_weight`` = mu > 0 (SPEC.md §12): one more slot per scale, behind the Gabor filters and the colour slot, with all
+    taps zero - the planes the coordinate kernel fills (``HipOps.position_features``). Counted in ``n_orient`` like the colour
+    slot; every other filter equals the bank's without it bit for bit."""
     w = check_color_weight(color_weight)
+    mu = check_position_weight(position_weight)
     taps, envs = _taps_and_envelopes(n_scales, n_orient, ksize, f_max, ratio, bandwidth)
     exponent = min(TAP_Q, int(math.floor(math.log2(TAPQ_MAX / np.abs(taps).max()))))
     tapq = np.rint(taps * 2.0 ** exponent).astype(np.int64)
@@ -116,6 +142,11 @@ def make_bank(n_scales=4, n_orient=6, ksize=13, f_max=0.4, ratio=math.sqrt(2.0),
         full[:, :n_orient] = tapq.reshape(n_scales, n_orient, 2, ksize, ksize)
         full[:, n_orient, 0] = np.rint(w * envs * 2.0 ** exponent).astype(np.int64)
         tapq = full.reshape(n_scales * n_slots, 2, ksize, ksize)
+    if mu > 0:
+        full = np.zeros((n_scales, n_slots + 1, 2, ksize, ksize), np.int64)
+        full[:, :n_slots] = tapq.reshape(n_scales, n_slots, 2, ksize, ksize)
+        n_slots += 1
+        tapq = full.reshape(n_scales * n_slots, 2, ksize, ksize)
     if np.abs(tapq).max() > TAPQ_MAX:
         raise AssertionError("tap quantisation overflowed the two-digit range")
     if exponent < FEATURE_Q:
@@ -124,7 +155,7 @@ def make_bank(n_scales=4, n_orient=6, ksize=13, f_max=0.4, ratio=math.sqrt(2.0),
         raise AssertionError("imaginary taps must sum to zero (odd symmetry)")
     return GaborBank(n_scales, n_slots, ksize, float(f_max), float(ratio),
                      float(bandwidth), exponent, exponent - FEATURE_Q,
-                     tapq.astype(np.int16), w, n_orient)
+                     tapq.astype(np.int16), w, n_orient, mu)
 
 
 def split_digits(tapq: np.ndarray):

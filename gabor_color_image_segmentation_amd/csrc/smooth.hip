@@ -13,6 +13,7 @@
 //                         runs of offset-binary u16. Slots that hold no pixel keep their bytes.
 // No atomics, no allocation, no host synchronisation: both launches sit on the caller's stream (and inside a captured graph).
 #include "common.h"
+#include "slab_slots.h"      // sm_nibble, sm_decode, sm_slot_pixel: shared with position.hip
 
 namespace {
 
@@ -43,61 +44,6 @@ __device__ __forceinline__ int sm_reflect(int i, int n) {     // SPEC.md §3 ref
     int m = i % p;
     if (m < 0) m += p;
     return m < n ? m : p - 1 - m;
-}
-
-// gcs_split_nibble with the group size as a shift: byte (relative to the MID / TOP array) and bit shift of a slot's nibble
-__device__ __forceinline__ void sm_nibble(int L, unsigned slot, unsigned &byte, int &shift) {
-    const int gsh = L < 2 ? 3 - L : 1;
-    const unsigned h = 1u << (gsh - 1), gi = slot & ((1u << gsh) - 1u), second = gi >= h ? 1u : 0u;
-    byte = (slot >> gsh) * h + gi - second * h;
-    shift = 4 * (int)second;
-}
-
-// Level-L pixel (yl, xl) -> value of physical plane r (plain uint16) in image b's slab.
-__device__ __forceinline__ unsigned sm_decode(const SmoothArgs &A, const unsigned char *img, int L, int r, int yl, int xl) {
-    const GcsLayout &lo = A.lo;
-    const int y = yl << L, x = xl << L;      // any full-resolution pixel of the level pixel's block holds its value
-    int blk, iy, ix;
-    gcs_locate(lo, y, x, blk, iy, ix);
-    const int side = 8 >> L, npl = KP_TP >> (2 * L);
-    if (!lo.split) {
-        const size_t off = (size_t)(blk >> 2) * lo.tile_bytes + lo.off[L] +
-                           ((size_t)(r - lo.row0[L]) * npl + (blk & 3) * side * side + (iy >> L) * side + (ix >> L)) * 2;
-        return *reinterpret_cast<const uint16_t *>(img + off) ^ 0x8080u;
-    }
-    const unsigned tile = (unsigned)(blk >> 2);
-    const unsigned slot = tile * (unsigned)lo.S + (unsigned)(lo.sl0[L] + (r - lo.row0[L]) * npl + (iy >> L) * 4 * side +
-                                                             (blk & 3) * side + (ix >> L));
-    unsigned nb;
-    int sh;
-    sm_nibble(L, slot, nb, sh);
-    unsigned v = (img[slot] ^ 0x80u) | (((unsigned)img[lo.mid_off + nb] >> sh & 15u) << 8);
-    if (img[lo.flag_off + 4u * tile + (unsigned)L]) v |= ((unsigned)img[lo.top_off + nb] >> sh & 15u) << 12;
-    return v;
-}
-
-// Slot (sy, sx) of level L in block blk -> the level pixel it holds; false: the slot holds no pixel.
-// by / bx: the block's row and column when it is a main block (the callers divide once per tile, not per slot).
-__device__ __forceinline__ bool sm_slot_pixel(const GcsLayout &lo, int blk, int by, int bx, int L, int sy, int sx, int &yl, int &xl) {
-    if (blk >= lo.nblk) return false;
-    if (blk < lo.nmain) {
-        yl = ((8 * by) >> L) + sy;
-        xl = ((8 * bx) >> L) + sx;
-        return yl < lo.HL[L] && xl < lo.WL[L];
-    }
-    // virtual blocks of the packed edge strips (banks of at most two levels): csrc/common.h
-    const bool right = blk < lo.nmain + lo.nR;
-    const int v = blk - lo.nmain - (right ? 0 : lo.nR);
-    if (L == 0) {
-        const int s = 32 * v + 8 * (sy >> 1) + 2 * (sx >> 1);
-        yl = right ? s + (sy & 1) : lo.Hm + (sy & 1);
-        xl = right ? lo.Wm + (sx & 1) : s + (sx & 1);
-        return yl < lo.H && xl < (right ? lo.W : lo.Wb);
-    }
-    const int q = 16 * v + 4 * sy + sx;      // the strip's level-1 parent
-    yl = right ? q : lo.Hm >> 1;
-    xl = right ? lo.Wm >> 1 : q;
-    return right ? 2 * q < lo.H : 2 * q < lo.Wb;
 }
 
 __global__ __launch_bounds__(256) void smooth_planes_kernel(SmoothArgs A) {
@@ -137,7 +83,7 @@ __global__ __launch_bounds__(256) void smooth_planes_kernel(SmoothArgs A) {
     if (ax < AW) {
         const int xl = sm_reflect(tx0 + ax - R, WL);
         for (int ay = tid >> 7; ay < AH; ay += 2)
-            in[ay][ax] = (uint16_t)sm_decode(A, img, L, r, sm_reflect(ty0 + ay - R, HL), xl);
+            in[ay][ax] = (uint16_t)sm_decode(lo, img, L, r, sm_reflect(ty0 + ay - R, HL), xl);
     }
     __syncthreads();
     const int n = 2 * R + 1;

@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 from . import _lib
-from .bank import GaborBank, check_color_weight, make_bank, smoothing_taps
+from .bank import GaborBank, check_color_weight, check_position_range, check_position_weight, make_bank, smoothing_taps
 
 # Feature-slab bytes per group of a per-image batch. Large on purpose: measured in round 4 with the current kernels
 # (tools/cache_resident_pass.py, profiles/r4_notes.md "Infinity-Cache-resident groups"): a pass that re-reads a slab small enough
@@ -314,6 +314,17 @@ class HipOps:
                    "gcs_smooth_features")
 
     @_on_device
+    def position_features(self, feats, b, h, w, y0=0):
+        """SPEC.md §12 in place on a slab that ``gabor_features`` (and ``smooth_features``, when smoothing is on) has filled: the
+        coordinate slot of every scale, with this plan's bank's ``position_weight``. ``y0``: the global row of the slab's row 0
+        (row strips of a taller image). One launch, no workspace (capturable as it is)."""
+        mu = getattr(self.bank, "position_weight", 0)
+        if mu == 0:
+            raise ValueError("position_features needs a bank made with position_weight = mu > 0")
+        _lib.check(self.lib.gcs_position_features(feats.data_ptr(), b, h, w, *self._bk, mu, int(y0), self._stream()),
+                   "gcs_position_features")
+
+    @_on_device
     def features_unpack(self, feats, b, h, w):
         d = self.bank.n_features
         out = self.torch.empty((b, d, h, w), dtype=self.torch.int16, device=self.device)
@@ -557,7 +568,8 @@ class Segmenter:
 
     def __init__(self, n_scales=4, n_orient=6, k=8, n_iter=10, ksize=13, f_max=0.4,
                  ratio=math.sqrt(2.0), bandwidth=1.0, connectivity=False, device="cuda:0", ops=None,
-                 slab_candidates=1, min_region_size=0, smoothing=0.0, color_weight=0.0, chroma_gain=0):
+                 slab_candidates=1, min_region_size=0, smoothing=0.0, color_weight=0.0, chroma_gain=0,
+                 position_weight=0):
         if not (1 <= k <= _lib.K_MAX):
             raise ValueError(f"k must be in 1..{_lib.K_MAX}")
         if n_iter < 1:
@@ -570,7 +582,8 @@ class Segmenter:
         self.min_region_size = int(min_region_size)  # SPEC.md §9 post-pass (> 0: connected regions, small ones merged)
         self.color_weight = check_color_weight(color_weight)        # SPEC.md §11: a low-pass slot behind every scale's filters
         self.chroma_gain = _check_chroma_gain(chroma_gain)          # SPEC.md §11: T_g in front of the Gabor stage
-        self.bank = make_bank(n_scales, n_orient, ksize, f_max, ratio, bandwidth, self.color_weight)
+        self.position_weight = check_position_weight(position_weight)   # SPEC.md §12: a coordinate slot behind every scale's filters
+        self.bank = make_bank(n_scales, n_orient, ksize, f_max, ratio, bandwidth, self.color_weight, self.position_weight)
         self.smoothing = _check_smoothing(smoothing, self.bank)     # SPEC.md §10, between the Gabor stage and k-means
         self.ops = ops if ops is not None else HipOps(self.bank, device, self.smoothing, self.chroma_gain)
         if self.smoothing > 0 and getattr(self.ops, "smoothing", 0.0) != self.smoothing:
@@ -581,6 +594,10 @@ class Segmenter:
         if getattr(ops_bank, "color_weight", 0.0) != self.color_weight or \
                 (self.color_weight > 0 and (ops_bank.n_scales, ops_bank.n_orient) != (self.bank.n_scales, self.bank.n_orient)):
             raise ValueError("Segmenter(color_weight=w, ops=...) needs ops built for the same colour bank")
+        if getattr(ops_bank, "position_weight", 0) != self.position_weight or \
+                (self.position_weight > 0 and ((ops_bank.n_scales, ops_bank.n_orient) != (self.bank.n_scales, self.bank.n_orient)
+                                               or not hasattr(self.ops, "position_features"))):
+            raise ValueError("Segmenter(position_weight=mu, ops=...) needs ops built for the same position bank")
         # feature-slab allocations to time at first use of a large workspace shape (see _place_slab). 1 = take the first
         # one (the library default: no extra memory, no host synchronisation, graph-capturable); bench.py asks for 2.
         self.slab_candidates = int(self.debug.slab_candidates or slab_candidates)
@@ -694,6 +711,7 @@ class Segmenter:
         b, h, w, _ = imgs.shape
         if h < 8 or w < 8:
             raise ValueError("images must be at least 8x8")
+        check_position_range(self.position_weight, h, w)
         on_gpu = self.native
         if on_gpu and imgs.device != self.ops.device:
             raise ValueError(f"imgs live on {imgs.device}, this Segmenter on {self.ops.device}")
@@ -745,6 +763,13 @@ class Segmenter:
         self.ops.gabor_features(self._opponent(imgs, ws["colour"]) if self.chroma_gain > 0 else imgs, ws["feats"])
         if self.smoothing > 0:
             self.ops.smooth_features(ws["feats"], b, h, w, scratch=ws["smooth"])
+        self._position(ws["feats"], b, h, w)
+
+    def _position(self, feats, b, h, w, y0=0):
+        """SPEC.md §12 when ``position_weight`` is on: the coordinate planes, written behind the Gabor stage and the smoothing
+        (every entry point has checked the range rule before its first launch). ``y0``: a row strip's first global row."""
+        if self.position_weight > 0:
+            self.ops.position_features(feats, b, h, w, y0=y0)
 
     def _opponent(self, imgs, colour):
         """T_g of ``imgs`` (SPEC.md §11) into the plan-owned buffer ``colour``; returns it. The caller's tensor is not changed."""
@@ -782,9 +807,11 @@ class Segmenter:
         halo = halo_rows(self.bank.n_levels, self.bank.ksize)
         if (r0 - s0 < halo and s0 > 0) or (s0 + hs - r1 < halo and s0 + hs < height):
             raise ValueError(f"interior strip edges need {halo} halo rows (use shard_rows)")
+        check_position_range(self.position_weight, height, w)
         ws = self._tail_workspace(b, hs, w, "global")
         # (T_g is per pixel: a strip with its halo rows transforms on its own)
         self.ops.gabor_features(self._opponent(strip, ws["colour"]) if self.chroma_gain > 0 else strip, ws["feats"])
+        self._position(ws["feats"], b, hs, w, y0=s0)                     # global coordinates: row 0 of the strip is row s0
         k, dfeat = self.k, self.bank.n_features
         import torch.distributed as td
         use_dist = td.is_available() and td.is_initialized() and td.get_world_size(dist_group) > 1
@@ -870,12 +897,14 @@ class Segmenter:
         when ``smoothing`` is on."""
         imgs = imgs.contiguous()
         b, h, w, _ = imgs.shape
+        check_position_range(self.position_weight, h, w)
         feats = self.ops.feature_slab(b, h, w)
         if self.chroma_gain > 0:
             imgs = self._opponent(imgs, self.ops.colour_scratch(b, h, w))
         self.ops.gabor_features(imgs, feats)
         if self.smoothing > 0:
             self.ops.smooth_features(feats, b, h, w)
+        self._position(feats, b, h, w)
         return self.ops.features_unpack(feats, b, h, w)
 
     # ---- host API: the slot
@@ -906,6 +935,7 @@ class Segmenter:
         b, h, w, _ = imgs.shape
         if h < 8 or w < 8:
             raise ValueError("images must be at least 8x8")
+        check_position_range(self.position_weight, h, w)
         dist_on = False
         if mode == "global":
             import torch.distributed as td
@@ -947,6 +977,7 @@ class Segmenter:
                 ops.gabor_features(chunk, ws["feats"][g0 * per_img:])
             if self.smoothing > 0:                                 # every chunk's Gabor stage is in front of it on `cur`
                 ops.smooth_features(ws["feats"], b, h, w, scratch=ws["smooth"])
+            self._position(ws["feats"], b, h, w)                   # once for the batch, behind every chunk's Gabor stage
             dev_out = st["dev_out"] if out_dtype == np.uint8 else st["dev_out32"]
             lloyd(ops, ws["feats"], b, h, w, self.k, self.n_iter, mode, ws["labels"], ws["partials"],
                   ws["cent"], ws["sums"], raster=dev_out, debug=self.debug, fold=ws.get("fold"))
@@ -1015,6 +1046,7 @@ class Segmenter:
                 # cycle is freed - with its graphs, streams, pinned and device buffers - only when the cyclic collector
                 # happens to run, not when the last user drops it)
                 ops, k, n_iter, debug = self.ops, self.k, self.n_iter, self.debug
+                position = self.position_weight > 0
 
                 def step():
                     if colour is not None:
@@ -1022,6 +1054,8 @@ class Segmenter:
                     ops.gabor_features(dev_in if colour is None else colour, ws["feats"], scratch=scratch)
                     if smooth is not None:
                         ops.smooth_features(ws["feats"], b, h, w, scratch=smooth)
+                    if position:
+                        ops.position_features(ws["feats"], b, h, w)
                     lloyd(ops, ws["feats"], b, h, w, k, n_iter, mode, ws["labels"], ws["partials"], ws["cent"],
                           ws["sums"], raster=dev_out, debug=debug, fold=ws.get("fold"))
                 dev_in.zero_()
@@ -1188,6 +1222,7 @@ class _StreamPipe:
         seg, dev, n_slots = self.seg, self.seg.ops.device, self.n_slots
         if h < 8 or w < 8:
             raise ValueError("images must be at least 8x8")
+        check_position_range(seg.position_weight, h, w)
         if seg.group_size(b, h, w, self.mode) < b:
             raise ValueError("batch too large for one feature slab: use smaller batches")
         self.shape = (b, h, w)
@@ -1247,6 +1282,7 @@ class _StreamPipe:
                                ws["feats"])
             if seg.smoothing > 0:
                 ops.smooth_features(ws["feats"], b, h, w, scratch=ws["smooth"])
+            seg._position(ws["feats"], b, h, w)
             lloyd(ops, ws["feats"], b, h, w, seg.k, seg.n_iter, self.mode, ws["labels"], ws["partials"], ws["cent"],
                   ws["sums"], raster=st["dev_out"][i], debug=seg.debug, fold=ws.get("fold"))
             st["ev_done"][i].record(cur)

@@ -341,6 +341,21 @@ int gcs_smooth_features(uint16_t *feats_dev, int B, int H, int W, int n_scales, 
  * Added within ABI 18: a new entry point changes no existing call, so GCS_ABI_VERSION did not move. */
 int gcs_colour_opponent(const uint8_t *img_dev, size_t n_pixels, int gain, uint8_t *out_dev, gcs_stream_t stream);
 
+/* ---- position features (SPEC.md §12) ------------------------------------------------------------ */
+
+/* In place on a feature slab (either format) of a bank whose LAST slot of every scale is the coordinate slot (zero taps; n_orient
+ * here counts it, as everywhere in this header): channel 0 of slot n_orient - 1 of scale s (level L = s / 2) becomes
+ * weight * (y0 + (yl << L)), channel 1 weight * (xl << L) at level pixel (yl, xl); channel 2 and every other plane keep what the
+ * Gabor stage (and gcs_smooth_features, which must run first when it is used) left. y0 = global row of row 0 (row strips of a
+ * taller image; 0 otherwise). A split slab's flag byte of level L is SET for a tile that receives a value of 4096 or more and is
+ * never cleared; slots that hold no pixel keep their bytes. One launch for all levels, stream-ordered, no workspace, no atomics,
+ * no allocation, no host synchronisation (capturable). GCS_EINVAL, with nothing launched, for a NULL pointer, a bad shape
+ * (B >= 1, H, W >= 8, a representable bank), a weight outside 1..255, weight * (max(y0 + H, W) - 1) > 46 340 (SPEC.md §3's value
+ * range) and a y0 that is negative or not a multiple of 2^(levels - 1).
+ * Added within ABI 18: a new entry point changes no existing call, so GCS_ABI_VERSION did not move. */
+int gcs_position_features(uint16_t *feats_dev, int B, int H, int W, int n_scales, int n_orient, int weight, int y0,
+                          gcs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
