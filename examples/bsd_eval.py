@@ -23,6 +23,11 @@ chroma_gain=G) (SPEC.md §11: a low-pass slot per scale, clustering in opponent 
 `--position-weight MU[,MU...]`: the same table through Segmenter(position_weight=MU) (SPEC.md §12: a coordinate slot per scale),
 every MU with every other option; `--n-orient 4 --color-weight 0.125 --chroma-gain 4 --position-weight 6` is the recommended
 setting.
+`--superpixels N [--spatial-weight L]`: the same 24 images through Segmenter(n_superpixels=N, spatial_weight=L) (SPEC.md §13:
+grid-local k-means instead of the Lloyd stage) with the other options of the table (`--n-orient`, `--color-weight`, `--chroma-gain`,
+`--min-region-size`, taken as single values; `--min-region-size auto` = S * S // 4 per image shape): mean boundary recall, underseg,
+undersegNP, compactness and regions from the GPU path; `--superpixels 300 --n-orient 5 --color-weight 0.125 --chroma-gain 4
+--min-region-size auto` is the recommended setting.
 """
 import os
 import sys
@@ -106,7 +111,37 @@ def merge_table(sizes, smoothings=(0.0,), weights=(0.0,), gains=(0,), n_orient=N
               "| %g | %d | %s | %d - %d |" % (K, m, " | ".join("%.4f" % v for v in mean), min(regions), max(regions)))
 
 
+def superpixel_row(n, lam, n_orient, cw, g, merge):
+    import numpy as np
+    import torch
+    from gabor_color_image_segmentation_amd import Segmenter, superpixel_grid
+    from gabor_color_image_segmentation_amd.evaluate_gpu import all_scores_batch_device
+    from gabor_color_image_segmentation_amd.groundtruth import PackedTruth
+    gold = os.path.join(ROOT, "tests", "golden")
+    pack = np.load(os.path.join(gold, "bsd_val_images.npz"))
+    truth = PackedTruth(os.path.join(gold, "bsd500_truth.npz"))
+    ids = [str(i) for i in pack["ids"]]
+    rows = []
+    for shape in sorted({pack["img_" + i].shape[:2] for i in ids}):
+        group = [i for i in ids if pack["img_" + i].shape[:2] == shape]
+        m = superpixel_grid(shape[0], shape[1], n)[0] ** 2 // 4 if merge == "auto" else int(merge)
+        seg = Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, n_superpixels=n, spatial_weight=lam, min_region_size=m)
+        labels = seg.segment_device(torch.from_numpy(np.stack([pack["img_" + i] for i in group])).cuda())
+        rows += all_scores_batch_device(labels, truth.to_device(group))
+    print("| n | lambda | n_orient | w | g | m | boundary recall | underseg | undersegNP | compactness | regions |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|")
+    print("| %d | %d | %d | %g | %d | %s | %s | %.1f |" % (n, lam, n_orient, cw, g, merge, " | ".join(
+        "%.4f" % float(np.mean([r[k] for r in rows])) for k in ("recall", "underseg", "undersegNP", "compactness")),
+        float(np.mean([r["regions"] for r in rows]))))
+
+
 if __name__ == '__main__':
+    if "--superpixels" in sys.argv:
+        def one(name, conv, default):
+            return conv(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
+        superpixel_row(one("--superpixels", int, 300), one("--spatial-weight", int, 576), one("--n-orient", int, 6),
+                       one("--color-weight", float, 0.0), one("--chroma-gain", int, 0), one("--min-region-size", str, "0"))
+        sys.exit(0)
     if any(o in sys.argv for o in ("--min-region-size", "--smoothing", "--color-weight", "--chroma-gain", "--n-orient", "--position-weight")):
         def arg(name, conv, default):
             return [conv(v) for v in sys.argv[sys.argv.index(name) + 1].split(",")] if name in sys.argv else default

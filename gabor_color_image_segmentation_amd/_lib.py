@@ -69,6 +69,9 @@ SIGNATURES = {
     "gcs_smooth_features": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "gcs_colour_opponent": (_i, [_vp, _sz, _i, _vp, _vp]),
     "gcs_position_features": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "gcs_superpixel_grid": (_i, [_i, _i, _i, _vp, _vp, _vp]),
+    "gcs_superpixel_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "gcs_superpixel_segment": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
 }
 
 

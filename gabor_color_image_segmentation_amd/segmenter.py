@@ -325,9 +325,12 @@ class HipOps:
                    "gcs_position_features")
 
     @_on_device
-    def features_unpack(self, feats, b, h, w):
+    def features_unpack(self, feats, b, h, w, out=None):
         d = self.bank.n_features
-        out = self.torch.empty((b, d, h, w), dtype=self.torch.int16, device=self.device)
+        if out is None:
+            out = self.torch.empty((b, d, h, w), dtype=self.torch.int16, device=self.device)
+        elif out.dtype != self.torch.int16 or tuple(out.shape) != (b, d, h, w) or not out.is_contiguous():
+            raise ValueError("out must be a contiguous (B,D,H,W) int16 tensor")
         _lib.check(self.lib.gcs_features_unpack(feats.data_ptr(), b, h, w, *self._bk, out.data_ptr(),
                                                 self._stream()), "gcs_features_unpack")
         return out
@@ -374,6 +377,33 @@ class HipOps:
             feats.data_ptr(), cent.data_ptr(), b, h, w, *self._bk, k, n_sets, 1 if reverse else 0, out.data_ptr(),
             1 if out.dtype == torch.uint8 else 0, None if scratch_labels is None else scratch_labels.data_ptr(),
             self._stream()), "gcs_kmeans_assign_raster")
+
+    def superpixel_buffers(self, b, h, w, n):
+        """What the stage of SPEC.md §13 needs beside the slab for one (batch, shape): the canonical (B,D,H,W) tensor the kernels
+        read and the workspace of ``gcs_superpixel_segment`` (a captured graph must own both)."""
+        need = self.lib.gcs_superpixel_workspace_bytes(b, h, w, self.bank.n_features, int(n))
+        if need == 0:
+            raise ValueError("no superpixel grid for this shape / bank (H, W <= 4096, D <= 207, 2 <= n <= 4096, ny * nx <= 4096)")
+        return (self.torch.empty((b, self.bank.n_features, h, w), dtype=self.torch.int16, device=self.device),
+                self.empty_bytes(need))
+
+    @_on_device
+    def superpixels(self, canon, b, h, w, ny, nx, spatial_weight, n_iter, out, workspace, centres=None):
+        """SPEC.md §13 on canonical features (``features_unpack``): ``out`` (B,H,W) int32 labels in 0 .. ny * nx - 1 of the last of
+        ``n_iter`` assigns; ``centres``: None or a (B, ny * nx, D + 2) int32 tensor that receives the centres that assign used
+        (D features, cy, cx). ``workspace``: from ``superpixel_buffers``. One call, 2 n_iter launches, capturable."""
+        torch, d = self.torch, self.bank.n_features
+        if canon.dtype != torch.int16 or tuple(canon.shape) != (b, d, h, w) or not canon.is_contiguous():
+            raise ValueError("canon must be the contiguous (B,D,H,W) int16 tensor of features_unpack")
+        if out.dtype != torch.int32 or tuple(out.shape) != (b, h, w) or not out.is_contiguous():
+            raise ValueError("out must be a contiguous (B,H,W) int32 tensor")
+        if centres is not None and (centres.dtype != torch.int32 or tuple(centres.shape) != (b, ny * nx, d + 2)
+                                    or not centres.is_contiguous()):
+            raise ValueError("centres must be a contiguous (B, ny * nx, D + 2) int32 tensor")
+        _lib.check(self.lib.gcs_superpixel_segment(canon.data_ptr(), b, h, w, d, int(ny), int(nx), int(spatial_weight), int(n_iter),
+                                                   workspace.data_ptr(), out.data_ptr(),
+                                                   None if centres is None else centres.data_ptr(), self._stream()),
+                   "gcs_superpixel_segment")
 
     def download(self, dst_pinned, src):
         """Device tensor -> pinned host tensor of the same bytes on the current stream, by SDMA (gcs_download)."""
@@ -478,6 +508,35 @@ def _check_smoothing(smoothing, bank) -> float:
     return K
 
 
+SUPERPIXELS_MAX = 4096        # SPEC.md §13: centres per image (the option's range and the grid's bound)
+_SP_SIDE_MAX, _SP_D_MAX = 4096, 207
+
+
+def superpixel_grid(height, width, n):
+    """SPEC.md §13 grid of ``n_superpixels = n`` on an image of ``height`` x ``width`` pixels: ``(S, ny, nx)`` with
+    S = max(1, rint(sqrt(H W / n))), ny = max(1, rint(H / S)), nx = max(1, rint(W / S)); rint is round-half-even on the float64
+    value (Python's ``round``). The stage runs K = ny * nx centres."""
+    s = max(1, round(math.sqrt(height * width / n)))
+    return s, max(1, round(height / s)), max(1, round(width / s))
+
+
+def _check_superpixels(n_superpixels, spatial_weight):
+    """SPEC.md §13 parameters: n the integer 0 (off) or 2..4096, lambda an integer in 1..65535."""
+    vals = []
+    for name, v, ok in (("n_superpixels", n_superpixels, lambda x: x == 0 or 2 <= x <= SUPERPIXELS_MAX),
+                        ("spatial_weight", spatial_weight, lambda x: 1 <= x <= 65535)):
+        try:
+            i = int(v)
+            good = i == v and not isinstance(v, bool) and ok(i)
+        except (TypeError, ValueError, OverflowError):
+            good = False
+        if not good:
+            raise ValueError(f"{name} must be " + ("the integer 0 (off) or 2..4096" if name == "n_superpixels"
+                                                   else "an integer in 1..65535") + f", got {v!r}")
+        vals.append(i)
+    return tuple(vals)
+
+
 def lloyd(ops, feats, b, h, w, k, n_iter, mode, labels, partials, cent, sums, dist_group=None,
           rows=None, init=None, raster=None, debug=_ENV_DEBUG, fold=None):
     """SPEC.md §4 schedule on one feature slab. ``mode``: 'per_image' or 'global'.
@@ -569,7 +628,12 @@ class Segmenter:
     def __init__(self, n_scales=4, n_orient=6, k=8, n_iter=10, ksize=13, f_max=0.4,
                  ratio=math.sqrt(2.0), bandwidth=1.0, connectivity=False, device="cuda:0", ops=None,
                  slab_candidates=1, min_region_size=0, smoothing=0.0, color_weight=0.0, chroma_gain=0,
-                 position_weight=0):
+                 position_weight=0, n_superpixels=0, spatial_weight=576):
+        """``n_superpixels = n`` (SPEC.md §13; 0 = off, 2..4096): grid-local k-means instead of the Lloyd stage - about n compact
+        superpixels per image (K = ny * nx of ``superpixel_grid``) on the same features; ``k`` and ``mode`` are then unused (centres
+        are per image). ``spatial_weight`` = lambda (1..65535, default 576) weighs the squared pixel distance to a centre against
+        the squared feature distance: larger = more compact. Recommended pairing: ``min_region_size = S * S // 4`` with S of
+        ``superpixel_grid(H, W, n)``, which turns the label map into connected regions and merges the fragments."""
         if not (1 <= k <= _lib.K_MAX):
             raise ValueError(f"k must be in 1..{_lib.K_MAX}")
         if n_iter < 1:
@@ -585,7 +649,12 @@ class Segmenter:
         self.position_weight = check_position_weight(position_weight)   # SPEC.md §12: a coordinate slot behind every scale's filters
         self.bank = make_bank(n_scales, n_orient, ksize, f_max, ratio, bandwidth, self.color_weight, self.position_weight)
         self.smoothing = _check_smoothing(smoothing, self.bank)     # SPEC.md §10, between the Gabor stage and k-means
+        self.n_superpixels, self.spatial_weight = _check_superpixels(n_superpixels, spatial_weight)   # SPEC.md §13 (0: §4's Lloyd stage)
+        if self.n_superpixels > 0 and self.bank.n_features > _SP_D_MAX:
+            raise ValueError(f"n_superpixels needs a bank of at most {_SP_D_MAX} features, this one has {self.bank.n_features}")
         self.ops = ops if ops is not None else HipOps(self.bank, device, self.smoothing, self.chroma_gain)
+        if self.n_superpixels > 0 and not hasattr(self.ops, "superpixels"):
+            raise ValueError("Segmenter(n_superpixels=n, ops=...) needs ops that have the superpixel stage")
         if self.smoothing > 0 and getattr(self.ops, "smoothing", 0.0) != self.smoothing:
             raise ValueError("Segmenter(smoothing=K, ops=...) needs ops built with the same smoothing")
         if getattr(self.ops, "chroma_gain", 0) != self.chroma_gain:
@@ -712,6 +781,8 @@ class Segmenter:
         if h < 8 or w < 8:
             raise ValueError("images must be at least 8x8")
         check_position_range(self.position_weight, h, w)
+        if self.n_superpixels > 0:
+            self._superpixel_check(h, w, mode, dist_group=dist_group)
         on_gpu = self.native
         if on_gpu and imgs.device != self.ops.device:
             raise ValueError(f"imgs live on {imgs.device}, this Segmenter on {self.ops.device}")
@@ -728,6 +799,9 @@ class Segmenter:
                 n = min(g, b - g0)
                 ws = self._workspace(n, h, w, mode) if n == g else self._tail_workspace(n, h, w, mode)
                 self._features(imgs[g0:g0 + n], ws, n, h, w)
+                if self.n_superpixels > 0:                       # SPEC.md §13 instead of §4: features -> canonical tensor -> stage
+                    self._superpixel_stage(ws, n, h, w, out[g0:g0 + n])
+                    continue
                 direct = hasattr(self.ops, "assign_raster")      # the last pass writes the raster map itself
                 lloyd(self.ops, ws["feats"], n, h, w, self.k, self.n_iter, mode, ws["labels"], ws["partials"],
                       ws["cent"], ws["sums"], dist_group, raster=out[g0:g0 + n] if direct else None, debug=self.debug,
@@ -743,6 +817,52 @@ class Segmenter:
                 self.ops.connected_regions(out, regions)
                 out.copy_(regions)
         return out
+
+    def _superpixel_check(self, h, w, mode="per_image", out_dtype=None, dist_group=None):
+        """The argument rules of SPEC.md §13 for one image shape, before anything is launched; returns (ny, nx)."""
+        if mode != "per_image":
+            raise ValueError("n_superpixels > 0: centres are per image, mode must be 'per_image'")
+        if dist_group is not None:
+            raise ValueError("n_superpixels > 0 does not run over a dist_group")
+        if h > _SP_SIDE_MAX or w > _SP_SIDE_MAX:
+            raise ValueError(f"n_superpixels > 0 needs images of at most {_SP_SIDE_MAX} x {_SP_SIDE_MAX} pixels")
+        _, ny, nx = superpixel_grid(h, w, self.n_superpixels)
+        if ny * nx > SUPERPIXELS_MAX:
+            raise ValueError(f"n_superpixels = {self.n_superpixels} on {h} x {w} pixels gives a grid of {ny} x {nx} centres, "
+                             f"more than {SUPERPIXELS_MAX}")
+        if out_dtype is not None and np.dtype(out_dtype) == np.uint8 and ny * nx > 256:
+            raise ValueError(f"out_dtype uint8 cannot hold the {ny * nx} labels of this superpixel grid")
+        return ny, nx
+
+    def _superpixel_stage(self, ws, b, h, w, out, centres=None):
+        """SPEC.md §13 on the slab ``ws["feats"]`` that ``_features`` has filled: unpack to the canonical tensor, then the one call
+        that enqueues every pass. The buffers join the workspace at first use."""
+        _, ny, nx = superpixel_grid(h, w, self.n_superpixels)
+        if "sp" not in ws:
+            ws["sp"] = self.ops.superpixel_buffers(b, h, w, self.n_superpixels)
+        canon, spws = ws["sp"]
+        self.ops.features_unpack(ws["feats"], b, h, w, out=canon)
+        self.ops.superpixels(canon, b, h, w, ny, nx, self.spatial_weight, self.n_iter, out, spws, centres)
+
+    def superpixels_device(self, imgs):
+        """(B,H,W,3) uint8 device tensor -> (labels (B,H,W) int32, centres (B, ny * nx, D + 2) int32: the D features, cy, cx the
+        last assign used) of SPEC.md §13, without the post-passes (tests / debugging)."""
+        torch = _torch()
+        if self.n_superpixels == 0:
+            raise ValueError("superpixels_device needs Segmenter(n_superpixels=n) with n > 0")
+        imgs = imgs.contiguous()
+        b, h, w, _ = imgs.shape
+        if h < 8 or w < 8:
+            raise ValueError("images must be at least 8x8")
+        check_position_range(self.position_weight, h, w)
+        ny, nx = self._superpixel_check(h, w)
+        with torch.cuda.device(self.ops.device):
+            ws = self._tail_workspace(b, h, w, "per_image")
+            self._features(imgs, ws, b, h, w)
+            out = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
+            centres = torch.empty((b, ny * nx, self.bank.n_features + 2), dtype=torch.int32, device=imgs.device)
+            self._superpixel_stage(ws, b, h, w, out, centres)
+        return out, centres
 
     def _tail_workspace(self, n, h, w, mode):
         n_sets = n if mode == "per_image" else 1
@@ -791,6 +911,8 @@ class Segmenter:
         the unsharded result. Needs torch.distributed initialised when the image is split.
         """
         torch = _torch()
+        if self.n_superpixels > 0:
+            raise ValueError("n_superpixels > 0 is not supported on row strips")
         if self.min_region_size > 0:
             raise ValueError("min_region_size is not supported on row strips (regions would cross strip boundaries)")
         if self.smoothing > 0:
@@ -851,6 +973,8 @@ class Segmenter:
         (r0, r1) = ``shard_rows(height, world, rank, n_levels, ksize)[:2]``. Every rank must own at least the halo
         (``halo_rows(n_levels, ksize)`` rows), so that a halo comes from ONE neighbour. Returns the (B, r1-r0, W) int32 labels."""
         torch = _torch()
+        if self.n_superpixels > 0:
+            raise ValueError("n_superpixels > 0 is not supported on row strips")
         if self.min_region_size > 0:
             raise ValueError("min_region_size is not supported on row strips (regions would cross strip boundaries)")
         if self.smoothing > 0:
@@ -936,12 +1060,16 @@ class Segmenter:
         if h < 8 or w < 8:
             raise ValueError("images must be at least 8x8")
         check_position_range(self.position_weight, h, w)
+        if self.n_superpixels > 0:
+            self._superpixel_check(h, w, mode, out_dtype)
         dist_on = False
         if mode == "global":
             import torch.distributed as td
             dist_on = td.is_available() and td.is_initialized()
+        # (superpixels: a small call replays its graph like any other; a large one takes the plain path)
         if not self.native or self.connectivity or self.min_region_size > 0 or dist_on or self.debug.force_collectives \
-                or self.group_size(b, h, w, mode) < b:
+                or self.group_size(b, h, w, mode) < b \
+                or (self.n_superpixels > 0 and (b * h * w > _GRAPH_MAX_PIXELS or self.debug.no_graph)):
             dev = torch.from_numpy(np.asarray(imgs)).to(self.ops.device)   # plain path (test stand-ins, post-passes, collectives)
             return self.segment_device(dev, mode).cpu().numpy().astype(out_dtype, copy=False)
 
@@ -1007,8 +1135,11 @@ class Segmenter:
         if mode == "global":
             import torch.distributed as td
             dist_on = td.is_available() and td.is_initialized()
-        if not self.native or self.connectivity or self.min_region_size > 0 or dist_on or self.debug.force_collectives:
-            for imgs in batches:                                   # no pipeline for post-passes / collectives / stand-ins
+        if self.n_superpixels > 0 and mode != "per_image":
+            raise ValueError("n_superpixels > 0: centres are per image, mode must be 'per_image'")
+        if not self.native or self.connectivity or self.min_region_size > 0 or dist_on or self.debug.force_collectives \
+                or self.n_superpixels > 0:
+            for imgs in batches:                                   # no pipeline for post-passes / collectives / stand-ins / §13
                 yield self.segment_batch(imgs, mode, out_dtype)
             return
         pipe = _StreamPipe(self, mode, out_dtype, depth)
@@ -1034,6 +1165,11 @@ class Segmenter:
                 ws = self._tail_workspace(b, h, w, mode)
                 dev_in = torch.empty((b, h, w, 3), dtype=torch.uint8, device=dev)
                 dev_out = torch.empty((b, h, w), dtype=torch.uint8 if out_dtype == np.uint8 else torch.int32, device=dev)
+                # SPEC.md §13: the canonical tensor, the stage's workspace and its int32 label map belong to the entry too
+                sp = None
+                if self.n_superpixels > 0:
+                    sp = self.ops.superpixel_buffers(b, h, w, self.n_superpixels) + superpixel_grid(h, w, self.n_superpixels)[1:] \
+                        + (self.spatial_weight, dev_out if out_dtype != np.uint8 else torch.empty((b, h, w), dtype=torch.int32, device=dev))
                 pin_in = torch.empty((b, h, w, 3), dtype=torch.uint8, pin_memory=True)
                 # the graph bakes raw pointers in: every buffer it touches, the Gabor scratch included, belongs to the
                 # entry and lives exactly as long as the graph does (the shared scratch of HipOps is replaced, and its
@@ -1056,6 +1192,13 @@ class Segmenter:
                         ops.smooth_features(ws["feats"], b, h, w, scratch=smooth)
                     if position:
                         ops.position_features(ws["feats"], b, h, w)
+                    if sp is not None:
+                        canon, spws, ny, nx, lam, out32 = sp
+                        ops.features_unpack(ws["feats"], b, h, w, out=canon)
+                        ops.superpixels(canon, b, h, w, ny, nx, lam, n_iter, out32, spws)
+                        if out32 is not dev_out:
+                            dev_out.copy_(out32)           # (K <= 256 was checked: the narrowing keeps every label)
+                        return
                     lloyd(ops, ws["feats"], b, h, w, k, n_iter, mode, ws["labels"], ws["partials"], ws["cent"],
                           ws["sums"], raster=dev_out, debug=debug, fold=ws.get("fold"))
                 dev_in.zero_()
@@ -1071,7 +1214,7 @@ class Segmenter:
                     _CAPTURES.fell_back(key, "torch.cuda.graph raised RuntimeError")
                     graph = None
                     torch.cuda.current_stream(dev).synchronize()
-                ent = dict(graph=graph, step=step, ws=ws, dev_in=dev_in, dev_out=dev_out, pin_in=pin_in, scratch=scratch)
+                ent = dict(graph=graph, step=step, ws=ws, dev_in=dev_in, dev_out=dev_out, pin_in=pin_in, scratch=scratch, sp=sp)
                 if len(self._graphs) >= 4:                 # evicted plans leave through the guard: never inside an open capture
                     _CAPTURES.retire([self._graphs.pop(next(iter(self._graphs)))])
                 self._graphs[key] = ent
@@ -1142,7 +1285,8 @@ class Segmenter:
         pipes, tags = {}, {}                   # per shape: the pipeline of its FULL batches and the image indices in flight
         if self.min_region_size > 0 and out_dtype == np.uint8:
             raise ValueError("min_region_size > 0 needs int32 labels")
-        piped = self.native and not self.connectivity and self.min_region_size == 0 and not self.debug.force_collectives
+        piped = self.native and not self.connectivity and self.min_region_size == 0 and not self.debug.force_collectives \
+            and self.n_superpixels == 0
 
         def emit(idx, labels):
             for i, lab in zip(idx, labels):

@@ -356,6 +356,32 @@ int gcs_colour_opponent(const uint8_t *img_dev, size_t n_pixels, int gain, uint8
 int gcs_position_features(uint16_t *feats_dev, int B, int H, int W, int n_scales, int n_orient, int weight, int y0,
                           gcs_stream_t stream);
 
+/* ---- superpixels: grid-local k-means (SPEC.md §13) ------------------------------------------------ */
+
+/* The Lloyd stage of §4 replaced by K = ny * nx centres per image on a grid, each pixel compared with the centres of the 3 x 3 grid
+ * cells around its own only: dist = sum_d (x_d - c_d)^2 + lambda ((y - cy)^2 + (x - cx)^2) in 64-bit integers, ties to the lowest
+ * centre index; update = §4's rounding rule on every feature and on cy, cx (an empty centre keeps its values); n_iter assigns, n_iter - 1
+ * updates. The kernels read the CANONICAL tensor of gcs_features_unpack, [B][D][H][W] uint16 (2 D bytes per pixel per pass), not the slab.
+ *   gcs_superpixel_grid             host only: S = max(1, rint(sqrt(H W / n))), ny = max(1, rint(H / S)), nx = max(1, rint(W / S)), rint =
+ *                                   round-half-even on the double value (any out pointer may be NULL). GCS_EINVAL outside 1 <= H, W <= 4096,
+ *                                   2 <= n <= 4096. ny * nx may exceed 4096 (small S): the two calls below refuse such a grid.
+ *   gcs_superpixel_workspace_bytes  host only: bytes of workspace_dev for the grid of (H, W, n): per image the centres, their positions
+ *                                   and one [K][D + 3] row set of uint64 sums (features, y, x, count). 0 for a bad argument. Contents are
+ *                                   undefined before and after a call (nothing to zero).
+ *   gcs_superpixel_segment          enqueues the whole schedule on `stream`: init (centre (i, j) := the pixel at cy = floor((2i+1) H /
+ *                                   (2 ny)), cx = floor((2j+1) W / (2 nx))), then n_iter assign passes with an update launch behind all
+ *                                   but the last: 2 n_iter launches (+1 with centres_out_dev). No allocation, no host synchronisation
+ *                                   (capturable). labels_out_dev int32 [B][H][W] in 0 .. K-1 (the last assign). centres_out_dev: NULL, or
+ *                                   int32 [B][K][D + 2] = the D features, cy, cx of every centre as the last assign used them.
+ * GCS_EINVAL, with nothing launched: a NULL feats / workspace / labels pointer, B outside 1..65535, H or W outside 1..4096, D outside
+ * 1..207, ny outside 1..H, nx outside 1..W, ny * nx > 4096, lambda outside 1..65535, n_iter < 1. In that domain a distance is at most
+ * 207 * 46340^2 + 65535 * 2 * 4095^2 < 2^63.
+ * Added within ABI 18: new entry points change no existing call, so GCS_ABI_VERSION did not move. */
+int gcs_superpixel_grid(int H, int W, int n, int *S_out, int *ny_out, int *nx_out);
+size_t gcs_superpixel_workspace_bytes(int B, int H, int W, int D, int n);
+int gcs_superpixel_segment(const uint16_t *feats_canonical_dev, int B, int H, int W, int D, int ny, int nx, int lambda, int n_iter,
+                           void *workspace_dev, int32_t *labels_out_dev, int32_t *centres_out_dev, gcs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
