@@ -28,6 +28,10 @@ grid-local k-means instead of the Lloyd stage) with the other options of the tab
 `--min-region-size`, taken as single values; `--min-region-size auto` = S * S // 4 per image shape): mean boundary recall, underseg,
 undersegNP, compactness and regions from the GPU path; `--superpixels 300 --n-orient 5 --color-weight 0.125 --chroma-gain 4
 --min-region-size auto` is the recommended setting.
+`--regions R[,R...]` beside `--superpixels`: the superpixels merged to R regions (SPEC.md §14); one tree per batch
+(`Segmenter.region_tree_device`), one cut per R (`cut_regions_device`), `--min-region-size` applied to every cut: a row per R with mean
+boundary recall, precision, F, PRI, VoI, covering and regions; `--superpixels 300 --regions 8 --n-orient 5 --color-weight 0.125
+--chroma-gain 4` is the recommended setting.
 """
 import os
 import sys
@@ -135,10 +139,47 @@ def superpixel_row(n, lam, n_orient, cw, g, merge):
         float(np.mean([r["regions"] for r in rows]))))
 
 
+def region_rows(n, lam, n_orient, cw, g, merge, regions):
+    import numpy as np
+    import torch
+    from gabor_color_image_segmentation_amd import Segmenter, superpixel_grid
+    from gabor_color_image_segmentation_amd.evaluate_gpu import all_scores_batch_device
+    from gabor_color_image_segmentation_amd.groundtruth import PackedTruth
+    gold = os.path.join(ROOT, "tests", "golden")
+    pack = np.load(os.path.join(gold, "bsd_val_images.npz"))
+    truth = PackedTruth(os.path.join(gold, "bsd500_truth.npz"))
+    ids = [str(i) for i in pack["ids"]]
+    rows = {r: [] for r in regions}
+    seg = Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, n_superpixels=n, spatial_weight=lam)
+    for shape in sorted({pack["img_" + i].shape[:2] for i in ids}):
+        group = [i for i in ids if pack["img_" + i].shape[:2] == shape]
+        m = superpixel_grid(shape[0], shape[1], n)[0] ** 2 // 4 if merge == "auto" else int(merge)
+        labels, merges, _, alive = seg.region_tree_device(torch.from_numpy(np.stack([pack["img_" + i] for i in group])).cuda())
+        dt = truth.to_device(group)
+        for r in regions:                                # one tree, a relabel per R
+            cut = seg.cut_regions_device(labels, merges, alive, r)
+            if m > 0:
+                post = torch.empty_like(cut)
+                seg.ops.merge_small_regions(cut, m, post)
+                cut = post
+            rows[r] += all_scores_batch_device(cut, dt, agreement=True)
+    keys = ("recall", "precision", "fmeasure", "PRI", "VoI", "covering")
+    print("| n | lambda | n_orient | w | g | R | m | R | P | F | PRI | VoI | covering | regions |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+    for r in regions:
+        print("| %d | %d | %d | %g | %d | %d | %s | %s | %.1f |" % (n, lam, n_orient, cw, g, r, merge, " | ".join(
+            "%.4f" % float(np.mean([x[k] for x in rows[r]])) for k in keys), float(np.mean([x["regions"] for x in rows[r]]))))
+
+
 if __name__ == '__main__':
     if "--superpixels" in sys.argv:
         def one(name, conv, default):
             return conv(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
+        if "--regions" in sys.argv:
+            region_rows(one("--superpixels", int, 300), one("--spatial-weight", int, 576), one("--n-orient", int, 6),
+                        one("--color-weight", float, 0.0), one("--chroma-gain", int, 0), one("--min-region-size", str, "0"),
+                        [int(v) for v in one("--regions", str, "8").split(",")])
+            sys.exit(0)
         superpixel_row(one("--superpixels", int, 300), one("--spatial-weight", int, 576), one("--n-orient", int, 6),
                        one("--color-weight", float, 0.0), one("--chroma-gain", int, 0), one("--min-region-size", str, "0"))
         sys.exit(0)

@@ -1,0 +1,438 @@
+// region_tree.hip — SPEC.md §14: agglomerative merging of a label map's regions on their adjacency graph (gfx950 only).
+//
+// Nodes = the labels 0 .. K-1 that own a pixel; state per node = pixel count n, exact feature sums S_d, mean m_d = floor((2 S_d + n) /
+// (2 n)); cost(A, B) = sum_d (m_A,d - m_B,d)^2 * min(n_A, n_B) in unsigned 64 bits (< 2^62); per round every node picks the adjacent
+// node of least (cost, rep), mutual picks merge, the round's merges are listed in (cost, rep) order. One call enqueues
+//   rt_zero_kernel      the [K][D + 1] uint64 sums and the K x K adjacency bit matrix of every image := 0.
+//   rt_stats_kernel     one workgroup per 8 x 32 pixel tile, one thread per pixel: ONE read of the canonical tensor and of the label
+//                       map. Sums: the labels a tile sees get a row of uint32 accumulators in LDS through a 32-slot hash table (256
+//                       pixels * 65 535 < 2^32), eight lanes that agree on the label add one sum, touched rows are flushed with 64-bit
+//                       vector atomics; a tile that sees more than 32 labels adds straight into the global rows (slow, exact).
+//                       Adjacency: a pixel whose right / lower neighbour carries another in-range label sets bits (a, b) and (b, a)
+//                       (an atomic OR only when the bit is not seen set: every later pixel of the same border reads and skips).
+//   rt_merge_kernel     ONE workgroup of 1024 threads per image runs every round (the trip count is data, so the loop lives here):
+//                       pick (a wave per node whose neighbourhood changed: it walks the node's adjacency row, lanes over the planes of a cost), mutual pairs,
+//                       rank of every pair in (cost, rep) order = its row of the merge list, merge (sums, mean, adjacency row OR),
+//                       remap (the merged node's neighbours drop the dead label's bit, gain the rep's, and pick again next round).
+//                       Picks, costs, pair list and flags sit in LDS, the means too where they fit beside them; sums and adjacency
+//                       stay in the workspace (L2). Only workgroup barriers: images are independent.
+// and gcs_region_tree_cut one launch: a workgroup per image builds the parent table of the first alive - R merges in LDS (parent <
+// child, so pointer jumping needs no union by rank), marks the labels in use, numbers the roots in increasing order and relabels.
+// No allocation, no host synchronisation: every launch sits on the caller's stream (and inside a captured graph).
+#include <algorithm>
+
+#include "common.h"
+
+namespace {
+
+constexpr int RT_TH = 8, RT_TW = 32;         // statistics tile: 8 rows of 32 pixels, 256 threads
+constexpr int RT_SLOTS = 32;                 // labels a tile accumulates in LDS
+constexpr int RT_D_MAX = 207, RT_K_MAX = 4096, RT_HW_MAX = 4096;
+constexpr int RT_T = 1024, RT_NW = RT_T / 64;   // merge / cut workgroup
+constexpr unsigned RT_NONE = 0xffffu;        // "no adjacent node" (a label is below 4096)
+constexpr size_t RT_LDS_MAX = 65536;
+
+typedef unsigned long long u64;
+
+struct RtArgs {
+    const uint16_t *feats;                   // [B][D][H][W]
+    const int *labels;                       // [B][H][W]
+    u64 *sums;                               // [B][K][D + 1] = the D feature sums, count
+    unsigned *adj;                           // [B][K][KW] bit (a, b): a and b are adjacent
+    uint16_t *mean;                          // [B][K][D] (used when the means do not fit LDS)
+    int *merges;                             // [B][K - 1][2]
+    u64 *costs;                              // [B][K - 1] or NULL
+    int *alive;                              // [B]
+    int B, H, W, D, K, KW;
+};
+
+__host__ __device__ inline size_t rt_align(size_t n) { return (n + 255) & ~(size_t)255; }
+
+__device__ __forceinline__ unsigned rt_ld(const unsigned *p) {             // a word other waves change with atomics: read it in L2
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(256) void rt_zero_kernel(uint4 *p, size_t n16) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) p[i] = make_uint4(0, 0, 0, 0);
+}
+
+__device__ __forceinline__ void rt_edge(unsigned *adj, int KW, int a, int b) {
+    unsigned *wa = adj + (size_t)a * KW + (b >> 5), *wb = adj + (size_t)b * KW + (a >> 5);
+    const unsigned ba = 1u << (b & 31), bb = 1u << (a & 31);
+    if (!(rt_ld(wa) & ba)) atomicOr(wa, ba);                               // (read in L2, where the atomics land)
+    if (!(rt_ld(wb) & bb)) atomicOr(wb, bb);
+}
+
+__global__ __launch_bounds__(256) void rt_stats_kernel(RtArgs A) {
+    extern __shared__ __attribute__((aligned(16))) unsigned rt_smem[];
+    const int tid = (int)threadIdx.x, b = (int)blockIdx.z, D = A.D, E = D + 1, K = A.K;
+    unsigned *s_acc = rt_smem;                                             // [RT_SLOTS][E]
+    int *s_keys = reinterpret_cast<int *>(s_acc + RT_SLOTS * E);          // [RT_SLOTS] label of the slot, -1: free
+    int *s_over = s_keys + RT_SLOTS;                                       // more labels than slots
+    for (int idx = tid; idx < RT_SLOTS * E; idx += 256) s_acc[idx] = 0u;
+    if (tid < RT_SLOTS) s_keys[tid] = -1;
+    if (tid == 0) *s_over = 0;
+    __syncthreads();
+    const size_t hw = (size_t)A.H * A.W;
+    const int yy = (int)blockIdx.y * RT_TH + tid / RT_TW, xx = (int)blockIdx.x * RT_TW + tid % RT_TW;
+    const bool valid = yy < A.H && xx < A.W;
+    const int y = yy < A.H ? yy : A.H - 1, x = xx < A.W ? xx : A.W - 1;    // clamped: reads stay inside
+    const int *lab = A.labels + (size_t)b * hw + (size_t)y * A.W + x;
+    const int l = *lab;
+    const bool in = valid && (unsigned)l < (unsigned)K;                    // a label outside 0 .. K-1 is counted nowhere
+    unsigned *adj = A.adj + (size_t)b * K * A.KW;
+    if (in) {
+        if (x + 1 < A.W) {
+            const int r = lab[1];
+            if (r != l && (unsigned)r < (unsigned)K) rt_edge(adj, A.KW, l, r);
+        }
+        if (y + 1 < A.H) {
+            const int r = lab[A.W];
+            if (r != l && (unsigned)r < (unsigned)K) rt_edge(adj, A.KW, l, r);
+        }
+    }
+    int slot = -1;
+    if (in) {
+        const unsigned h = ((unsigned)l * 2654435761u) >> 27;
+        for (int p = 0; p < RT_SLOTS; ++p) {
+            const int s = (int)((h + p) & (RT_SLOTS - 1));
+            const int old = atomicCAS(&s_keys[s], -1, l);
+            if (old == -1 || old == l) {
+                slot = s;
+                break;
+            }
+        }
+        if (slot < 0) *s_over = 1;
+    }
+    __syncthreads();
+    const uint16_t *px = A.feats + (size_t)b * D * hw + (size_t)y * A.W + x;
+    u64 *g_sums = A.sums + (size_t)b * K * E;
+    if (*s_over) {                                                         // (uniform over the workgroup)
+        if (in) {
+            u64 *row = g_sums + (size_t)l * E;
+            for (int d = 0; d < D; ++d) atomicAdd(row + d, (u64)px[(size_t)d * hw]);
+            atomicAdd(row + D, 1ull);
+        }
+        return;
+    }
+    // eight neighbouring lanes that are all counted and agree on the label add ONE sum (fewer same-address LDS atomics)
+    int same = in ? 1 : 0;
+#pragma unroll
+    for (int m = 1; m < 8; m <<= 1) {
+        const int os = __shfl_xor(slot, m), osame = __shfl_xor(same, m);
+        same = same && osame && os == slot;
+    }
+    unsigned *row = s_acc + (in ? slot : 0) * E;
+    const bool lead = (tid & 7) == 0;
+    for (int d = 0; d < E; ++d) {
+        const unsigned v = d < D ? px[(size_t)d * hw] : 1u;
+        unsigned t = v;
+#pragma unroll
+        for (int m = 1; m < 8; m <<= 1) t += (unsigned)__shfl_xor((int)t, m);
+        if (same) {
+            if (lead) atomicAdd(row + d, t);
+        } else if (in) {
+            atomicAdd(row + d, v);
+        }
+    }
+    __syncthreads();
+    for (int idx = tid; idx < RT_SLOTS * E; idx += 256) {
+        const int s = idx / E, e = idx - s * E;
+        const unsigned v = s_acc[idx];
+        if (v) atomicAdd(g_sums + (size_t)s_keys[s] * E + e, (u64)v);
+    }
+}
+
+// LDS of the merge kernel: 16 bytes of counters, then per node the pick's cost (8 bytes) and target (2), a slot of the pair list (2)
+// and a flag byte (bit 0: alive, bit 1: picks again), then the means where they fit.
+__host__ __device__ inline size_t rt_state_bytes(int K) { return (16 + (size_t)13 * K + 15) & ~(size_t)15; }
+
+// sum_d (ma_d - mb_d)^2 by one wave, the planes spread over its lanes; every lane returns the sum
+__device__ __forceinline__ u64 rt_delta(const uint16_t *ma, const uint16_t *mb, int D, int lane) {
+    u64 acc = 0;
+    if ((D & 1) == 0) {                                                    // rows of an even D start on a 32-bit boundary: two planes per load
+        const unsigned *pa = reinterpret_cast<const unsigned *>(ma), *pb = reinterpret_cast<const unsigned *>(mb);
+        for (int i = lane; i < (D >> 1); i += 64) {
+            const unsigned va = pa[i], vb = pb[i];
+            const int d0 = (int)(va & 0xffffu) - (int)(vb & 0xffffu), d1 = (int)(va >> 16) - (int)(vb >> 16);
+            acc += (u64)((unsigned)(d0 * d0) + (unsigned)(d1 * d1));      // 2 * 46 340^2 < 2^32 (a mean is at most 46 340)
+        }
+    } else {
+        for (int d = lane; d < D; d += 64) {
+            const int df = (int)ma[d] - (int)mb[d];
+            acc += (u64)(unsigned)(df * df);
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m);
+    return acc;
+}
+
+__global__ __launch_bounds__(RT_T) void rt_merge_kernel(RtArgs A, int mean_in_lds) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char rt_lds[];
+    const int tid = (int)threadIdx.x, b = (int)blockIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int K = A.K, D = A.D, E = D + 1, KW = A.KW;
+    int *s_cnt = reinterpret_cast<int *>(rt_lds);                          // [0] alive, [1] pairs of the round
+    u64 *s_cost = reinterpret_cast<u64 *>(rt_lds + 16);                    // [K]
+    uint16_t *s_t = reinterpret_cast<uint16_t *>(rt_lds + 16 + (size_t)8 * K);      // [K] the pick; of a dead node: who absorbed it
+    uint16_t *s_pair = reinterpret_cast<uint16_t *>(rt_lds + 16 + (size_t)10 * K);  // [K] the smaller rep of every mutual pair
+    unsigned char *s_flag = rt_lds + 16 + (size_t)12 * K;                  // [K]
+    u64 *sums = A.sums + (size_t)b * K * E;
+    unsigned *adj = A.adj + (size_t)b * K * KW;
+    uint16_t *mean = mean_in_lds ? reinterpret_cast<uint16_t *>(rt_lds + rt_state_bytes(K)) : A.mean + (size_t)b * K * D;
+    int *merges = A.merges + (size_t)b * (K - 1) * 2;
+    u64 *costs = A.costs ? A.costs + (size_t)b * (K - 1) : nullptr;
+
+    if (tid < 2) s_cnt[tid] = 0;
+    __syncthreads();
+    for (int q = tid; q < K; q += RT_T) {
+        const u64 n = sums[(size_t)q * E + D];
+        s_flag[q] = n ? 3 : 0;
+        s_t[q] = (uint16_t)RT_NONE;
+        s_cost[q] = 0;
+        if (n) atomicAdd(&s_cnt[0], 1);
+    }
+    for (int idx = tid; idx < K * D; idx += RT_T) {
+        const int q = idx / D, d = idx - q * D;
+        const u64 n = sums[(size_t)q * E + D];
+        mean[idx] = n ? (uint16_t)((2 * sums[(size_t)q * E + d] + n) / (2 * n)) : (uint16_t)0;
+    }
+    for (int t = tid; t < K - 1; t += RT_T) {
+        merges[2 * t] = -1;
+        merges[2 * t + 1] = -1;
+        if (costs) costs[t] = 0;
+    }
+    __threadfence();
+    __syncthreads();
+    int alive = s_cnt[0], base = 0;
+    if (tid == 0) A.alive[b] = alive;
+
+    while (alive > 1) {
+        // pick: the adjacent node of least (cost, rep), for every node whose neighbourhood changed (all of them in round one)
+        for (int q = wave; q < K; q += RT_NW) {
+            if (s_flag[q] != 3) continue;                                  // (uniform over the wave)
+            const u64 nq = sums[(size_t)q * E + D];
+            u64 best = ~0ull;
+            unsigned bt = RT_NONE;
+            for (int w0 = 0; w0 < KW; w0 += 64) {                          // the row's words, 64 at a time; the wave then walks the set bits
+                const unsigned mine = w0 + lane < KW ? rt_ld(adj + (size_t)q * KW + w0 + lane) : 0u;
+                u64 nz = __ballot(mine != 0u);
+                while (nz) {
+                    const int src = __ffsll((long long)nz) - 1;
+                    nz &= nz - 1;
+                    unsigned bits = (unsigned)__shfl((int)mine, src);
+                    while (bits) {                                         // (uniform: every lane holds the same word)
+                        const unsigned r = (unsigned)(32 * (w0 + src) + __ffs((int)bits) - 1);
+                        bits &= bits - 1;
+                        const u64 nr = sums[(size_t)r * E + D];
+                        const u64 c = rt_delta(mean + (size_t)q * D, mean + (size_t)r * D, D, lane) * (nq < nr ? nq : nr);
+                        if (c < best || (c == best && r < bt)) {
+                            best = c;
+                            bt = r;
+                        }
+                    }
+                }
+            }
+            if (lane == 0) {
+                s_cost[q] = best;
+                s_t[q] = (uint16_t)bt;
+                s_flag[q] = 1;
+            }
+        }
+        __syncthreads();
+        // mutual pairs, listed by their smaller rep
+        for (int q = tid; q < K; q += RT_T) {
+            if (!(s_flag[q] & 1)) continue;
+            const unsigned t = s_t[q];
+            if (t != RT_NONE && (unsigned)q < t && s_t[t] == (unsigned)q) s_pair[atomicAdd(&s_cnt[1], 1)] = (uint16_t)q;
+        }
+        __syncthreads();
+        const int P = s_cnt[1];
+        if (P == 0) break;                                                 // out-of-range labels cut the graph apart: nothing is adjacent
+        // the round's rows of the merge list: a pair's rank in (cost, smaller rep) order
+        for (int i = tid; i < P; i += RT_T) {
+            const unsigned a = s_pair[i];
+            const u64 c = s_cost[a];
+            int rank = 0;
+            for (int j = 0; j < P; ++j) {
+                const unsigned aj = s_pair[j];
+                const u64 cj = s_cost[aj];
+                rank += (cj < c || (cj == c && aj < a)) ? 1 : 0;
+            }
+            merges[2 * (base + rank)] = (int)a;
+            merges[2 * (base + rank) + 1] = (int)s_t[a];
+            if (costs) costs[base + rank] = c;
+        }
+        // merge: a wave per pair (a < bq): sums add, the mean follows, a's adjacency row takes bq's bits
+        for (int i = wave; i < P; i += RT_NW) {
+            const unsigned a = s_pair[i], bq = s_t[a];
+            const u64 n = sums[(size_t)a * E + D] + sums[(size_t)bq * E + D];
+            for (int e = lane; e < D; e += 64) {
+                const u64 s = sums[(size_t)a * E + e] + sums[(size_t)bq * E + e];
+                sums[(size_t)a * E + e] = s;
+                mean[(size_t)a * D + e] = (uint16_t)((2 * s + n) / (2 * n));
+            }
+            if (lane == 0) sums[(size_t)a * E + D] = n;
+            for (int w = lane; w < KW; w += 64) {
+                const unsigned v = rt_ld(adj + (size_t)bq * KW + w);
+                if (v) atomicOr(adj + (size_t)a * KW + w, v);
+            }
+        }
+        __threadfence();
+        __syncthreads();
+        for (int i = tid; i < P; i += RT_T) {
+            const unsigned a = s_pair[i];
+            s_flag[s_t[a]] = 0;
+            s_flag[a] = 3;
+        }
+        __syncthreads();
+        // remap: every neighbour c of the merged node drops bq's bit, gains a's and picks again; a neighbour that died in this round
+        // stands for the node that absorbed it. Rows of living nodes hold bits of living nodes only when the round ends.
+        for (int i = wave; i < P; i += RT_NW) {
+            const unsigned a = s_pair[i], bq = s_t[a];
+            for (int w = lane; w < KW; w += 64) {
+                unsigned bits = rt_ld(adj + (size_t)a * KW + w);
+                while (bits) {
+                    const unsigned c = (unsigned)(32 * w + __ffs((int)bits) - 1);
+                    bits &= bits - 1;
+                    if (c == a || c == bq) continue;
+                    const unsigned cc = (s_flag[c] & 1) ? c : s_t[c];
+                    if (cc == a || cc >= (unsigned)K) continue;
+                    atomicAnd(adj + (size_t)cc * KW + (bq >> 5), ~(1u << (bq & 31)));
+                    atomicOr(adj + (size_t)cc * KW + (a >> 5), 1u << (a & 31));
+                    if (c != cc) {                                         // a's own row: the dead neighbour's bit becomes its rep's
+                        atomicAnd(adj + (size_t)a * KW + (c >> 5), ~(1u << (c & 31)));
+                        atomicOr(adj + (size_t)a * KW + (cc >> 5), 1u << (cc & 31));
+                    }
+                    s_flag[cc] = 3;
+                }
+            }
+            if (lane == 0) {
+                atomicAnd(adj + (size_t)a * KW + (a >> 5), ~(1u << (a & 31)));
+                atomicAnd(adj + (size_t)a * KW + (bq >> 5), ~(1u << (bq & 31)));
+            }
+        }
+        if (tid == 0) s_cnt[1] = 0;
+        __threadfence();
+        __syncthreads();
+        alive -= P;
+        base += P;
+    }
+}
+
+__global__ __launch_bounds__(RT_T) void rt_cut_kernel(const int *labels, const int *merges, const int *alive_p, int H, int W, int K,
+                                                      int R, int *out) {
+    __shared__ unsigned short s_parent[RT_K_MAX];
+    __shared__ short s_new[RT_K_MAX];
+    __shared__ unsigned s_used[RT_K_MAX / 32], s_root[RT_K_MAX / 32], s_pref[RT_K_MAX / 32];
+    const int tid = (int)threadIdx.x, b = (int)blockIdx.x, KW = (K + 31) >> 5;
+    const size_t hw = (size_t)H * W;
+    labels += (size_t)b * hw;
+    out += (size_t)b * hw;
+    merges += (size_t)b * (K - 1) * 2;
+    const int m = min(max(alive_p[b] - R, 0), K - 1);                      // rows to apply
+    for (int q = tid; q < K; q += RT_T) s_parent[q] = (unsigned short)q;
+    if (tid < RT_K_MAX / 32) s_used[tid] = s_root[tid] = 0u;
+    __syncthreads();
+    for (int t = tid; t < m; t += RT_T) {
+        const int a = merges[2 * t], c = merges[2 * t + 1];
+        if (a >= 0 && a < c && c < K) s_parent[c] = (unsigned short)a;    // every c dies once; (-1, -1) rows are skipped
+    }
+    __syncthreads();
+    for (int it = 0; it < 12; ++it) {                                      // parent < child: chains of at most 4096 = 2^12 links
+        unsigned short pp[RT_K_MAX / RT_T];
+#pragma unroll
+        for (int j = 0; j < RT_K_MAX / RT_T; ++j) {
+            const int q = tid + j * RT_T;
+            pp[j] = q < K ? s_parent[s_parent[q]] : 0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < RT_K_MAX / RT_T; ++j) {
+            const int q = tid + j * RT_T;
+            if (q < K) s_parent[q] = pp[j];
+        }
+        __syncthreads();
+    }
+    for (size_t p = tid; p < hw; p += RT_T) {
+        const int l = labels[p];
+        if ((unsigned)l < (unsigned)K && !(s_used[l >> 5] & (1u << (l & 31)))) atomicOr(&s_used[l >> 5], 1u << (l & 31));
+    }
+    __syncthreads();
+    for (int q = tid; q < K; q += RT_T)
+        if (s_used[q >> 5] & (1u << (q & 31))) {
+            const int r = s_parent[q];
+            atomicOr(&s_root[r >> 5], 1u << (r & 31));
+        }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned acc = 0;
+        for (int w = 0; w < KW; ++w) {
+            s_pref[w] = acc;
+            acc += (unsigned)__popc(s_root[w]);
+        }
+    }
+    __syncthreads();
+    for (int q = tid; q < K; q += RT_T) {                                  // groups numbered in increasing order of their rep
+        const int r = s_parent[q];
+        const bool used = s_used[q >> 5] & (1u << (q & 31));
+        s_new[q] = used ? (short)(s_pref[r >> 5] + (unsigned)__popc(s_root[r >> 5] & ((1u << (r & 31)) - 1u))) : (short)-1;
+    }
+    __syncthreads();
+    for (size_t p = tid; p < hw; p += RT_T) {                              // (out may be labels: a pixel is read, then written, by one thread)
+        const int l = labels[p];
+        out[p] = (unsigned)l < (unsigned)K ? (int)s_new[l] : -1;
+    }
+}
+
+bool rt_shape_ok(int B, int H, int W, int K) {
+    return B >= 1 && B <= 65535 && H >= 1 && W >= 1 && H <= RT_HW_MAX && W <= RT_HW_MAX && K >= 1 && K <= RT_K_MAX;
+}
+
+}  // namespace
+
+extern "C" size_t gcs_region_tree_workspace_bytes(int B, int H, int W, int D, int K) {
+    if (!rt_shape_ok(B, H, W, K) || D < 1 || D > RT_D_MAX) return 0;
+    const size_t k = (size_t)K, kw = (k + 31) / 32;
+    return (size_t)B * (rt_align(k * (D + 1) * 8) + rt_align(k * kw * 4) + rt_align(k * D * 2));
+}
+
+extern "C" int gcs_region_tree(const uint16_t *feats, const int32_t *labels, int B, int H, int W, int D, int K, void *workspace,
+                               int32_t *merges_out, uint64_t *costs_out, int32_t *alive_out, gcs_stream_t stream) {
+    if (!feats || !labels || !workspace || !alive_out || (K > 1 && !merges_out))
+        return gcs_fail(GCS_EINVAL, "gcs_region_tree: NULL pointer");
+    if (!rt_shape_ok(B, H, W, K) || D < 1 || D > RT_D_MAX)
+        return gcs_fail(GCS_EINVAL, "gcs_region_tree: bad shape (1 <= B <= 65535, 1 <= H, W <= 4096, 1 <= D <= 207, 1 <= K <= 4096)");
+    RtArgs A{};
+    A.feats = feats, A.labels = labels;
+    A.B = B, A.H = H, A.W = W, A.D = D, A.K = K, A.KW = (K + 31) / 32;
+    const size_t k = (size_t)K;
+    const size_t sums_b = rt_align(k * (D + 1) * 8), adj_b = rt_align(k * A.KW * 4);
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    A.sums = reinterpret_cast<u64 *>(ws);                                  // image b's rows: [b][K][D + 1] (dense; the padding sits behind all)
+    A.adj = reinterpret_cast<unsigned *>(ws + (size_t)B * sums_b);
+    A.mean = reinterpret_cast<uint16_t *>(ws + (size_t)B * (sums_b + adj_b));
+    A.merges = merges_out, A.costs = reinterpret_cast<u64 *>(costs_out), A.alive = alive_out;
+    const size_t n16 = (size_t)B * (sums_b + adj_b) / 16;
+    const int zgrid = (int)std::min<size_t>((n16 + 255) / 256, (size_t)gcs_cu_count() * 8);
+    hipLaunchKernelGGL(rt_zero_kernel, dim3(zgrid), dim3(256), 0, stream, reinterpret_cast<uint4 *>(ws), n16);
+    GCS_CHECK_LAUNCH("gcs_region_tree (zero)");
+    const dim3 tiles((W + RT_TW - 1) / RT_TW, (H + RT_TH - 1) / RT_TH, B);
+    hipLaunchKernelGGL(rt_stats_kernel, tiles, dim3(256), (size_t)RT_SLOTS * (D + 1) * 4 + RT_SLOTS * 4 + 16, stream, A);
+    GCS_CHECK_LAUNCH("gcs_region_tree (statistics)");
+    const size_t state = rt_state_bytes(K), with_mean = state + k * D * 2;
+    const int mean_in_lds = with_mean <= RT_LDS_MAX ? 1 : 0;
+    hipLaunchKernelGGL(rt_merge_kernel, dim3(B), dim3(RT_T), mean_in_lds ? with_mean : state, stream, A, mean_in_lds);
+    GCS_CHECK_LAUNCH("gcs_region_tree (merge)");
+    return GCS_OK;
+}
+
+extern "C" int gcs_region_tree_cut(const int32_t *labels, const int32_t *merges, const int32_t *alive, int B, int H, int W, int K,
+                                   int R, int32_t *labels_out, gcs_stream_t stream) {
+    if (!labels || !alive || !labels_out || (K > 1 && !merges)) return gcs_fail(GCS_EINVAL, "gcs_region_tree_cut: NULL pointer");
+    if (!rt_shape_ok(B, H, W, K)) return gcs_fail(GCS_EINVAL, "gcs_region_tree_cut: bad shape (1 <= B <= 65535, 1 <= H, W <= 4096, 1 <= K <= 4096)");
+    if (R < 1) return gcs_fail(GCS_EINVAL, "gcs_region_tree_cut: R must be >= 1");
+    hipLaunchKernelGGL(rt_cut_kernel, dim3(B), dim3(RT_T), 0, stream, labels, merges, alive, H, W, K, R, labels_out);
+    GCS_CHECK_LAUNCH("gcs_region_tree_cut");
+    return GCS_OK;
+}

@@ -12,6 +12,7 @@ PyTorch is plumbing only: device memory, the current HIP stream and torch.distri
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 
@@ -405,6 +406,51 @@ class HipOps:
                                                    None if centres is None else centres.data_ptr(), self._stream()),
                    "gcs_superpixel_segment")
 
+    def region_tree_buffers(self, b, h, w, K):
+        """What SPEC.md §14 needs for one (batch, shape, K): ``(workspace, merges (B, K-1, 2) int32, costs (B, K-1) int64, alive (B,)
+        int32)`` (a captured graph must own them). The costs are unsigned 64-bit values below 2^62: an int64 tensor holds the bits."""
+        torch, K = self.torch, int(K)
+        need = self.lib.gcs_region_tree_workspace_bytes(b, h, w, self.bank.n_features, K)
+        if need == 0:
+            raise ValueError("no region tree for this shape / bank (H, W <= 4096, D <= 207, 1 <= K <= 4096)")
+        return (self.empty_bytes(need), torch.empty((b, K - 1, 2), dtype=torch.int32, device=self.device),
+                torch.empty((b, K - 1), dtype=torch.int64, device=self.device), torch.empty((b,), dtype=torch.int32, device=self.device))
+
+    @_on_device
+    def region_tree(self, canon, labels, b, h, w, K, workspace, merges, costs, alive):
+        """SPEC.md §14 on canonical features and an int32 (B,H,W) label map in 0 .. K-1: fills ``merges`` (B, K-1, 2) int32, ``costs``
+        (None or (B, K-1) int64) and ``alive`` (B,) int32. ``workspace``: from ``region_tree_buffers``. Three launches, capturable."""
+        torch, d, K = self.torch, self.bank.n_features, int(K)
+        if canon.dtype != torch.int16 or tuple(canon.shape) != (b, d, h, w) or not canon.is_contiguous():
+            raise ValueError("canon must be the contiguous (B,D,H,W) int16 tensor of features_unpack")
+        if labels.dtype != torch.int32 or tuple(labels.shape) != (b, h, w) or not labels.is_contiguous():
+            raise ValueError("labels must be a contiguous (B,H,W) int32 tensor")
+        if merges.dtype != torch.int32 or tuple(merges.shape) != (b, K - 1, 2) or not merges.is_contiguous():
+            raise ValueError("merges must be a contiguous (B, K - 1, 2) int32 tensor")
+        if costs is not None and (costs.dtype != torch.int64 or tuple(costs.shape) != (b, K - 1) or not costs.is_contiguous()):
+            raise ValueError("costs must be a contiguous (B, K - 1) int64 tensor")
+        if alive.dtype != torch.int32 or tuple(alive.shape) != (b,) or not alive.is_contiguous():
+            raise ValueError("alive must be a contiguous (B,) int32 tensor")
+        _lib.check(self.lib.gcs_region_tree(canon.data_ptr(), labels.data_ptr(), b, h, w, d, K, workspace.data_ptr(),
+                                            merges.data_ptr() if K > 1 else None,
+                                            None if costs is None or K == 1 else costs.data_ptr(), alive.data_ptr(), self._stream()),
+                   "gcs_region_tree")
+
+    @_on_device
+    def region_tree_cut(self, labels, merges, alive, b, h, w, K, R, out):
+        """The cut of SPEC.md §14 at ``R``: ``out`` (B,H,W) int32 (it may be ``labels``) gets min(alive, R) labels per image. One
+        launch, capturable."""
+        torch, K = self.torch, int(K)
+        for name, t in (("labels", labels), ("out", out)):
+            if t.dtype != torch.int32 or tuple(t.shape) != (b, h, w) or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous (B,H,W) int32 tensor")
+        if merges.dtype != torch.int32 or tuple(merges.shape) != (b, K - 1, 2) or not merges.is_contiguous():
+            raise ValueError("merges must be a contiguous (B, K - 1, 2) int32 tensor")
+        if alive.dtype != torch.int32 or tuple(alive.shape) != (b,) or not alive.is_contiguous():
+            raise ValueError("alive must be a contiguous (B,) int32 tensor")
+        _lib.check(self.lib.gcs_region_tree_cut(labels.data_ptr(), merges.data_ptr() if K > 1 else None, alive.data_ptr(), b, h, w, K,
+                                                int(R), out.data_ptr(), self._stream()), "gcs_region_tree_cut")
+
     def download(self, dst_pinned, src):
         """Device tensor -> pinned host tensor of the same bytes on the current stream, by SDMA (gcs_download)."""
         self._check_dev(src)
@@ -537,6 +583,23 @@ def _check_superpixels(n_superpixels, spatial_weight):
     return tuple(vals)
 
 
+REGIONS_MAX = 4096            # SPEC.md §14: the option's range (a cut cannot have more labels than the superpixel grid has centres)
+
+
+def _check_regions(n_regions, n_superpixels):
+    """SPEC.md §14 parameter: R the integer 0 (off) or 1..4096, and only on top of the superpixel stage."""
+    try:
+        r = int(n_regions)
+        good = r == n_regions and not isinstance(n_regions, bool) and 0 <= r <= REGIONS_MAX
+    except (TypeError, ValueError, OverflowError):
+        good = False
+    if not good:
+        raise ValueError(f"n_regions must be the integer 0 (off) or 1..{REGIONS_MAX}, got {n_regions!r}")
+    if r > 0 and n_superpixels == 0:
+        raise ValueError("n_regions > 0 merges superpixels: it needs n_superpixels > 0")
+    return r
+
+
 def lloyd(ops, feats, b, h, w, k, n_iter, mode, labels, partials, cent, sums, dist_group=None,
           rows=None, init=None, raster=None, debug=_ENV_DEBUG, fold=None):
     """SPEC.md §4 schedule on one feature slab. ``mode``: 'per_image' or 'global'.
@@ -628,12 +691,16 @@ class Segmenter:
     def __init__(self, n_scales=4, n_orient=6, k=8, n_iter=10, ksize=13, f_max=0.4,
                  ratio=math.sqrt(2.0), bandwidth=1.0, connectivity=False, device="cuda:0", ops=None,
                  slab_candidates=1, min_region_size=0, smoothing=0.0, color_weight=0.0, chroma_gain=0,
-                 position_weight=0, n_superpixels=0, spatial_weight=576):
+                 position_weight=0, n_superpixels=0, spatial_weight=576, n_regions=0):
         """``n_superpixels = n`` (SPEC.md §13; 0 = off, 2..4096): grid-local k-means instead of the Lloyd stage - about n compact
         superpixels per image (K = ny * nx of ``superpixel_grid``) on the same features; ``k`` and ``mode`` are then unused (centres
         are per image). ``spatial_weight`` = lambda (1..65535, default 576) weighs the squared pixel distance to a centre against
         the squared feature distance: larger = more compact. Recommended pairing: ``min_region_size = S * S // 4`` with S of
-        ``superpixel_grid(H, W, n)``, which turns the label map into connected regions and merges the fragments."""
+        ``superpixel_grid(H, W, n)``, which turns the label map into connected regions and merges the fragments.
+
+        ``n_regions = R`` (SPEC.md §14; 0 = off, 1..4096; needs ``n_superpixels > 0``): the superpixels are merged on their adjacency
+        graph, cheapest mutual pair first, until min(R, superpixels in use) regions are left; ``connectivity`` and
+        ``min_region_size`` then apply to that map. ``region_tree_device`` / ``cut_regions_device`` give the tree itself and any cut."""
         if not (1 <= k <= _lib.K_MAX):
             raise ValueError(f"k must be in 1..{_lib.K_MAX}")
         if n_iter < 1:
@@ -655,6 +722,9 @@ class Segmenter:
         self.ops = ops if ops is not None else HipOps(self.bank, device, self.smoothing, self.chroma_gain)
         if self.n_superpixels > 0 and not hasattr(self.ops, "superpixels"):
             raise ValueError("Segmenter(n_superpixels=n, ops=...) needs ops that have the superpixel stage")
+        self.n_regions = _check_regions(n_regions, self.n_superpixels)          # SPEC.md §14 (0: the superpixel map as it is)
+        if self.n_regions > 0 and not all(hasattr(self.ops, m) for m in ("region_tree_buffers", "region_tree", "region_tree_cut")):
+            raise ValueError("Segmenter(n_regions=R, ops=...) needs ops that have the region tree")
         if self.smoothing > 0 and getattr(self.ops, "smoothing", 0.0) != self.smoothing:
             raise ValueError("Segmenter(smoothing=K, ops=...) needs ops built with the same smoothing")
         if getattr(self.ops, "chroma_gain", 0) != self.chroma_gain:
@@ -801,6 +871,8 @@ class Segmenter:
                 self._features(imgs[g0:g0 + n], ws, n, h, w)
                 if self.n_superpixels > 0:                       # SPEC.md §13 instead of §4: features -> canonical tensor -> stage
                     self._superpixel_stage(ws, n, h, w, out[g0:g0 + n])
+                    if self.n_regions > 0:                       # SPEC.md §14 on the raw §13 map, in place
+                        self._region_stage(ws, n, h, w, out[g0:g0 + n])
                     continue
                 direct = hasattr(self.ops, "assign_raster")      # the last pass writes the raster map itself
                 lloyd(self.ops, ws["feats"], n, h, w, self.k, self.n_iter, mode, ws["labels"], ws["partials"],
@@ -830,8 +902,9 @@ class Segmenter:
         if ny * nx > SUPERPIXELS_MAX:
             raise ValueError(f"n_superpixels = {self.n_superpixels} on {h} x {w} pixels gives a grid of {ny} x {nx} centres, "
                              f"more than {SUPERPIXELS_MAX}")
-        if out_dtype is not None and np.dtype(out_dtype) == np.uint8 and ny * nx > 256:
-            raise ValueError(f"out_dtype uint8 cannot hold the {ny * nx} labels of this superpixel grid")
+        n_labels = min(ny * nx, self.n_regions) if self.n_regions > 0 else ny * nx      # SPEC.md §14: a cut has min(alive, R) labels
+        if out_dtype is not None and np.dtype(out_dtype) == np.uint8 and n_labels > 256:
+            raise ValueError(f"out_dtype uint8 cannot hold the {n_labels} labels of this superpixel grid")
         return ny, nx
 
     def _superpixel_stage(self, ws, b, h, w, out, centres=None):
@@ -843,6 +916,54 @@ class Segmenter:
         canon, spws = ws["sp"]
         self.ops.features_unpack(ws["feats"], b, h, w, out=canon)
         self.ops.superpixels(canon, b, h, w, ny, nx, self.spatial_weight, self.n_iter, out, spws, centres)
+
+    def _region_stage(self, ws, b, h, w, out, cut=True):
+        """SPEC.md §14 behind ``_superpixel_stage``: the tree of the §13 map ``out`` on the canonical tensor that stage left in
+        ``ws["sp"]``, then (``cut``) the cut at ``n_regions`` in place. The buffers join the workspace at first use. Returns them."""
+        _, ny, nx = superpixel_grid(h, w, self.n_superpixels)
+        if "rt" not in ws:
+            ws["rt"] = self.ops.region_tree_buffers(b, h, w, ny * nx)
+        rtws, merges, costs, alive = ws["rt"]
+        self.ops.region_tree(ws["sp"][0], out, b, h, w, ny * nx, rtws, merges, costs, alive)
+        if cut:
+            self.ops.region_tree_cut(out, merges, alive, b, h, w, ny * nx, self.n_regions, out)
+        return merges, costs, alive
+
+    def region_tree_device(self, imgs):
+        """(B,H,W,3) uint8 device tensor -> (labels (B,H,W) int32: the §13 map; merges (B, K-1, 2) int32; costs (B, K-1) int64: the
+        unsigned 64-bit costs, all below 2^62; alive (B,) int32) of SPEC.md §14, K = ny * nx: no cut, no post-passes. Any
+        ``n_regions`` of the plan is ignored; ``cut_regions_device`` cuts the tree at any R for the cost of a relabel."""
+        torch = _torch()
+        if self.n_superpixels == 0:
+            raise ValueError("region_tree_device needs Segmenter(n_superpixels=n) with n > 0")
+        if not hasattr(self.ops, "region_tree"):
+            raise ValueError("region_tree_device needs ops that have the region tree")
+        imgs = imgs.contiguous()
+        b, h, w, _ = imgs.shape
+        if h < 8 or w < 8:
+            raise ValueError("images must be at least 8x8")
+        check_position_range(self.position_weight, h, w)
+        self._superpixel_check(h, w)
+        with (torch.cuda.device(self.ops.device) if self.native else contextlib.nullcontext()):
+            ws = self._tail_workspace(b, h, w, "per_image")
+            self._features(imgs, ws, b, h, w)
+            out = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
+            self._superpixel_stage(ws, b, h, w, out)
+            merges, costs, alive = self._region_stage(ws, b, h, w, out, cut=False)
+        return out, merges, costs, alive
+
+    def cut_regions_device(self, labels, merges, alive, R):
+        """The cut of SPEC.md §14 at ``R`` (1..4096) of a tree ``region_tree_device`` returned: a fresh (B,H,W) int32 label map with
+        min(alive, R) labels per image, numbered in increasing order of each group's smallest superpixel index."""
+        torch = _torch()
+        R = _check_regions(R, 1)
+        if R == 0:
+            raise ValueError("R must be in 1..4096")
+        b, h, w = labels.shape
+        out = torch.empty_like(labels)
+        with (torch.cuda.device(self.ops.device) if self.native else contextlib.nullcontext()):
+            self.ops.region_tree_cut(labels, merges, alive, b, h, w, merges.shape[1] + 1, R, out)
+        return out
 
     def superpixels_device(self, imgs):
         """(B,H,W,3) uint8 device tensor -> (labels (B,H,W) int32, centres (B, ny * nx, D + 2) int32: the D features, cy, cx the
@@ -1170,6 +1291,10 @@ class Segmenter:
                 if self.n_superpixels > 0:
                     sp = self.ops.superpixel_buffers(b, h, w, self.n_superpixels) + superpixel_grid(h, w, self.n_superpixels)[1:] \
                         + (self.spatial_weight, dev_out if out_dtype != np.uint8 else torch.empty((b, h, w), dtype=torch.int32, device=dev))
+                # SPEC.md §14: the tree's workspace and outputs, and R (None: the stage is off)
+                rt = None
+                if self.n_regions > 0:
+                    rt = self.ops.region_tree_buffers(b, h, w, sp[2] * sp[3]) + (self.n_regions,)
                 pin_in = torch.empty((b, h, w, 3), dtype=torch.uint8, pin_memory=True)
                 # the graph bakes raw pointers in: every buffer it touches, the Gabor scratch included, belongs to the
                 # entry and lives exactly as long as the graph does (the shared scratch of HipOps is replaced, and its
@@ -1196,8 +1321,12 @@ class Segmenter:
                         canon, spws, ny, nx, lam, out32 = sp
                         ops.features_unpack(ws["feats"], b, h, w, out=canon)
                         ops.superpixels(canon, b, h, w, ny, nx, lam, n_iter, out32, spws)
+                        if rt is not None:
+                            rtws, merges, costs, alive, n_regions = rt
+                            ops.region_tree(canon, out32, b, h, w, ny * nx, rtws, merges, costs, alive)
+                            ops.region_tree_cut(out32, merges, alive, b, h, w, ny * nx, n_regions, out32)
                         if out32 is not dev_out:
-                            dev_out.copy_(out32)           # (K <= 256 was checked: the narrowing keeps every label)
+                            dev_out.copy_(out32)           # (K, or min(K, R), <= 256 was checked: the narrowing keeps every label)
                         return
                     lloyd(ops, ws["feats"], b, h, w, k, n_iter, mode, ws["labels"], ws["partials"], ws["cent"],
                           ws["sums"], raster=dev_out, debug=debug, fold=ws.get("fold"))
@@ -1214,7 +1343,7 @@ class Segmenter:
                     _CAPTURES.fell_back(key, "torch.cuda.graph raised RuntimeError")
                     graph = None
                     torch.cuda.current_stream(dev).synchronize()
-                ent = dict(graph=graph, step=step, ws=ws, dev_in=dev_in, dev_out=dev_out, pin_in=pin_in, scratch=scratch, sp=sp)
+                ent = dict(graph=graph, step=step, ws=ws, dev_in=dev_in, dev_out=dev_out, pin_in=pin_in, scratch=scratch, sp=sp, rt=rt)
                 if len(self._graphs) >= 4:                 # evicted plans leave through the guard: never inside an open capture
                     _CAPTURES.retire([self._graphs.pop(next(iter(self._graphs)))])
                 self._graphs[key] = ent

@@ -382,6 +382,34 @@ size_t gcs_superpixel_workspace_bytes(int B, int H, int W, int D, int n);
 int gcs_superpixel_segment(const uint16_t *feats_canonical_dev, int B, int H, int W, int D, int ny, int nx, int lambda, int n_iter,
                            void *workspace_dev, int32_t *labels_out_dev, int32_t *centres_out_dev, gcs_stream_t stream);
 
+/* ---- region tree: merging a label map's regions on their adjacency graph (SPEC.md §14) ------------ */
+
+/* Nodes = the labels 0 .. K-1 of labels_dev that own a pixel (`alive` of them); per node the pixel count n, the exact feature sums and
+ * the mean m_d = floor((2 S_d + n) / (2 n)); two nodes are adjacent when a pixel of one is a 4-neighbour of a pixel of the other;
+ * cost(A, B) = sum_d (m_A,d - m_B,d)^2 * min(n_A, n_B) in unsigned 64 bits (< 2^62). Per round every node picks the adjacent node of
+ * least (cost, rep), rep = the smallest label of a group; mutual picks merge; a round's merges are listed in (cost, smaller rep) order.
+ *   gcs_region_tree_workspace_bytes  host only: bytes of workspace_dev: per image the [K][D + 1] uint64 sums, the K x K adjacency bit
+ *                                    matrix and the [K][D] uint16 means. 0 for a bad argument. Contents are undefined before and after a
+ *                                    call (the call zeroes what it accumulates into).
+ *   gcs_region_tree                  enqueues three launches on `stream` (zero, statistics + adjacency in one read of feats and labels,
+ *                                    every merge round inside one kernel, a workgroup per image). No allocation, no host synchronisation
+ *                                    (capturable). merges_out_dev int32 [B][K - 1][2]: row t = the reps (a < b) of the two groups merged at
+ *                                    step t; costs_out_dev: NULL, or uint64 [B][K - 1]; alive_out_dev int32 [B]. Rows that no merge filled
+ *                                    (rows >= alive - 1) are (-1, -1) with cost 0. The tree does not depend on any R.
+ *   gcs_region_tree_cut              one launch: the first max(0, alive - R) rows applied, the groups numbered 0, 1, ... in increasing order
+ *                                    of their rep: labels_out_dev int32 [B][H][W] has min(alive, R) labels per image. labels_out_dev may
+ *                                    BE labels_dev (in place); it must not overlap it otherwise.
+ * A pixel whose label is outside 0 .. K-1 is counted nowhere, is adjacent to nothing and leaves the cut as -1. feats_canonical_dev is
+ * the [B][D][H][W] uint16 tensor of gcs_features_unpack. With K = 1 there are no rows: merges / costs pointers are not read.
+ * GCS_EINVAL, with nothing launched: a NULL feats / labels / workspace / alive / labels_out pointer, a NULL merges pointer with K > 1,
+ * B outside 1..65535, H or W outside 1..4096, D outside 1..207, K outside 1..4096, R < 1.
+ * Added within ABI 18: new entry points change no existing call, so GCS_ABI_VERSION did not move. */
+size_t gcs_region_tree_workspace_bytes(int B, int H, int W, int D, int K);
+int gcs_region_tree(const uint16_t *feats_canonical_dev, const int32_t *labels_dev, int B, int H, int W, int D, int K,
+                    void *workspace_dev, int32_t *merges_out_dev, uint64_t *costs_out_dev, int32_t *alive_out_dev, gcs_stream_t stream);
+int gcs_region_tree_cut(const int32_t *labels_dev, const int32_t *merges_dev, const int32_t *alive_dev, int B, int H, int W, int K,
+                        int R, int32_t *labels_out_dev, gcs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
