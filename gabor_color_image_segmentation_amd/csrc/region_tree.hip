@@ -385,6 +385,178 @@ __global__ __launch_bounds__(RT_T) void rt_cut_kernel(const int *labels, const i
     }
 }
 
+// ---- contour map (SPEC.md §15): the level at which every boundary pixel of the label map disappears from the tree
+//   rt_contour_prepare_kernel  ONE workgroup per image turns the merge list into a leaf order in which every group of every step is a
+//                       contiguous run: a list per rep (head = the rep, a tail table), row t appends b's list to a's and writes the gap
+//                       value t + 1 at the seam (one thread: K - 1 dependent LDS steps); the roots that are left are chained in
+//                       increasing order with the gap "never" (RT_NEVER, above every level). Positions by list ranking (pointer
+//                       jumping, ceil(log2 K) rounds), then a range-maximum table over the K - 1 gaps, ceil(log2 K) levels of K
+//                       uint16 entries: join(p, q) = the maximum gap between pos[p] and pos[q] = two table entries. A row that is
+//                       not (a < b, both still reps) is skipped, so any list gives a forest and every position lies in 0 .. K-1.
+//   rt_contour_kernel   RT_CP consecutive pixels of an image per workgroup: a pixel that agrees with its four neighbours stores 0; the
+//                       others read two positions and two table entries per differing neighbour. pos and the table sit in LDS
+//                       where one copy per workgroup costs less than the pixels it serves (RT_CLDS_MAX), else they are read in L2.
+constexpr unsigned RT_NEVER = 0xffffu;       // gap between two roots: no row joins them (levels are below 4096)
+constexpr int RT_CP = 4096;                  // pixels per workgroup of the pixel kernel
+constexpr size_t RT_CLDS_MAX = 16384;        // pos + table bytes a pixel workgroup copies to LDS (4 bytes per pixel it serves)
+
+__host__ __device__ inline int rt_levels(int K) { return K > 1 ? 32 - __builtin_clz((unsigned)(K - 1)) : 0; }   // ceil(log2 K)
+__host__ __device__ inline size_t rt_contour_bytes(int K) { return rt_align((size_t)2 * K * (1 + rt_levels(K))); }
+
+__global__ __launch_bounds__(RT_T) void rt_contour_prepare_kernel(const int *merges, int K, unsigned char *ws) {
+    __shared__ unsigned short s_tail[RT_K_MAX], s_next[RT_K_MAX], s_gap[RT_K_MAX], s_dist[RT_K_MAX];
+    __shared__ unsigned short s_a[RT_K_MAX], s_b[RT_K_MAX];
+    __shared__ unsigned s_dead[RT_K_MAX / 32];
+    const int tid = (int)threadIdx.x, b = (int)blockIdx.x, LV = rt_levels(K);
+    unsigned short *pos = reinterpret_cast<unsigned short *>(ws + (size_t)b * rt_contour_bytes(K)), *table = pos + K;
+    for (int q = tid; q < K; q += RT_T) {
+        s_tail[q] = s_next[q] = (unsigned short)q;
+        s_gap[q] = 0;
+    }
+    if (tid < RT_K_MAX / 32) s_dead[tid] = 0u;
+    if (K > 1) {
+        const int *rows = merges + (size_t)b * (K - 1) * 2;
+        for (int t = tid; t < K - 1; t += RT_T) {
+            const int a = rows[2 * t], c = rows[2 * t + 1];
+            const bool ok = a >= 0 && a < c && c < K;
+            s_a[t] = ok ? (unsigned short)a : (unsigned short)RT_NEVER;
+            s_b[t] = ok ? (unsigned short)c : (unsigned short)RT_NEVER;
+        }
+    }
+    __syncthreads();
+    if (tid == 0 && K > 1) {                                               // the concatenation: serial, its steps depend on each other
+        // One LDS round trip per row: the row after this one is fetched before this one's stores, and a dead rep is one whose tail
+        // entry says RT_NEVER (its list has gone to its absorber: the entry is never needed again), so the two tails are all a row reads.
+        unsigned a = s_a[0], c = s_b[0];
+        for (int t = 0; t < K - 1; ++t) {
+            const unsigned an = t + 1 < K - 1 ? s_a[t + 1] : RT_NEVER, cn = t + 1 < K - 1 ? s_b[t + 1] : RT_NEVER;
+            if (a != RT_NEVER) {
+                const unsigned ta = s_tail[a], tc = s_tail[c];
+                if (ta != RT_NEVER && tc != RT_NEVER) {                    // both still reps; a row that is not is skipped
+                    s_next[ta] = (unsigned short)c;
+                    s_gap[ta] = (unsigned short)(t + 1);
+                    s_tail[a] = (unsigned short)tc;
+                    s_tail[c] = (unsigned short)RT_NEVER;
+                }
+            }
+            a = an;
+            c = cn;
+        }
+    }
+    __syncthreads();
+    for (int q = tid; q < K; q += RT_T)
+        if (s_tail[q] == RT_NEVER) atomicOr(&s_dead[q >> 5], 1u << (q & 31));
+    __syncthreads();
+    const int KW = (K + 31) >> 5;
+    for (int q = tid; q < K; q += RT_T) {                                  // a root's list goes in front of the next root's
+        if ((s_dead[q >> 5] >> (q & 31)) & 1u) continue;
+        int nxt = -1;
+        for (int w = q >> 5; w < KW && nxt < 0; ++w) {
+            unsigned live = ~s_dead[w];
+            if (w == (q >> 5)) live &= (q & 31) == 31 ? 0u : ~0u << ((q & 31) + 1);
+            if (live) nxt = 32 * w + __ffs((int)live) - 1;
+        }
+        if (nxt >= 0 && nxt < K) {
+            const unsigned tq = s_tail[q];
+            s_next[tq] = (unsigned short)nxt;
+            s_gap[tq] = (unsigned short)RT_NEVER;
+        }
+    }
+    __syncthreads();
+    for (int q = tid; q < K; q += RT_T) s_dist[q] = s_next[q] != q ? 1 : 0;
+    __syncthreads();
+    for (int it = 0; it < LV; ++it) {                                      // one list of K elements: at most K - 1 <= 2^LV links
+        unsigned short nn[RT_K_MAX / RT_T], dd[RT_K_MAX / RT_T];
+#pragma unroll
+        for (int j = 0; j < RT_K_MAX / RT_T; ++j) {
+            const int q = tid + j * RT_T;
+            if (q < K) {
+                const unsigned n = s_next[q];
+                nn[j] = s_next[n];
+                dd[j] = (unsigned short)(s_dist[q] + s_dist[n]);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < RT_K_MAX / RT_T; ++j) {
+            const int q = tid + j * RT_T;
+            if (q < K) {
+                s_next[q] = nn[j];
+                s_dist[q] = dd[j];
+            }
+        }
+        __syncthreads();
+    }
+    // positions; the gaps in position order = level 0 of the table (entry K - 1, behind the last element, is 0)
+    unsigned short *lv_a = s_tail, *lv_b = s_next;
+    for (int q = tid; q < K; q += RT_T) lv_a[q] = 0;
+    __syncthreads();
+    for (int q = tid; q < K; q += RT_T) {
+        const int d = min((int)s_dist[q], K - 1), p = K - 1 - d;
+        pos[q] = (unsigned short)p;
+        if (p < K - 1) lv_a[p] = s_gap[q];
+    }
+    __syncthreads();
+    for (int j = 0; j < LV; ++j) {                                         // level j entry i = max of the gaps i .. i + 2^j - 1
+        for (int i = tid; i < K; i += RT_T) table[(size_t)j * K + i] = lv_a[i];
+        const int half = 1 << j;
+        for (int i = tid; i < K; i += RT_T) lv_b[i] = max(lv_a[i], i + half < K ? lv_a[i + half] : (unsigned short)0);
+        __syncthreads();
+        unsigned short *t = lv_a;
+        lv_a = lv_b;
+        lv_b = t;
+    }
+}
+
+// s(p, q) of SPEC.md §15 for two labels already known to differ; q < 0: out of range
+__device__ __forceinline__ int rt_strength(const unsigned short *pos, const unsigned short *table, int K, int alive, int p, int q) {
+    if (p < 0 || q < 0) return alive;
+    int l = pos[p], r = pos[q];
+    if (l > r) {
+        const int t = l;
+        l = r;
+        r = t;
+    }
+    if (l == r) return alive;                                              // (only a list that is no forest order: never read past)
+    const int j = 31 - __builtin_clz((unsigned)(r - l));
+    const unsigned v = max((unsigned)table[(size_t)j * K + l], (unsigned)table[(size_t)j * K + r - (1 << j)]);
+    return v == RT_NEVER ? alive : (int)v;
+}
+
+__global__ __launch_bounds__(256) void rt_contour_kernel(const int *labels, const int *alive_p, int H, int W, int K,
+                                                         const unsigned char *ws, int in_lds, int *out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned short rt_ctab[];
+    const int tid = (int)threadIdx.x, b = (int)blockIdx.y;
+    const size_t hw = (size_t)H * W;
+    const unsigned short *pos = reinterpret_cast<const unsigned short *>(ws + (size_t)b * rt_contour_bytes(K));
+    if (in_lds) {
+        const int n = K * (1 + rt_levels(K));
+        for (int i = tid; i < n; i += 256) rt_ctab[i] = pos[i];
+        __syncthreads();
+        pos = rt_ctab;
+    }
+    const unsigned short *table = pos + K;
+    const int alive = alive_p[b];
+    labels += (size_t)b * hw;
+    out += (size_t)b * hw;
+    const size_t p0 = (size_t)blockIdx.x * RT_CP, p1 = p0 + RT_CP < hw ? p0 + RT_CP : hw;
+    for (size_t p = p0 + tid; p < p1; p += 256) {
+        const int y = (int)(p / (size_t)W), x = (int)(p - (size_t)y * W);
+        int c = labels[p];
+        if ((unsigned)c >= (unsigned)K) c = -1;                            // every label outside 0 .. K-1 is the one label -1
+        int u = 0;
+        const int nb[4] = {x > 0 ? labels[p - 1] : c, x + 1 < W ? labels[p + 1] : c, y > 0 ? labels[p - W] : c,
+                           y + 1 < H ? labels[p + W] : c};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            int q = nb[k];
+            if ((unsigned)q >= (unsigned)K) q = -1;
+            if (q != c) u = max(u, rt_strength(pos, table, K, alive, c, q));
+        }
+        out[p] = u;
+    }
+}
+
 bool rt_shape_ok(int B, int H, int W, int K) {
     return B >= 1 && B <= 65535 && H >= 1 && W >= 1 && H <= RT_HW_MAX && W <= RT_HW_MAX && K >= 1 && K <= RT_K_MAX;
 }
@@ -434,5 +606,32 @@ extern "C" int gcs_region_tree_cut(const int32_t *labels, const int32_t *merges,
     if (R < 1) return gcs_fail(GCS_EINVAL, "gcs_region_tree_cut: R must be >= 1");
     hipLaunchKernelGGL(rt_cut_kernel, dim3(B), dim3(RT_T), 0, stream, labels, merges, alive, H, W, K, R, labels_out);
     GCS_CHECK_LAUNCH("gcs_region_tree_cut");
+    return GCS_OK;
+}
+
+extern "C" size_t gcs_region_tree_contours_workspace_bytes(int B, int K) {
+    if (B < 1 || B > 65535 || K < 1 || K > RT_K_MAX) return 0;
+    return (size_t)B * rt_contour_bytes(K);
+}
+
+extern "C" int gcs_region_tree_contours(const int32_t *labels, const int32_t *merges, const int32_t *alive, int B, int H, int W, int K,
+                                        void *workspace, int32_t *contours_out, gcs_stream_t stream) {
+    if (!labels || !alive || !workspace || !contours_out || (K > 1 && !merges))
+        return gcs_fail(GCS_EINVAL, "gcs_region_tree_contours: NULL pointer");
+    if (!rt_shape_ok(B, H, W, K))
+        return gcs_fail(GCS_EINVAL, "gcs_region_tree_contours: bad shape (1 <= B <= 65535, 1 <= H, W <= 4096, 1 <= K <= 4096)");
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(labels), co = reinterpret_cast<uintptr_t>(contours_out);
+    const size_t map_bytes = (size_t)B * H * W * sizeof(int32_t);
+    if (lo < co + map_bytes && co < lo + map_bytes)
+        return gcs_fail(GCS_EINVAL, "gcs_region_tree_contours: contours_out overlaps labels (neighbours are read)");
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    hipLaunchKernelGGL(rt_contour_prepare_kernel, dim3(B), dim3(RT_T), 0, stream, merges, K, ws);
+    GCS_CHECK_LAUNCH("gcs_region_tree_contours (prepare)");
+    const size_t tab = (size_t)2 * K * (1 + rt_levels(K));
+    const int in_lds = tab <= RT_CLDS_MAX ? 1 : 0;
+    const size_t hw = (size_t)H * W;
+    hipLaunchKernelGGL(rt_contour_kernel, dim3((unsigned)((hw + RT_CP - 1) / RT_CP), B), dim3(256), in_lds ? tab : 0, stream, labels,
+                       alive, H, W, K, ws, in_lds, contours_out);
+    GCS_CHECK_LAUNCH("gcs_region_tree_contours (pixels)");
     return GCS_OK;
 }

@@ -1,6 +1,8 @@
 // scoring.hip — evaluation-side kernels of libgcs.so (gfx950): boundary recall / precision counts
 // (/root/reference/BSD_metrics/metrics.py:58-96), region tables (metrics.py:102-201) and connected regions (SPEC.md §7).
 // Nothing here allocates, frees or synchronises; every entry point enqueues on the caller's stream.
+#include <limits.h>
+
 #include "common.h"
 
 // ======================================================================= boundary scoring (§8f-1)
@@ -356,6 +358,116 @@ extern "C" int gcs_boundary_counts_resident(const int32_t *labels, const void *t
                        reinterpret_cast<const unsigned long long *>(truth_bd_counts), img_of, B, T, H, W,
                        reinterpret_cast<unsigned long long *>(counts));
     GCS_CHECK_LAUNCH("gcs_boundary_counts_resident");
+    return GCS_OK;
+}
+
+// ================================================= boundary counts of every cut of a region tree at once (SPEC.md §15)
+// A contour map U (gcs_region_tree_contours) holds, per pixel, the level at which its boundary disappears: the thick boundary of the
+// cut at R is U > tau, tau = max(0, alive - R), and its 5 x 5 dilation is M5(U) > tau, M5 = the maximum of U over the window clipped
+// to the image. So the three counts gcs_boundary_counts_resident returns for ONE cut are suffix sums of three histograms of U:
+//   hist [b][s]          = #{ U = s }                       rows 0 .. B-1
+//   hist [B + 2t][s]     = #{ bd(T_t)   : M5(U) = s }       (recall numerator)
+//   hist [B + 2t + 1][s] = #{ dil5(T_t) : U = s }           (precision numerator)        s = 1 .. K; bin 0 stays 0
+// One workgroup per 16 x 64 tile of one image: U with a two-pixel halo in LDS (outside the image: INT_MIN, it never wins a
+// maximum), the 5 x 5 maximum separably, then only pixels with U or M5 in 1 .. K touch the annotator bit planes and a histogram.
+// The annotators of image b are the run of t with img_of[t] = b (img_of is non-decreasing: PackedTruth.stack's order). The
+// (1 + 2 A_b)(K + 1) counters of the image sit in LDS when they fit the launch's SW_LDS_COUNTERS and leave with one vector atomic
+// per non-zero counter; otherwise every count is a global atomic (slow, exact). Integer counts: any order, the same bits.
+constexpr int SW_TH = 16, SW_TW = 64, SW_HALO = 2;
+constexpr int SW_LDS_COUNTERS = 8192;
+__global__ __launch_bounds__(256) void boundary_sweep_kernel(const int32_t *__restrict__ contours,
+                                                             const unsigned long long *__restrict__ tru,
+                                                             const int32_t *__restrict__ img_of, int B, int T, int H, int W, int K,
+                                                             int lds_counters, unsigned *__restrict__ hist) {
+    extern __shared__ unsigned sw_hist[];
+    __shared__ int s_u[SW_TH + 2 * SW_HALO][SW_TW + 2 * SW_HALO + 1];
+    __shared__ int s_hor[SW_TH + 2 * SW_HALO][SW_TW];
+    __shared__ int s_t[2];
+    const int tid = threadIdx.x, b = blockIdx.z, y0 = blockIdx.y * SW_TH, x0 = blockIdx.x * SW_TW;
+    const int32_t *u = contours + (size_t)b * H * W;
+    if (tid < 2) s_t[tid] = 0;
+    __syncthreads();
+    int below = 0, upto = 0;
+    for (int t = tid; t < T; t += 256) {
+        const int i = img_of[t];
+        below += i < b ? 1 : 0;
+        upto += i <= b ? 1 : 0;
+    }
+    for (int s = 32; s >= 1; s >>= 1) {
+        below += __shfl_xor(below, s);
+        upto += __shfl_xor(upto, s);
+    }
+    if ((tid & 63) == 0) {
+        atomicAdd(&s_t[0], below);
+        atomicAdd(&s_t[1], upto);
+    }
+    for (int i = tid; i < (SW_TH + 2 * SW_HALO) * (SW_TW + 2 * SW_HALO); i += 256) {
+        const int r = i / (SW_TW + 2 * SW_HALO), c = i % (SW_TW + 2 * SW_HALO);
+        const int y = y0 + r - SW_HALO, x = x0 + c - SW_HALO;
+        s_u[r][c] = (y >= 0 && y < H && x >= 0 && x < W) ? u[(size_t)y * W + x] : INT_MIN;
+    }
+    __syncthreads();
+    const int t0 = s_t[0], A = s_t[1] - s_t[0], E = K + 1;
+    const long long want = (long long)(1 + 2 * A) * E;
+    const bool local = want <= (long long)lds_counters;                    // (uniform over the workgroup)
+    if (local)
+        for (int i = tid; i < (int)want; i += 256) sw_hist[i] = 0u;
+    for (int i = tid; i < (SW_TH + 2 * SW_HALO) * SW_TW; i += 256) {
+        const int r = i / SW_TW, c = i % SW_TW;
+        int m = s_u[r][c];
+#pragma unroll
+        for (int d = 1; d <= 2 * SW_HALO; ++d) m = max(m, s_u[r][c + d]);
+        s_hor[r][c] = m;
+    }
+    __syncthreads();
+    const int wp = bits_wp(W);
+    const size_t words = (size_t)H * wp;
+    unsigned *g_map = hist + (size_t)b * E, *g_ann = hist + ((size_t)B + 2 * (size_t)t0) * E;
+    for (int i = tid; i < SW_TH * SW_TW; i += 256) {
+        const int ty = i / SW_TW, tx = i % SW_TW, y = y0 + ty, x = x0 + tx;
+        if (y >= H || x >= W) continue;
+        const int v = s_u[ty + SW_HALO][tx + SW_HALO];
+        int m5 = s_hor[ty][tx];
+#pragma unroll
+        for (int d = 1; d <= 2 * SW_HALO; ++d) m5 = max(m5, s_hor[ty + d][tx]);
+        const bool v_ok = v >= 1 && v <= K, m_ok = m5 >= 1 && m5 <= K;   // a value outside 1 .. K is counted nowhere
+        if (!v_ok && !m_ok) continue;
+        if (v_ok) atomicAdd(local ? &sw_hist[v] : &g_map[v], 1u);
+        const size_t wi = (size_t)y * wp + (x >> 6);
+        const int bit = x & 63;
+        for (int a = 0; a < A; ++a) {
+            if (m_ok && ((tru[(size_t)(t0 + a) * words + wi] >> bit) & 1ull))
+                atomicAdd(local ? &sw_hist[(size_t)(1 + 2 * a) * E + m5] : &g_ann[(size_t)(2 * a) * E + m5], 1u);
+            if (v_ok && ((tru[((size_t)T + t0 + a) * words + wi] >> bit) & 1ull))
+                atomicAdd(local ? &sw_hist[(size_t)(2 + 2 * a) * E + v] : &g_ann[(size_t)(2 * a + 1) * E + v], 1u);
+        }
+    }
+    if (!local) return;
+    __syncthreads();
+    for (int i = tid; i < (int)want; i += 256) {
+        const unsigned c = sw_hist[i];
+        if (c) atomicAdd(i < E ? &g_map[i] : &g_ann[i - E], c);
+    }
+}
+
+extern "C" int gcs_boundary_sweep_resident(const int32_t *contours, const void *truth_planes, const int32_t *img_of, int B, int T,
+                                           int H, int W, int K, uint32_t *hist_out, gcs_stream_t stream) {
+    if (!contours || !truth_planes || !img_of || !hist_out) return gcs_fail(GCS_EINVAL, "gcs_boundary_sweep_resident: NULL pointer");
+    if (B < 1 || B > 65535 || T < 1 || T > 1000000 || H < 1 || W < 1 || H > 4096 || W > 4096 || K < 1 || K > 4096)
+        return gcs_fail(GCS_EINVAL, "gcs_boundary_sweep_resident: bad shape (1 <= B <= 65535, 1 <= T <= 1000000, 1 <= H, W <= 4096, 1 <= K <= 4096)");
+    const long long n = ((long long)B + 2LL * T) * (K + 1);
+    if (n > 0x7fffffffLL) return gcs_fail(GCS_EINVAL, "gcs_boundary_sweep_resident: (B + 2 T)(K + 1) must be below 2^31");
+    ZeroList z{};
+    z.p[0] = hist_out;
+    z.n[0] = (unsigned)n;
+    hipLaunchKernelGGL(zero_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, stream, z);
+    GCS_CHECK_LAUNCH("gcs_boundary_sweep_resident(zero)");
+    const long long most = (1LL + 2LL * T) * (K + 1);                      // (the kernel decides per image: A_b is data)
+    const int lds_counters = (int)(most < SW_LDS_COUNTERS ? most : SW_LDS_COUNTERS);
+    hipLaunchKernelGGL(boundary_sweep_kernel, dim3((W + SW_TW - 1) / SW_TW, (H + SW_TH - 1) / SW_TH, B), dim3(256),
+                       (size_t)lds_counters * sizeof(unsigned), stream, contours, static_cast<const unsigned long long *>(truth_planes),
+                       img_of, B, T, H, W, K, lds_counters, hist_out);
+    GCS_CHECK_LAUNCH("gcs_boundary_sweep_resident");
     return GCS_OK;
 }
 

@@ -212,3 +212,29 @@ def region_agreement(labels, segments_truth) -> dict:
         raise ValueError(f"region agreement needs at least 2 pixels, got {labels.size}")
     st = [agreement_sums(labels, g) for g in segments_truth]
     return agreement_from_sums([s for s, _ in st], [t for _, t in st], [0, len(st)], labels.size)[0]
+
+
+# ---- the whole hierarchy at once (SPEC.md §15)
+
+def ods_ois(f_table, regions) -> dict:
+    """``f_table[b][j]`` = F of image b at ``regions[j]`` -> ``{"OIS", "ODS", "ODS_regions", "OIS_regions"}``: OIS = the mean over the
+    images of each image's best F, ODS = the best mean F of one R for the whole set (on ties the smallest R), ``OIS_regions`` = each
+    image's best R (smallest on ties). Plain Python floats, summed in image order."""
+    regions = [int(r) for r in regions]
+    rows = [[float(v) for v in row] for row in f_table]
+    if not rows or not regions or any(len(row) != len(regions) for row in rows):
+        raise ValueError("f_table must be a non-empty list of rows with one F per entry of regions")
+    order = sorted(range(len(regions)), key=lambda j: regions[j])           # ties go to the smallest R: visit R in increasing order
+    best_r, ois = [], 0.0
+    for row in rows:
+        j = max(order, key=lambda q: row[q])                               # max keeps the first of equals
+        best_r.append(regions[j])
+        ois += row[j]
+    means = []
+    for j in range(len(regions)):
+        m = 0.0
+        for row in rows:
+            m += row[j]
+        means.append(m / len(rows))
+    jd = max(order, key=lambda q: means[q])
+    return {"OIS": ois / len(rows), "ODS": means[jd], "ODS_regions": regions[jd], "OIS_regions": best_r}

@@ -498,3 +498,80 @@ def all_scores_batch_resident(labels, truth: DeviceTruth, n_segments=None, agree
     device, ONE device-to-host copy of a few KB. ``n_segments``: an upper bound of max label + 1 over the batch (the
     Segmenter's k); None reads it from the labels (one more synchronisation)."""
     return submit_scores_batch_resident(labels, truth, n_segments, agreement).result()
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Every cut of a region tree at once (SPEC.md §15): three histograms of the contour map per image, one pass over the map.
+
+def boundary_sweep_resident(contours, alive, truth: DeviceTruth):
+    """contours: (B,H,W) int32 device tensor of ``Segmenter.contour_map_device``; alive: the (B,) int32 tensor beside it; truth: the resident ground truth of the same images. Returns host arrays
+    ``(hist_map uint32 [B][K + 1], hist_rec uint32 [T][K + 1], hist_prec uint32 [T][K + 1])`` with K = max(alive) (every level
+    the batch's trees have): #{U = s}, #{bd(T_t) : M5(U) = s}, #{dil5(bd(T_t)) : U = s}. Buffers of its own: ``truth``'s result block and
+    its one-submission rule are not touched."""
+    import torch
+    lib = _lib.load()
+    if contours.dtype != torch.int32 or contours.dim() != 3:
+        raise ValueError("contours must be a (B,H,W) int32 tensor")
+    b, h, w = contours.shape
+    if (b, h, w) != (truth.b, truth.h, truth.w) or contours.device != truth.device:
+        raise ValueError("contour batch does not match the resident truth (images, shape or device)")
+    if tuple(alive.shape) != (b,):
+        raise ValueError("alive must be a (B,) tensor")
+    if h > 4096 or w > 4096:
+        raise ValueError("the sweep takes images of at most 4096 x 4096 pixels")
+    k = min(max(1, int(alive.max().item())), SWEEP_LEVELS)       # U lies in 0 .. alive: the bins of the largest tree of the batch
+    contours = contours.contiguous()
+    with torch.cuda.device(truth.device):
+        hist = torch.empty((b + 2 * truth.t, k + 1), dtype=torch.int32, device=truth.device)
+        _lib.check(lib.gcs_boundary_sweep_resident(contours.data_ptr(), truth.planes.data_ptr(), truth.img_of_d.data_ptr(), b, truth.t,
+                                                   h, w, k, hist.data_ptr(), torch.cuda.current_stream(truth.device).cuda_stream),
+                   "gcs_boundary_sweep_resident")
+        raw = hist.cpu().numpy().view(np.uint32)
+    ann = raw[b:].reshape(truth.t, 2, k + 1)
+    return raw[:b].copy(), ann[:, 0].copy(), ann[:, 1].copy()
+
+
+SWEEP_LEVELS = 4096                                              # the most labels a region tree has (SPEC.md §14)
+
+
+def sweep_counts(hists, alive, bd_counts, first, regions) -> np.ndarray:
+    """The integer counts ``gcs_boundary_counts_resident`` returns for the cut at every R of ``regions``, from the histograms of
+    ``boundary_sweep_resident``: uint64 [len(regions)][B + 3T] in that call's layout ([b], then per annotator [B + 3t] recall
+    numerator, [B + 3t + 1] = bd_counts[t], [B + 3t + 2] precision numerator): suffix sums over the bins above
+    max(0, alive_b - R)."""
+    hist_map, hist_rec, hist_prec = (np.asarray(x).astype(np.uint64) for x in hists)
+    alive = np.asarray(alive).astype(np.int64).ravel()
+    first = np.asarray(first).astype(np.int64)
+    bd_counts = np.asarray(bd_counts).astype(np.uint64).ravel()
+    b, t, nb = hist_map.shape[0], hist_rec.shape[0], hist_map.shape[1]
+    if len(alive) != b or len(first) != b + 1 or int(first[-1]) != t or len(bd_counts) != t:
+        raise ValueError("alive / first / bd_counts do not describe the histograms")
+    # above[s] = sum of the bins > s (s = 0 .. nb - 1)
+    above = [np.concatenate([np.cumsum(x[:, ::-1], axis=1)[:, ::-1][:, 1:], np.zeros((x.shape[0], 1), np.uint64)], axis=1)
+             for x in (hist_map, hist_rec, hist_prec)]
+    img_of = np.repeat(np.arange(b), np.diff(first))
+    out = np.zeros((len(regions), b + 3 * t), np.uint64)
+    for j, r in enumerate(regions):
+        if int(r) < 1:
+            raise ValueError("R must be >= 1")
+        tau = np.minimum(np.maximum(alive - int(r), 0), nb - 1)
+        out[j, :b] = above[0][np.arange(b), tau]
+        out[j, b::3] = above[1][np.arange(t), tau[img_of]]
+        out[j, b + 1::3] = bd_counts
+        out[j, b + 2::3] = above[2][np.arange(t), tau[img_of]]
+    return out
+
+
+def sweep_scores(hists, alive, bd_counts, first, regions) -> list:
+    """Per image a list with one ``{"recall", "precision", "fmeasure"}`` per R of ``regions``: the floats
+    ``all_scores_batch_resident`` gives for ``cut_regions_device(..., R)`` (the same integer counts through the same float
+    operations in the same order, ``scores_from_counts``). ZeroDivisionError where the reference raises it: a cut without a
+    boundary pixel (R = 1), an annotator map without one."""
+    counts = sweep_counts(hists, alive, bd_counts, first, regions)
+    first = np.asarray(first).astype(np.int64)
+    b = len(first) - 1
+    out = []
+    for i in range(b):
+        t0, t1 = int(first[i]), int(first[i + 1])
+        out.append([scores_from_counts(np.concatenate([c[i:i + 1], c[b + 3 * t0:b + 3 * t1]])) for c in counts])
+    return out

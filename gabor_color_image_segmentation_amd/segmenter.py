@@ -451,6 +451,32 @@ class HipOps:
         _lib.check(self.lib.gcs_region_tree_cut(labels.data_ptr(), merges.data_ptr() if K > 1 else None, alive.data_ptr(), b, h, w, K,
                                                 int(R), out.data_ptr(), self._stream()), "gcs_region_tree_cut")
 
+    def contour_buffers(self, b, K):
+        """The workspace of ``gcs_region_tree_contours`` for ``b`` images of ``K`` labels (SPEC.md §15): per image the positions of
+        the labels in the tree's leaf order and the range-maximum table over its gaps (a captured graph must own it)."""
+        need = self.lib.gcs_region_tree_contours_workspace_bytes(int(b), int(K))
+        if need == 0:
+            raise ValueError("no contour map for this batch / K (1 <= B <= 65535, 1 <= K <= 4096)")
+        return self.empty_bytes(need)
+
+    @_on_device
+    def region_tree_contours(self, labels, merges, alive, b, h, w, K, workspace, out):
+        """The contour map of SPEC.md §15: ``out`` (B,H,W) int32 (not ``labels``: neighbours are read) gets, per pixel, the level in
+        0 .. alive at which its boundary disappears from the tree. ``workspace``: from ``contour_buffers``. Two launches, capturable."""
+        torch, K = self.torch, int(K)
+        for name, t in (("labels", labels), ("out", out)):
+            if t.dtype != torch.int32 or tuple(t.shape) != (b, h, w) or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous (B,H,W) int32 tensor")
+        if out.data_ptr() == labels.data_ptr():
+            raise ValueError("out must not be labels: the contour map reads every pixel's neighbours")
+        if merges.dtype != torch.int32 or tuple(merges.shape) != (b, K - 1, 2) or not merges.is_contiguous():
+            raise ValueError("merges must be a contiguous (B, K - 1, 2) int32 tensor")
+        if alive.dtype != torch.int32 or tuple(alive.shape) != (b,) or not alive.is_contiguous():
+            raise ValueError("alive must be a contiguous (B,) int32 tensor")
+        _lib.check(self.lib.gcs_region_tree_contours(labels.data_ptr(), merges.data_ptr() if K > 1 else None, alive.data_ptr(), b, h, w,
+                                                     K, workspace.data_ptr(), out.data_ptr(), self._stream()),
+                   "gcs_region_tree_contours")
+
     def download(self, dst_pinned, src):
         """Device tensor -> pinned host tensor of the same bytes on the current stream, by SDMA (gcs_download)."""
         self._check_dev(src)
@@ -964,6 +990,39 @@ class Segmenter:
         with (torch.cuda.device(self.ops.device) if self.native else contextlib.nullcontext()):
             self.ops.region_tree_cut(labels, merges, alive, b, h, w, merges.shape[1] + 1, R, out)
         return out
+
+    def contour_map_device(self, labels, merges, alive, out=None):
+        """The contour map of SPEC.md §15 of a tree ``region_tree_device`` returned (or of any label map and merge list of that
+        form): a (B,H,W) int32 tensor, 0 inside the regions of the finest cut and, on a boundary pixel, the level in 1 .. alive at
+        which that boundary disappears: ``contours > max(0, alive - R)`` is the thick boundary map of the cut at R. It describes
+        the raw cuts: ``connectivity`` and ``min_region_size`` are not reflected. ``out``: a tensor to fill (not ``labels``)."""
+        torch = _torch()
+        if not hasattr(self.ops, "region_tree_contours"):
+            raise ValueError("contour_map_device needs ops that have the contour map")
+        if labels.dim() != 3 or labels.dtype != torch.int32:
+            raise ValueError("labels must be a (B,H,W) int32 tensor")
+        b, h, w = labels.shape
+        if merges.dim() != 3 or merges.shape[0] != b or merges.shape[2] != 2 or not 1 <= merges.shape[1] + 1 <= SUPERPIXELS_MAX:
+            raise ValueError(f"merges must be a (B, K - 1, 2) int32 tensor with K in 1..{SUPERPIXELS_MAX}")
+        if tuple(alive.shape) != (b,):
+            raise ValueError("alive must be a (B,) int32 tensor")
+        if h > _SP_SIDE_MAX or w > _SP_SIDE_MAX or b > 65535:
+            raise ValueError(f"the contour map takes at most 65535 images of at most {_SP_SIDE_MAX} x {_SP_SIDE_MAX} pixels")
+        K = merges.shape[1] + 1
+        if out is None:
+            out = torch.empty_like(labels)
+        with (torch.cuda.device(self.ops.device) if self.native else contextlib.nullcontext()):
+            # (the workspace comes from and goes back to the stream-ordered allocator: no state a second stream could share)
+            self.ops.region_tree_contours(labels, merges, alive, b, h, w, K, self.ops.contour_buffers(b, K), out)
+        return out
+
+    def contours_device(self, imgs):
+        """(B,H,W,3) uint8 device tensor -> (contours (B,H,W) int32, alive (B,) int32): features, superpixels (SPEC.md §13), tree
+        (§14), contour map (§15). Needs ``Segmenter(n_superpixels=n)``; any ``n_regions`` of the plan is ignored."""
+        if not hasattr(self.ops, "region_tree_contours"):
+            raise ValueError("contours_device needs ops that have the contour map")
+        labels, merges, _, alive = self.region_tree_device(imgs)
+        return self.contour_map_device(labels, merges, alive), alive
 
     def superpixels_device(self, imgs):
         """(B,H,W,3) uint8 device tensor -> (labels (B,H,W) int32, centres (B, ny * nx, D + 2) int32: the D features, cy, cx the
@@ -1647,6 +1706,22 @@ def _plan(kw) -> Segmenter:
 def segment(img, **kw) -> np.ndarray:
     """Drop-in for ``slic(img, ...)`` at script.py:30: (H,W,3) uint8 -> (H,W) int32 labels 0..k-1."""
     return _plan(kw)(img)
+
+
+def segment_contours(img, **kw) -> np.ndarray:
+    """(H,W,3) uint8 -> (H,W) float32 boundary strengths in [0, 1]: the contour map of SPEC.md §15 divided by max(1, alive), so
+    that thresholding it at (alive - R) / alive gives the boundaries of the cut at R regions. ``kw``: the plan's options
+    (``n_superpixels`` is needed); the plan is cached like ``segment``'s."""
+    torch = _torch()
+    img = np.ascontiguousarray(img)
+    if img.ndim != 3 or img.shape[2] != 3 or img.dtype != np.uint8:
+        raise ValueError("img must be an (H,W,3) uint8 array")
+    if not kw.get("n_superpixels"):
+        raise ValueError("segment_contours needs n_superpixels=n with n > 0")
+    seg = _plan(kw)
+    dev = torch.from_numpy(img[None]).to(seg.ops.device) if seg.native else torch.from_numpy(img[None])
+    contours, alive = seg.contours_device(dev)
+    return (contours[0].cpu().numpy().astype(np.float32) / np.float32(max(1, int(alive[0])))).astype(np.float32)
 
 
 def segment_images(images, batch=64, **kw):

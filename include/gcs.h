@@ -410,6 +410,34 @@ int gcs_region_tree(const uint16_t *feats_canonical_dev, const int32_t *labels_d
 int gcs_region_tree_cut(const int32_t *labels_dev, const int32_t *merges_dev, const int32_t *alive_dev, int B, int H, int W, int K,
                         int R, int32_t *labels_out_dev, gcs_stream_t stream);
 
+/* ---- contour map of the region tree, and the boundary counts of every cut at once (SPEC.md §15) ---- */
+
+/* U(y, x) = the largest s(L(y, x), L(y', x')) over the 4-neighbours inside the image, s(p, q) = t + 1 for the row t of merges_dev whose
+ * merge first puts the labels p and q into one group, `alive` where no row does or one of them is outside 0 .. K-1, 0 for p = q. For
+ * every R >= 1, U > max(0, alive - R) is the thick boundary map of gcs_region_tree_cut at R.
+ *   gcs_region_tree_contours_workspace_bytes  host only: per image K uint16 positions and a range-maximum table of ceil(log2 K) levels
+ *                                    of K uint16 entries. 0 for a bad argument. Contents are undefined before and after a call.
+ *   gcs_region_tree_contours         two launches on `stream` (prepare: a workgroup per image; pixels). No allocation, no host
+ *                                    synchronisation (capturable). merges_dev / alive_dev as gcs_region_tree wrote them, or any list
+ *                                    whose written rows come first and have a < b, both reps at that step (a row that is not is
+ *                                    skipped). contours_out_dev int32 [B][H][W], values 0 .. alive; it must NOT overlap labels_dev
+ *                                    (neighbours are read). With K = 1 merges_dev is not read.
+ *   gcs_boundary_sweep_resident      two launches (zero, one pass over the map). hist_out_dev uint32 [B + 2T][K + 1], zeroed by the call:
+ *                                    row b: #{U_b = s}; row B + 2t: #{bd(T_t) : M5(U) = s}; row B + 2t + 1: #{dil5(bd(T_t)) : U = s},
+ *                                    for s = 1 .. K (bin 0 stays 0, a value of U outside 1 .. K is counted nowhere), M5 = the maximum over
+ *                                    the 5 x 5 window clipped to the image. With tau = max(0, alive_b - R) the sums over s > tau are the
+ *                                    counts [b], [B + 3t] and [B + 3t + 2] of gcs_boundary_counts_resident for the cut at R.
+ *                                    truth_planes_dev: what gcs_truth_prepare wrote; img_of_dev int32 [T], non-decreasing (the
+ *                                    annotators of an image are consecutive). No allocation, no host synchronisation (capturable).
+ * GCS_EINVAL, with nothing launched: a NULL pointer (merges_dev may be NULL with K = 1), contours_out_dev == labels_dev, B outside
+ * 1..65535, H or W outside 1..4096, K outside 1..4096, T outside 1..1000000, (B + 2T)(K + 1) >= 2^31.
+ * Added within ABI 18: new entry points change no existing call, so GCS_ABI_VERSION did not move. */
+size_t gcs_region_tree_contours_workspace_bytes(int B, int K);
+int gcs_region_tree_contours(const int32_t *labels_dev, const int32_t *merges_dev, const int32_t *alive_dev, int B, int H, int W, int K,
+                             void *workspace_dev, int32_t *contours_out_dev, gcs_stream_t stream);
+int gcs_boundary_sweep_resident(const int32_t *contours_dev, const void *truth_planes_dev, const int32_t *img_of_dev, int B, int T,
+                                int H, int W, int K, uint32_t *hist_out_dev, gcs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
