@@ -7,11 +7,15 @@ metrics.__init__ (/root/reference/BSD_metrics/metrics.py:43-51). Errors are plai
 exceptions (script.py:19-38 catches nothing).
 
 PyTorch is plumbing only: device memory, the current HIP stream and torch.distributed
-(RCCL). All arithmetic runs in libgcs.so (csrc/gcs.hip) through the C ABI
-(include/gcs.h). There is no CPU fallback.
+(RCCL). All arithmetic runs in libgcs.so (one csrc/*.hip file per stage, csrc/abi.hip for the
+entry points) through the C ABI (include/gcs.h). There is no CPU fallback.
+
+Every host path runs the same per-batch step, ``_step_features`` then ``_step_cluster``, around its own buffers,
+streams and events (DESIGN.md §1 lists which path wraps them with what).
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import math
 import os
@@ -58,7 +62,6 @@ class DebugSwitches:
 
 
 _ENV_DEBUG = DebugSwitches(os.environ.get("GCS_DEBUG", ""))
-
 
 
 class _CaptureGuard:
@@ -251,6 +254,32 @@ class HipOps:
             if t.device != self.device:
                 raise ValueError(f"tensor on {t.device}, this Segmenter's kernels run on {self.device}")
 
+    @staticmethod
+    def _need(t, dtypes, shape, what):
+        """The ONE tensor-argument check: ``t`` (None passes: an optional output) is a contiguous tensor of ``shape`` and of one
+        of ``dtypes`` (a dtype or a tuple of them), or ValueError(``what``)."""
+        if t is not None and (t.dtype not in (dtypes if isinstance(dtypes, tuple) else (dtypes,)) or tuple(t.shape) != shape
+                              or not t.is_contiguous()):
+            raise ValueError(what)
+
+    def _need_tree(self, b, h, w, K, merges, alive, **maps):
+        """What the entry points of SPEC.md §14 and §15 share: (B,H,W) int32 maps by name, the merge list and ``alive``."""
+        for name, t in maps.items():
+            self._need(t, self.torch.int32, (b, h, w), f"{name} must be a contiguous (B,H,W) int32 tensor")
+        self._need(merges, self.torch.int32, (b, K - 1, 2), "merges must be a contiguous (B, K - 1, 2) int32 tensor")
+        self._need(alive, self.torch.int32, (b,), "alive must be a contiguous (B,) int32 tensor")
+
+    def _scratch(self, shared, scratch, need, what):
+        """The caller's ``scratch`` when it gave one (checked), else the shared, growing workspace this HipOps keeps in the
+        attribute ``shared`` (see ``gabor_features`` for who may use which)."""
+        if scratch is None:
+            if getattr(self, shared) is None or getattr(self, shared).numel() < need:
+                setattr(self, shared, self.empty_bytes(need))
+            return getattr(self, shared)
+        if scratch.numel() < need or scratch.device != self.device:
+            raise ValueError(f"{what} scratch too small or on another device")
+        return scratch
+
     # ---- device entry points
     def gabor_scratch(self, b, h, w):
         """A private Gabor workspace for one (batch, shape): what a captured graph must own (see ``gabor_features``)."""
@@ -263,13 +292,7 @@ class HipOps:
         same stream only), NOT for a captured graph: a replay would keep writing through the raw pointer of a block that
         a later, larger call has meanwhile given back to the allocator."""
         b, h, w, _ = imgs.shape
-        need = self.lib.gcs_gabor_workspace_bytes(b, h, w, self.bank.n_scales)
-        if scratch is None:
-            if self._gabor_ws is None or self._gabor_ws.numel() < need:
-                self._gabor_ws = self.empty_bytes(need)
-            scratch = self._gabor_ws
-        elif scratch.numel() < need or scratch.device != self.device:
-            raise ValueError("gabor scratch too small or on another device")
+        scratch = self._scratch("_gabor_ws", scratch, self.lib.gcs_gabor_workspace_bytes(b, h, w, self.bank.n_scales), "gabor")
         _lib.check(self.lib.gcs_gabor_features(imgs.data_ptr(), b, h, w, self.packed.data_ptr(),
                                                self.bias.data_ptr(), *self._bk,
                                                self.bank.ksize, self.bank.shift, scratch.data_ptr(),
@@ -303,13 +326,7 @@ class HipOps:
         ``gabor_features`` (a captured graph must own its workspace; eager calls may share the growing one of this HipOps)."""
         if self.smooth_taps is None:
             raise ValueError("smooth_features needs HipOps(smoothing=K) with K > 0")
-        need = self.lib.gcs_smooth_workspace_bytes(b, h, w, *self._bk)
-        if scratch is None:
-            if self._smooth_ws is None or self._smooth_ws.numel() < need:
-                self._smooth_ws = self.empty_bytes(need)
-            scratch = self._smooth_ws
-        elif scratch.numel() < need or scratch.device != self.device:
-            raise ValueError("smoothing scratch too small or on another device")
+        scratch = self._scratch("_smooth_ws", scratch, self.lib.gcs_smooth_workspace_bytes(b, h, w, *self._bk), "smoothing")
         _lib.check(self.lib.gcs_smooth_features(feats.data_ptr(), b, h, w, *self._bk, self.smooth_taps.data_ptr(),
                                                 self.smooth_radius.data_ptr(), scratch.data_ptr(), self._stream()),
                    "gcs_smooth_features")
@@ -330,8 +347,7 @@ class HipOps:
         d = self.bank.n_features
         if out is None:
             out = self.torch.empty((b, d, h, w), dtype=self.torch.int16, device=self.device)
-        elif out.dtype != self.torch.int16 or tuple(out.shape) != (b, d, h, w) or not out.is_contiguous():
-            raise ValueError("out must be a contiguous (B,D,H,W) int16 tensor")
+        self._need(out, self.torch.int16, (b, d, h, w), "out must be a contiguous (B,D,H,W) int16 tensor")
         _lib.check(self.lib.gcs_features_unpack(feats.data_ptr(), b, h, w, *self._bk, out.data_ptr(),
                                                 self._stream()), "gcs_features_unpack")
         return out
@@ -370,8 +386,7 @@ class HipOps:
         """The last Lloyd pass with the label map written in raster order: ``out`` (B,H,W) int32 or uint8 device tensor.
         ``fused=(workspace, t)``: as the last pass of a self-updating loop (see ``assign_accumulate``)."""
         torch = self.torch
-        if out.dtype not in (torch.int32, torch.uint8) or tuple(out.shape) != (b, h, w) or not out.is_contiguous():
-            raise ValueError("out must be a contiguous (B,H,W) int32 or uint8 tensor")
+        self._need(out, (torch.int32, torch.uint8), (b, h, w), "out must be a contiguous (B,H,W) int32 or uint8 tensor")
         if fused is not None:
             return self._pass_fused(feats, cent, b, h, w, k, n_sets, fused, reverse, out=out)
         _lib.check(self.lib.gcs_kmeans_assign_raster(
@@ -394,13 +409,9 @@ class HipOps:
         ``n_iter`` assigns; ``centres``: None or a (B, ny * nx, D + 2) int32 tensor that receives the centres that assign used
         (D features, cy, cx). ``workspace``: from ``superpixel_buffers``. One call, 2 n_iter launches, capturable."""
         torch, d = self.torch, self.bank.n_features
-        if canon.dtype != torch.int16 or tuple(canon.shape) != (b, d, h, w) or not canon.is_contiguous():
-            raise ValueError("canon must be the contiguous (B,D,H,W) int16 tensor of features_unpack")
-        if out.dtype != torch.int32 or tuple(out.shape) != (b, h, w) or not out.is_contiguous():
-            raise ValueError("out must be a contiguous (B,H,W) int32 tensor")
-        if centres is not None and (centres.dtype != torch.int32 or tuple(centres.shape) != (b, ny * nx, d + 2)
-                                    or not centres.is_contiguous()):
-            raise ValueError("centres must be a contiguous (B, ny * nx, D + 2) int32 tensor")
+        self._need(canon, torch.int16, (b, d, h, w), "canon must be the contiguous (B,D,H,W) int16 tensor of features_unpack")
+        self._need(out, torch.int32, (b, h, w), "out must be a contiguous (B,H,W) int32 tensor")
+        self._need(centres, torch.int32, (b, ny * nx, d + 2), "centres must be a contiguous (B, ny * nx, D + 2) int32 tensor")
         _lib.check(self.lib.gcs_superpixel_segment(canon.data_ptr(), b, h, w, d, int(ny), int(nx), int(spatial_weight), int(n_iter),
                                                    workspace.data_ptr(), out.data_ptr(),
                                                    None if centres is None else centres.data_ptr(), self._stream()),
@@ -421,16 +432,9 @@ class HipOps:
         """SPEC.md §14 on canonical features and an int32 (B,H,W) label map in 0 .. K-1: fills ``merges`` (B, K-1, 2) int32, ``costs``
         (None or (B, K-1) int64) and ``alive`` (B,) int32. ``workspace``: from ``region_tree_buffers``. Three launches, capturable."""
         torch, d, K = self.torch, self.bank.n_features, int(K)
-        if canon.dtype != torch.int16 or tuple(canon.shape) != (b, d, h, w) or not canon.is_contiguous():
-            raise ValueError("canon must be the contiguous (B,D,H,W) int16 tensor of features_unpack")
-        if labels.dtype != torch.int32 or tuple(labels.shape) != (b, h, w) or not labels.is_contiguous():
-            raise ValueError("labels must be a contiguous (B,H,W) int32 tensor")
-        if merges.dtype != torch.int32 or tuple(merges.shape) != (b, K - 1, 2) or not merges.is_contiguous():
-            raise ValueError("merges must be a contiguous (B, K - 1, 2) int32 tensor")
-        if costs is not None and (costs.dtype != torch.int64 or tuple(costs.shape) != (b, K - 1) or not costs.is_contiguous()):
-            raise ValueError("costs must be a contiguous (B, K - 1) int64 tensor")
-        if alive.dtype != torch.int32 or tuple(alive.shape) != (b,) or not alive.is_contiguous():
-            raise ValueError("alive must be a contiguous (B,) int32 tensor")
+        self._need(canon, torch.int16, (b, d, h, w), "canon must be the contiguous (B,D,H,W) int16 tensor of features_unpack")
+        self._need_tree(b, h, w, K, merges, alive, labels=labels)
+        self._need(costs, torch.int64, (b, K - 1), "costs must be a contiguous (B, K - 1) int64 tensor")
         _lib.check(self.lib.gcs_region_tree(canon.data_ptr(), labels.data_ptr(), b, h, w, d, K, workspace.data_ptr(),
                                             merges.data_ptr() if K > 1 else None,
                                             None if costs is None or K == 1 else costs.data_ptr(), alive.data_ptr(), self._stream()),
@@ -440,14 +444,8 @@ class HipOps:
     def region_tree_cut(self, labels, merges, alive, b, h, w, K, R, out):
         """The cut of SPEC.md §14 at ``R``: ``out`` (B,H,W) int32 (it may be ``labels``) gets min(alive, R) labels per image. One
         launch, capturable."""
-        torch, K = self.torch, int(K)
-        for name, t in (("labels", labels), ("out", out)):
-            if t.dtype != torch.int32 or tuple(t.shape) != (b, h, w) or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous (B,H,W) int32 tensor")
-        if merges.dtype != torch.int32 or tuple(merges.shape) != (b, K - 1, 2) or not merges.is_contiguous():
-            raise ValueError("merges must be a contiguous (B, K - 1, 2) int32 tensor")
-        if alive.dtype != torch.int32 or tuple(alive.shape) != (b,) or not alive.is_contiguous():
-            raise ValueError("alive must be a contiguous (B,) int32 tensor")
+        K = int(K)
+        self._need_tree(b, h, w, K, merges, alive, labels=labels, out=out)
         _lib.check(self.lib.gcs_region_tree_cut(labels.data_ptr(), merges.data_ptr() if K > 1 else None, alive.data_ptr(), b, h, w, K,
                                                 int(R), out.data_ptr(), self._stream()), "gcs_region_tree_cut")
 
@@ -463,16 +461,10 @@ class HipOps:
     def region_tree_contours(self, labels, merges, alive, b, h, w, K, workspace, out):
         """The contour map of SPEC.md §15: ``out`` (B,H,W) int32 (not ``labels``: neighbours are read) gets, per pixel, the level in
         0 .. alive at which its boundary disappears from the tree. ``workspace``: from ``contour_buffers``. Two launches, capturable."""
-        torch, K = self.torch, int(K)
-        for name, t in (("labels", labels), ("out", out)):
-            if t.dtype != torch.int32 or tuple(t.shape) != (b, h, w) or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous (B,H,W) int32 tensor")
+        K = int(K)
+        self._need_tree(b, h, w, K, merges, alive, labels=labels, out=out)
         if out.data_ptr() == labels.data_ptr():
             raise ValueError("out must not be labels: the contour map reads every pixel's neighbours")
-        if merges.dtype != torch.int32 or tuple(merges.shape) != (b, K - 1, 2) or not merges.is_contiguous():
-            raise ValueError("merges must be a contiguous (B, K - 1, 2) int32 tensor")
-        if alive.dtype != torch.int32 or tuple(alive.shape) != (b,) or not alive.is_contiguous():
-            raise ValueError("alive must be a contiguous (B,) int32 tensor")
         _lib.check(self.lib.gcs_region_tree_contours(labels.data_ptr(), merges.data_ptr() if K > 1 else None, alive.data_ptr(), b, h, w,
                                                      K, workspace.data_ptr(), out.data_ptr(), self._stream()),
                    "gcs_region_tree_contours")
@@ -555,14 +547,19 @@ def _collective(fn, t, **kw):
         fn(t, **kw)
 
 
+def _as_int(v):
+    """``v`` as an int when it is a whole number and not a bool, else None: the test every integer option shares."""
+    try:
+        i = int(v)
+    except (TypeError, ValueError, OverflowError):
+        return None
+    return i if i == v and not isinstance(v, bool) else None
+
+
 def _check_chroma_gain(chroma_gain) -> int:
     """SPEC.md §11 parameter: the integer 0 (off) or 1..16."""
-    try:
-        g = int(chroma_gain)
-        ok = g == chroma_gain and not isinstance(chroma_gain, bool)
-    except (TypeError, ValueError, OverflowError):
-        ok = False
-    if not ok or not (0 <= g <= 16):
+    g = _as_int(chroma_gain)
+    if g is None or not (0 <= g <= 16):
         raise ValueError(f"chroma_gain must be the integer 0 (off) or 1..16, got {chroma_gain!r}")
     return g
 
@@ -594,19 +591,12 @@ def superpixel_grid(height, width, n):
 
 def _check_superpixels(n_superpixels, spatial_weight):
     """SPEC.md §13 parameters: n the integer 0 (off) or 2..4096, lambda an integer in 1..65535."""
-    vals = []
-    for name, v, ok in (("n_superpixels", n_superpixels, lambda x: x == 0 or 2 <= x <= SUPERPIXELS_MAX),
-                        ("spatial_weight", spatial_weight, lambda x: 1 <= x <= 65535)):
-        try:
-            i = int(v)
-            good = i == v and not isinstance(v, bool) and ok(i)
-        except (TypeError, ValueError, OverflowError):
-            good = False
-        if not good:
-            raise ValueError(f"{name} must be " + ("the integer 0 (off) or 2..4096" if name == "n_superpixels"
-                                                   else "an integer in 1..65535") + f", got {v!r}")
-        vals.append(i)
-    return tuple(vals)
+    n, lam = _as_int(n_superpixels), _as_int(spatial_weight)
+    if n is None or not (n == 0 or 2 <= n <= SUPERPIXELS_MAX):
+        raise ValueError(f"n_superpixels must be the integer 0 (off) or 2..4096, got {n_superpixels!r}")
+    if lam is None or not (1 <= lam <= 65535):
+        raise ValueError(f"spatial_weight must be an integer in 1..65535, got {spatial_weight!r}")
+    return n, lam
 
 
 REGIONS_MAX = 4096            # SPEC.md §14: the option's range (a cut cannot have more labels than the superpixel grid has centres)
@@ -614,12 +604,8 @@ REGIONS_MAX = 4096            # SPEC.md §14: the option's range (a cut cannot h
 
 def _check_regions(n_regions, n_superpixels):
     """SPEC.md §14 parameter: R the integer 0 (off) or 1..4096, and only on top of the superpixel stage."""
-    try:
-        r = int(n_regions)
-        good = r == n_regions and not isinstance(n_regions, bool) and 0 <= r <= REGIONS_MAX
-    except (TypeError, ValueError, OverflowError):
-        good = False
-    if not good:
+    r = _as_int(n_regions)
+    if r is None or not (0 <= r <= REGIONS_MAX):
         raise ValueError(f"n_regions must be the integer 0 (off) or 1..{REGIONS_MAX}, got {n_regions!r}")
     if r > 0 and n_superpixels == 0:
         raise ValueError("n_regions > 0 merges superpixels: it needs n_superpixels > 0")
@@ -685,6 +671,84 @@ def lloyd(ops, feats, b, h, w, k, n_iter, mode, labels, partials, cent, sums, di
                 ops.finalize(sums, n_sets, k, cent)
 
 
+# What the per-batch step needs to know of a plan, made once in Segmenter.__init__ (``colour``, ``smooth``, ``position``: is the
+# stage on). The two pieces of the step take it, the ops, a workspace and the debug switches as arguments and never the
+# Segmenter: a graph entry holds them, and an entry that held its plan would be a reference cycle (see _segment_small).
+_StepOptions = collections.namedtuple("_StepOptions", "k n_iter colour smooth position n_superpixels spatial_weight n_regions")
+
+
+def _opponent(ops, imgs, colour):
+    """T_g of ``imgs`` (SPEC.md §11) into the plan-owned buffer ``colour``; returns it. The caller's tensor is not changed."""
+    ops.colour_opponent(imgs, colour)
+    return colour
+
+
+def _unpack(ops, ws, b, h, w, out=None):
+    """The canonical (B,D,H,W) tensor of the slab ``ws["feats"]``, into ``out`` or a fresh tensor."""
+    return ops.features_unpack(ws["feats"], b, h, w, **({} if out is None else {"out": out}))
+
+
+def _step_features(ops, opt, ws, imgs, b, h, w, y0=0, chunk=None):
+    """The first piece of the per-batch step, on the (B,H,W,3) uint8 device tensor ``imgs``: the transform of SPEC.md §11 when
+    ``chroma_gain`` is on, the Gabor stage into ``ws["feats"]``, the smoothing of SPEC.md §10 when it is on, then the coordinate
+    planes of SPEC.md §12 when ``position_weight`` is on, written behind the Gabor stage and the smoothing (every entry point has
+    checked the range rule before its first launch). ``y0``: a row strip's first global row. ``chunk=(g0, g1)``: ``imgs`` holds images [g0, g1) of the ``b`` the slab is for; only their transform and their Gabor stage
+    are launched (the chunked upload, which overlaps the next chunk's copy with them). ``imgs=None`` launches the rest: what
+    follows the Gabor stage, once for the batch."""
+    if imgs is not None:
+        feats, colour = ws["feats"], ws.get("colour")
+        if chunk is not None:                      # (a chunk of 481 x 321 images starts at any byte)
+            feats = feats[chunk[0] * ops.lib.gcs_feature_slab_bytes(1, h, w, *ops._bk):]
+            colour = colour[chunk[0]:chunk[1]] if opt.colour else None
+        # a private Gabor scratch only where the workspace owns one (a graph entry: see HipOps.gabor_features)
+        ops.gabor_features(_opponent(ops, imgs, colour) if opt.colour else imgs, feats,
+                           **({"scratch": ws["scratch"]} if "scratch" in ws else {}))
+        if chunk is not None:
+            return
+    if opt.smooth:                                 # (in the chunked upload every chunk's Gabor stage is in front of it)
+        ops.smooth_features(ws["feats"], b, h, w, scratch=ws.get("smooth"))
+    if opt.position:
+        ops.position_features(ws["feats"], b, h, w, y0=y0)
+
+
+def _stage_buffers(ops, opt, ws, key, b, h, w):
+    """The one place where the buffers of SPEC.md §13 (``key`` "sp": canonical tensor, workspace) and §14 ("rt": workspace,
+    merges, costs, alive) join a workspace: at a stage's first use, or up front for a graph entry. Returns them. A stage that is
+    off leaves no key."""
+    if key not in ws:
+        _, ny, nx = superpixel_grid(h, w, opt.n_superpixels)
+        ws[key] = ops.superpixel_buffers(b, h, w, opt.n_superpixels) if key == "sp" else ops.region_tree_buffers(b, h, w, ny * nx)
+    return ws[key]
+
+
+def _step_cluster(ops, opt, ws, out, b, h, w, mode, debug, dist_group=None, rows=None, init=None, centres=None, tree=None):
+    """The second piece of the per-batch step, on the slab ``_step_features`` has filled: the labels of ``b`` images into ``out``,
+    a contiguous (B,H,W) device tensor. ``n_superpixels = 0``: the Lloyd loop of SPEC.md §4 (``rows``, ``init``, ``dist_group``:
+    see ``lloyd``); without a raster pass the label slab is widened into the int32 ``out``. ``n_superpixels > 0`` (SPEC.md §13
+    instead of §4): features -> canonical tensor -> the one call that enqueues every pass (``centres``: see
+    ``HipOps.superpixels``), then the tree of SPEC.md §14 on the raw §13 map and its cut in place. ``tree``: None = as the plan
+    says (tree and cut at ``n_regions`` when that is on), True = the tree without a cut (it stays in ``ws["rt"]``), False = no
+    tree. A uint8 ``out`` is narrowed from the int32 map of the workspace (a graph entry)."""
+    if opt.n_superpixels == 0:
+        raster = out if rows is None and hasattr(ops, "assign_raster") else None      # the last pass writes the raster map itself
+        lloyd(ops, ws["feats"], b, h, w, opt.k, opt.n_iter, mode, ws["labels"], ws["partials"], ws["cent"], ws["sums"],
+              dist_group, rows=rows, init=init, raster=raster, debug=debug, fold=ws.get("fold"))
+        if raster is None:
+            ops.labels_widen(ws["labels"], b, h, w, out)
+        return
+    _, ny, nx = superpixel_grid(h, w, opt.n_superpixels)
+    (canon, spws), out32 = _stage_buffers(ops, opt, ws, "sp", b, h, w), ws.get("out32", out)
+    _unpack(ops, ws, b, h, w, out=canon)
+    ops.superpixels(canon, b, h, w, ny, nx, opt.spatial_weight, opt.n_iter, out32, spws, centres)
+    if opt.n_regions > 0 if tree is None else tree:
+        rtws, merges, costs, alive = _stage_buffers(ops, opt, ws, "rt", b, h, w)
+        ops.region_tree(canon, out32, b, h, w, ny * nx, rtws, merges, costs, alive)
+        if tree is None:
+            ops.region_tree_cut(out32, merges, alive, b, h, w, ny * nx, opt.n_regions, out32)
+    if out32 is not out:
+        out.copy_(out32)                           # (K, or min(K, R), <= 256 was checked: the narrowing keeps every label)
+
+
 def halo_rows(n_levels: int = 2, ksize: int = 13) -> int:
     """Real neighbour rows an interior strip edge needs: the reach (ksize - 1) / 2 of the coarsest level's kernel in
     full-resolution rows (12 for the default 13x13 bank on two levels - the defaults here -, 14 for a 15x15 one)."""
@@ -733,7 +797,7 @@ class Segmenter:
             raise ValueError("n_iter must be >= 1")
         if int(min_region_size) != min_region_size or min_region_size < 0:
             raise ValueError("min_region_size must be a non-negative integer")
-        self.k, self.n_iter = int(k), int(n_iter)
+        self.k = int(k)
         self.debug = DebugSwitches(os.environ.get("GCS_DEBUG", ""))     # measurement / test switches (see the class)
         self.connectivity = bool(connectivity)     # SPEC.md §7 post-pass
         self.min_region_size = int(min_region_size)  # SPEC.md §9 post-pass (> 0: connected regions, small ones merged)
@@ -767,6 +831,8 @@ class Segmenter:
         # one (the library default: no extra memory, no host synchronisation, graph-capturable); bench.py asks for 2.
         self.slab_candidates = int(self.debug.slab_candidates or slab_candidates)
         self.slab_placement_ms = None
+        self._opt = _StepOptions(self.k, int(n_iter), self.chroma_gain > 0, self.smoothing > 0, self.position_weight > 0,
+                                 self.n_superpixels, self.spatial_weight, self.n_regions)
         self._ws = {}
         self._host = {}
         self._stream = {}
@@ -790,22 +856,106 @@ class Segmenter:
         (tests/fake_ops.py), which has no slabs, streams or graphs: the pipelined / captured host paths need ``native``."""
         return hasattr(self.ops, "lib")
 
+    @property
+    def n_iter(self):
+        return self._opt.n_iter
+
+    @n_iter.setter
+    def n_iter(self, n):             # (the one option that is changed on a live plan, by tests: the step's record follows)
+        self._opt = self._opt._replace(n_iter=int(n))
+
+    def _device(self):
+        """Launches go through ctypes on the current stream of ``self.ops.device``: the context that makes that device current
+        (the stand-in ops have no device)."""
+        return _torch().cuda.device(self.ops.device) if self.native else contextlib.nullcontext()
+
+    # ---- argument rules, path decisions
+    def _check_args(self, imgs=None, mode="per_image", out_dtype=None, dist_group=None, kind="array", cluster=True):
+        """The ONE set of argument rules of the entry points, applied before an entry point's first launch, in this order: the
+        batch ``imgs`` (a (B,H,W,3) uint8 ``kind``; None: no batch is at hand yet, the rules about its shape wait for it), ``mode``,
+        ``out_dtype`` (None: the entry point has none) and what it conflicts with, the smallest image, the range rule of SPEC.md
+        §12, the rules of SPEC.md §13 (not with ``cluster=False``: an entry point that stops behind the features). Returns
+        ``out_dtype`` as a ``np.dtype``."""
+        if imgs is not None and (not str(imgs.dtype).endswith("uint8") or imgs.ndim != 4 or imgs.shape[3] != 3):
+            raise ValueError(f"imgs must be a (B,H,W,3) uint8 {kind}")
+        if mode not in ("per_image", "global"):
+            raise ValueError("mode must be 'per_image' or 'global'")
+        if out_dtype is not None:
+            out_dtype = np.dtype(out_dtype)
+            if out_dtype not in (np.dtype(np.int32), np.dtype(np.uint8)):
+                raise ValueError("out_dtype must be int32 or uint8")
+            if self.connectivity and out_dtype == np.uint8:
+                raise ValueError("connectivity=True needs int32 labels")
+            if self.min_region_size > 0 and out_dtype == np.uint8:
+                raise ValueError("min_region_size > 0 needs int32 labels")
+        h = w = None
+        if imgs is not None:
+            h, w = imgs.shape[1:3]
+            if h < 8 or w < 8:
+                raise ValueError("images must be at least 8x8")
+            check_position_range(self.position_weight, h, w)
+        if self.n_superpixels > 0 and cluster:
+            self._superpixel_check(h, w, mode, out_dtype, dist_group)
+        return out_dtype
+
+    def _may_pipeline(self, mode, superpixels=False):
+        """May host batches of this plan leave the plain path (``segment_device`` between two blocking copies)? Not the test
+        stand-ins, the post-passes and the collectives; SPEC.md §13 only where the caller says so (``superpixels``: a small call
+        replays its graph like any other, but there is no chunked upload and no three-stream pipeline for it)."""
+        dist_on = False
+        if mode == "global":
+            import torch.distributed as td
+            dist_on = td.is_available() and td.is_initialized()
+        return self.native and not self.connectivity and self.min_region_size == 0 and not dist_on \
+            and not self.debug.force_collectives and (superpixels or self.n_superpixels == 0)
+
+    def _host_path(self, b, h, w, mode):
+        """How ``segment_batch`` runs a (b,h,w) batch: "graph" (replay of the captured step: calls of up to _GRAPH_MAX_PIXELS),
+        "chunked" (chunked upload, eager launches) or "plain" (see ``_may_pipeline``; a batch of more than one group; a large or
+        uncaptured superpixel call)."""
+        small = b * h * w <= _GRAPH_MAX_PIXELS and not self.debug.no_graph
+        if not self._may_pipeline(mode, superpixels=True) or self.group_size(b, h, w, mode) < b \
+                or (self.n_superpixels > 0 and not small):
+            return "plain"
+        return "graph" if small else "chunked"
+
     # ---- workspaces
+    def _tail_workspace(self, n, h, w, mode, slab_only=False, private=None):
+        """The buffers of one step on ``n`` images: the only place that allocates them. A key for a stage that is off stays
+        absent. ``slab_only``: no Lloyd buffers and no private smoothing scratch (``features_device``). ``private``: the out
+        dtype of a graph entry - a captured graph bakes raw pointers in, so every buffer it touches belongs to the entry and lives
+        exactly as long as the graph does: the stage buffers of SPEC.md §13 / §14 up front, the int32 map behind a uint8 superpixel
+        result, and the Gabor scratch (the shared scratch of HipOps is replaced, and its block recycled, whenever a later call
+        needs a larger one)."""
+        ops, opt = self.ops, self._opt
+        n_sets = n if mode == "per_image" else 1
+        ws = dict(feats=ops.feature_slab(n, h, w))
+        if not slab_only:
+            ws.update(labels=ops.label_slab(n, h, w), partials=ops.partial_slab(n, h, w, opt.k),
+                      cent=ops.new_centroids(n_sets, opt.k), sums=ops.new_sums(n_sets, opt.k))
+            if hasattr(ops, "fused_workspace"):
+                ws["fold"] = ops.fused_workspace(n, h, w, opt.k, n_sets)
+            if opt.smooth:
+                ws["smooth"] = ops.smooth_scratch(n, h, w)
+        if opt.colour:
+            ws["colour"] = ops.colour_scratch(n, h, w)
+        if private is not None:
+            if opt.n_superpixels > 0:
+                _stage_buffers(ops, opt, ws, "sp", n, h, w)
+                if opt.n_regions > 0:
+                    _stage_buffers(ops, opt, ws, "rt", n, h, w)
+                if private == np.uint8:
+                    ws["out32"] = _torch().empty((n, h, w), dtype=_torch().int32, device=ops.device)
+            ws["scratch"] = ops.gabor_scratch(n, h, w)
+        return ws
+
     def _workspace(self, g, h, w, mode):
+        """``_tail_workspace`` behind a cache of the most recent shapes, with the slab placed (``_place_slab``)."""
         key = (g, h, w, mode)
         ws = self._ws.get(key)
         if ws is None:
-            n_sets = g if mode == "per_image" else 1
-            ws = dict(feats=self.ops.feature_slab(g, h, w), labels=self.ops.label_slab(g, h, w),
-                      partials=self.ops.partial_slab(g, h, w, self.k),
-                      cent=self.ops.new_centroids(n_sets, self.k), sums=self.ops.new_sums(n_sets, self.k))
-            if hasattr(self.ops, "fused_workspace"):
-                ws["fold"] = self.ops.fused_workspace(g, h, w, self.k, n_sets)
-            if self.smoothing > 0:
-                ws["smooth"] = self.ops.smooth_scratch(g, h, w)
-            if self.chroma_gain > 0:
-                ws["colour"] = self.ops.colour_scratch(g, h, w)
-            self._place_slab(ws, g, h, w, n_sets)
+            ws = self._tail_workspace(g, h, w, mode)
+            self._place_slab(ws, g, h, w, g if mode == "per_image" else 1)
             # keep the eight most recent (batch, shape, mode) triples resident (a data set alternating landscape and
             # portrait batches, each with a remainder batch at its end, beside a global-codebook run, would otherwise
             # rebuild - and re-place - its workspace on every switch; 0.95 GB per 64-image entry)
@@ -868,19 +1018,10 @@ class Segmenter:
     def segment_device(self, imgs, mode="per_image", out=None, dist_group=None, group=None):
         """imgs: (B,H,W,3) uint8 device tensor -> (B,H,W) int32 device tensor."""
         torch = _torch()
-        if imgs.dtype != torch.uint8 or imgs.dim() != 4 or imgs.shape[3] != 3:
-            raise ValueError("imgs must be a (B,H,W,3) uint8 tensor")
-        if mode not in ("per_image", "global"):
-            raise ValueError("mode must be 'per_image' or 'global'")
+        self._check_args(imgs, mode, dist_group=dist_group, kind="tensor")
         imgs = imgs.contiguous()
         b, h, w, _ = imgs.shape
-        if h < 8 or w < 8:
-            raise ValueError("images must be at least 8x8")
-        check_position_range(self.position_weight, h, w)
-        if self.n_superpixels > 0:
-            self._superpixel_check(h, w, mode, dist_group=dist_group)
-        on_gpu = self.native
-        if on_gpu and imgs.device != self.ops.device:
+        if self.native and imgs.device != self.ops.device:
             raise ValueError(f"imgs live on {imgs.device}, this Segmenter on {self.ops.device}")
         if out is None:
             out = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
@@ -888,24 +1029,12 @@ class Segmenter:
                 or not out.is_contiguous():
             raise ValueError("out must be a contiguous (B,H,W) int32 tensor on the device of imgs")
         g = group or self.group_size(b, h, w, mode)
-        import contextlib
-        # launches go through ctypes on the current stream of self.ops.device: make that device current
-        with (torch.cuda.device(self.ops.device) if on_gpu else contextlib.nullcontext()):
+        with self._device():
             for g0 in range(0, b, g):
                 n = min(g, b - g0)
                 ws = self._workspace(n, h, w, mode) if n == g else self._tail_workspace(n, h, w, mode)
-                self._features(imgs[g0:g0 + n], ws, n, h, w)
-                if self.n_superpixels > 0:                       # SPEC.md §13 instead of §4: features -> canonical tensor -> stage
-                    self._superpixel_stage(ws, n, h, w, out[g0:g0 + n])
-                    if self.n_regions > 0:                       # SPEC.md §14 on the raw §13 map, in place
-                        self._region_stage(ws, n, h, w, out[g0:g0 + n])
-                    continue
-                direct = hasattr(self.ops, "assign_raster")      # the last pass writes the raster map itself
-                lloyd(self.ops, ws["feats"], n, h, w, self.k, self.n_iter, mode, ws["labels"], ws["partials"],
-                      ws["cent"], ws["sums"], dist_group, raster=out[g0:g0 + n] if direct else None, debug=self.debug,
-                      fold=ws.get("fold"))
-                if not direct:
-                    self.ops.labels_widen(ws["labels"], n, h, w, out[g0:g0 + n])
+                _step_features(self.ops, self._opt, ws, imgs[g0:g0 + n], n, h, w)
+                _step_cluster(self.ops, self._opt, ws, out[g0:g0 + n], n, h, w, mode, self.debug, dist_group)
             if self.min_region_size > 0:
                 regions = torch.empty_like(out)
                 self.ops.merge_small_regions(out, self.min_region_size, regions)
@@ -917,11 +1046,14 @@ class Segmenter:
         return out
 
     def _superpixel_check(self, h, w, mode="per_image", out_dtype=None, dist_group=None):
-        """The argument rules of SPEC.md §13 for one image shape, before anything is launched; returns (ny, nx)."""
+        """The argument rules of SPEC.md §13 for one image shape (``h`` None: only those that need no shape), before anything is
+        launched; returns (ny, nx)."""
         if mode != "per_image":
             raise ValueError("n_superpixels > 0: centres are per image, mode must be 'per_image'")
         if dist_group is not None:
             raise ValueError("n_superpixels > 0 does not run over a dist_group")
+        if h is None:
+            return None
         if h > _SP_SIDE_MAX or w > _SP_SIDE_MAX:
             raise ValueError(f"n_superpixels > 0 needs images of at most {_SP_SIDE_MAX} x {_SP_SIDE_MAX} pixels")
         _, ny, nx = superpixel_grid(h, w, self.n_superpixels)
@@ -933,50 +1065,32 @@ class Segmenter:
             raise ValueError(f"out_dtype uint8 cannot hold the {n_labels} labels of this superpixel grid")
         return ny, nx
 
-    def _superpixel_stage(self, ws, b, h, w, out, centres=None):
-        """SPEC.md §13 on the slab ``ws["feats"]`` that ``_features`` has filled: unpack to the canonical tensor, then the one call
-        that enqueues every pass. The buffers join the workspace at first use."""
+    def _superpixel_maps(self, imgs, tree, centres=False):
+        """The step on a (B,H,W,3) uint8 device tensor with SPEC.md §13 as its second piece and no post-passes: the fresh int32 §13
+        map, the workspace (``tree``: the uncut tree of SPEC.md §14 is in its ``"rt"``) and, if asked for, the centres."""
+        torch = _torch()
+        self._check_args(imgs, kind="tensor")
+        imgs = imgs.contiguous()
+        b, h, w, _ = imgs.shape
         _, ny, nx = superpixel_grid(h, w, self.n_superpixels)
-        if "sp" not in ws:
-            ws["sp"] = self.ops.superpixel_buffers(b, h, w, self.n_superpixels)
-        canon, spws = ws["sp"]
-        self.ops.features_unpack(ws["feats"], b, h, w, out=canon)
-        self.ops.superpixels(canon, b, h, w, ny, nx, self.spatial_weight, self.n_iter, out, spws, centres)
-
-    def _region_stage(self, ws, b, h, w, out, cut=True):
-        """SPEC.md §14 behind ``_superpixel_stage``: the tree of the §13 map ``out`` on the canonical tensor that stage left in
-        ``ws["sp"]``, then (``cut``) the cut at ``n_regions`` in place. The buffers join the workspace at first use. Returns them."""
-        _, ny, nx = superpixel_grid(h, w, self.n_superpixels)
-        if "rt" not in ws:
-            ws["rt"] = self.ops.region_tree_buffers(b, h, w, ny * nx)
-        rtws, merges, costs, alive = ws["rt"]
-        self.ops.region_tree(ws["sp"][0], out, b, h, w, ny * nx, rtws, merges, costs, alive)
-        if cut:
-            self.ops.region_tree_cut(out, merges, alive, b, h, w, ny * nx, self.n_regions, out)
-        return merges, costs, alive
+        with self._device():
+            ws = self._tail_workspace(b, h, w, "per_image")
+            _step_features(self.ops, self._opt, ws, imgs, b, h, w)
+            out = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
+            centres = torch.empty((b, ny * nx, self.bank.n_features + 2), dtype=torch.int32, device=imgs.device) if centres else None
+            _step_cluster(self.ops, self._opt, ws, out, b, h, w, "per_image", self.debug, centres=centres, tree=tree)
+        return out, ws, centres
 
     def region_tree_device(self, imgs):
         """(B,H,W,3) uint8 device tensor -> (labels (B,H,W) int32: the §13 map; merges (B, K-1, 2) int32; costs (B, K-1) int64: the
         unsigned 64-bit costs, all below 2^62; alive (B,) int32) of SPEC.md §14, K = ny * nx: no cut, no post-passes. Any
         ``n_regions`` of the plan is ignored; ``cut_regions_device`` cuts the tree at any R for the cost of a relabel."""
-        torch = _torch()
         if self.n_superpixels == 0:
             raise ValueError("region_tree_device needs Segmenter(n_superpixels=n) with n > 0")
         if not hasattr(self.ops, "region_tree"):
             raise ValueError("region_tree_device needs ops that have the region tree")
-        imgs = imgs.contiguous()
-        b, h, w, _ = imgs.shape
-        if h < 8 or w < 8:
-            raise ValueError("images must be at least 8x8")
-        check_position_range(self.position_weight, h, w)
-        self._superpixel_check(h, w)
-        with (torch.cuda.device(self.ops.device) if self.native else contextlib.nullcontext()):
-            ws = self._tail_workspace(b, h, w, "per_image")
-            self._features(imgs, ws, b, h, w)
-            out = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
-            self._superpixel_stage(ws, b, h, w, out)
-            merges, costs, alive = self._region_stage(ws, b, h, w, out, cut=False)
-        return out, merges, costs, alive
+        out, ws, _ = self._superpixel_maps(imgs, tree=True)
+        return (out,) + ws["rt"][1:]
 
     def cut_regions_device(self, labels, merges, alive, R):
         """The cut of SPEC.md §14 at ``R`` (1..4096) of a tree ``region_tree_device`` returned: a fresh (B,H,W) int32 label map with
@@ -987,7 +1101,7 @@ class Segmenter:
             raise ValueError("R must be in 1..4096")
         b, h, w = labels.shape
         out = torch.empty_like(labels)
-        with (torch.cuda.device(self.ops.device) if self.native else contextlib.nullcontext()):
+        with self._device():
             self.ops.region_tree_cut(labels, merges, alive, b, h, w, merges.shape[1] + 1, R, out)
         return out
 
@@ -1011,7 +1125,7 @@ class Segmenter:
         K = merges.shape[1] + 1
         if out is None:
             out = torch.empty_like(labels)
-        with (torch.cuda.device(self.ops.device) if self.native else contextlib.nullcontext()):
+        with self._device():
             # (the workspace comes from and goes back to the stream-ordered allocator: no state a second stream could share)
             self.ops.region_tree_contours(labels, merges, alive, b, h, w, K, self.ops.contour_buffers(b, K), out)
         return out
@@ -1027,54 +1141,22 @@ class Segmenter:
     def superpixels_device(self, imgs):
         """(B,H,W,3) uint8 device tensor -> (labels (B,H,W) int32, centres (B, ny * nx, D + 2) int32: the D features, cy, cx the
         last assign used) of SPEC.md §13, without the post-passes (tests / debugging)."""
-        torch = _torch()
         if self.n_superpixels == 0:
             raise ValueError("superpixels_device needs Segmenter(n_superpixels=n) with n > 0")
-        imgs = imgs.contiguous()
-        b, h, w, _ = imgs.shape
-        if h < 8 or w < 8:
-            raise ValueError("images must be at least 8x8")
-        check_position_range(self.position_weight, h, w)
-        ny, nx = self._superpixel_check(h, w)
-        with torch.cuda.device(self.ops.device):
-            ws = self._tail_workspace(b, h, w, "per_image")
-            self._features(imgs, ws, b, h, w)
-            out = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
-            centres = torch.empty((b, ny * nx, self.bank.n_features + 2), dtype=torch.int32, device=imgs.device)
-            self._superpixel_stage(ws, b, h, w, out, centres)
+        out, _, centres = self._superpixel_maps(imgs, tree=False, centres=True)
         return out, centres
 
-    def _tail_workspace(self, n, h, w, mode):
-        n_sets = n if mode == "per_image" else 1
-        ws = dict(feats=self.ops.feature_slab(n, h, w), labels=self.ops.label_slab(n, h, w),
-                  partials=self.ops.partial_slab(n, h, w, self.k),
-                  cent=self.ops.new_centroids(n_sets, self.k), sums=self.ops.new_sums(n_sets, self.k))
-        if hasattr(self.ops, "fused_workspace"):
-            ws["fold"] = self.ops.fused_workspace(n, h, w, self.k, n_sets)
-        if self.smoothing > 0:
-            ws["smooth"] = self.ops.smooth_scratch(n, h, w)
-        if self.chroma_gain > 0:
-            ws["colour"] = self.ops.colour_scratch(n, h, w)
-        return ws
-
-    def _features(self, imgs, ws, b, h, w):
-        """The transform of SPEC.md §11 when ``chroma_gain`` is on, the Gabor stage into ``ws["feats"]``, then the smoothing of
-        SPEC.md §10 when it is on."""
-        self.ops.gabor_features(self._opponent(imgs, ws["colour"]) if self.chroma_gain > 0 else imgs, ws["feats"])
-        if self.smoothing > 0:
-            self.ops.smooth_features(ws["feats"], b, h, w, scratch=ws["smooth"])
-        self._position(ws["feats"], b, h, w)
-
-    def _position(self, feats, b, h, w, y0=0):
-        """SPEC.md §12 when ``position_weight`` is on: the coordinate planes, written behind the Gabor stage and the smoothing
-        (every entry point has checked the range rule before its first launch). ``y0``: a row strip's first global row."""
-        if self.position_weight > 0:
-            self.ops.position_features(feats, b, h, w, y0=y0)
-
     def _opponent(self, imgs, colour):
-        """T_g of ``imgs`` (SPEC.md §11) into the plan-owned buffer ``colour``; returns it. The caller's tensor is not changed."""
-        self.ops.colour_opponent(imgs, colour)
-        return colour
+        return _opponent(self.ops, imgs, colour)
+
+    def _check_strips(self):
+        """The options the two row-strip entry points refuse."""
+        if self.n_superpixels > 0:
+            raise ValueError("n_superpixels > 0 is not supported on row strips")
+        if self.min_region_size > 0:
+            raise ValueError("min_region_size is not supported on row strips (regions would cross strip boundaries)")
+        if self.smoothing > 0:
+            raise ValueError("smoothing is not supported on row strips (the halo would have to grow by the smoothing radius)")
 
     def shard_rows(self, height, world, rank):
         """``shard_rows`` for THIS plan's bank (its pyramid depth and kernel size decide alignment and halo)."""
@@ -1091,12 +1173,7 @@ class Segmenter:
         the unsharded result. Needs torch.distributed initialised when the image is split.
         """
         torch = _torch()
-        if self.n_superpixels > 0:
-            raise ValueError("n_superpixels > 0 is not supported on row strips")
-        if self.min_region_size > 0:
-            raise ValueError("min_region_size is not supported on row strips (regions would cross strip boundaries)")
-        if self.smoothing > 0:
-            raise ValueError("smoothing is not supported on row strips (the halo would have to grow by the smoothing radius)")
+        self._check_strips()
         strip = strip.contiguous()
         b, hs, w, _ = strip.shape
         if hs < 8 or w < 8:
@@ -1111,9 +1188,8 @@ class Segmenter:
             raise ValueError(f"interior strip edges need {halo} halo rows (use shard_rows)")
         check_position_range(self.position_weight, height, w)
         ws = self._tail_workspace(b, hs, w, "global")
-        # (T_g is per pixel: a strip with its halo rows transforms on its own)
-        self.ops.gabor_features(self._opponent(strip, ws["colour"]) if self.chroma_gain > 0 else strip, ws["feats"])
-        self._position(ws["feats"], b, hs, w, y0=s0)                     # global coordinates: row 0 of the strip is row s0
+        # (T_g is per pixel: a strip with its halo rows transforms on its own; global coordinates: row 0 of the strip is row s0)
+        _step_features(self.ops, self._opt, ws, strip, b, hs, w, y0=s0)
         k, dfeat = self.k, self.bank.n_features
         import torch.distributed as td
         use_dist = td.is_available() and td.is_initialized() and td.get_world_size(dist_group) > 1
@@ -1133,10 +1209,8 @@ class Segmenter:
                 _collective(td.all_reduce, table, op=td.ReduceOp.SUM, group=dist_group)
             cent.copy_(table.to(torch.int16).view(1, k, dfeat))               # wraps back to the uint16 bits
 
-        lloyd(self.ops, ws["feats"], b, hs, w, k, self.n_iter, "global", ws["labels"], ws["partials"],
-              ws["cent"], ws["sums"], dist_group, rows=(r0 - s0, r1 - s0), init=init, debug=self.debug)
         full = torch.empty((b, hs, w), dtype=torch.int32, device=strip.device)
-        self.ops.labels_widen(ws["labels"], b, hs, w, full)
+        _step_cluster(self.ops, self._opt, ws, full, b, hs, w, "global", self.debug, dist_group, rows=(r0 - s0, r1 - s0), init=init)
         res = full[:, r0 - s0:r1 - s0]
         if out is not None:
             out.copy_(res)
@@ -1153,12 +1227,7 @@ class Segmenter:
         (r0, r1) = ``shard_rows(height, world, rank, n_levels, ksize)[:2]``. Every rank must own at least the halo
         (``halo_rows(n_levels, ksize)`` rows), so that a halo comes from ONE neighbour. Returns the (B, r1-r0, W) int32 labels."""
         torch = _torch()
-        if self.n_superpixels > 0:
-            raise ValueError("n_superpixels > 0 is not supported on row strips")
-        if self.min_region_size > 0:
-            raise ValueError("min_region_size is not supported on row strips (regions would cross strip boundaries)")
-        if self.smoothing > 0:
-            raise ValueError("smoothing is not supported on row strips (the halo would have to grow by the smoothing radius)")
+        self._check_strips()
         import torch.distributed as td
         if not (td.is_available() and td.is_initialized()):
             raise RuntimeError("segment_owned_rows_device needs torch.distributed (one rank per row strip)")
@@ -1199,17 +1268,12 @@ class Segmenter:
     def features_device(self, imgs):
         """Canonical (B,D,H,W) uint16 features as an int16 tensor (tests / debugging): what the Lloyd passes consume, smoothed
         when ``smoothing`` is on."""
+        self._check_args(imgs, kind="tensor", cluster=False)
         imgs = imgs.contiguous()
         b, h, w, _ = imgs.shape
-        check_position_range(self.position_weight, h, w)
-        feats = self.ops.feature_slab(b, h, w)
-        if self.chroma_gain > 0:
-            imgs = self._opponent(imgs, self.ops.colour_scratch(b, h, w))
-        self.ops.gabor_features(imgs, feats)
-        if self.smoothing > 0:
-            self.ops.smooth_features(feats, b, h, w)
-        self._position(feats, b, h, w)
-        return self.ops.features_unpack(feats, b, h, w)
+        ws = self._tail_workspace(b, h, w, "per_image", slab_only=True)
+        _step_features(self.ops, self._opt, ws, imgs, b, h, w)
+        return _unpack(self.ops, ws, b, h, w)
 
     # ---- host API: the slot
     def segment_batch(self, imgs: np.ndarray, mode="per_image", out_dtype=np.int32) -> np.ndarray:
@@ -1225,40 +1289,17 @@ class Segmenter:
             imgs = _ImageList(imgs)
         else:
             imgs = np.ascontiguousarray(imgs)
-        if imgs.dtype != np.uint8 or imgs.ndim != 4 or imgs.shape[3] != 3:
-            raise ValueError("imgs must be a (B,H,W,3) uint8 array")
-        if mode not in ("per_image", "global"):
-            raise ValueError("mode must be 'per_image' or 'global'")
-        out_dtype = np.dtype(out_dtype)
-        if out_dtype not in (np.dtype(np.int32), np.dtype(np.uint8)):
-            raise ValueError("out_dtype must be int32 or uint8")
-        if self.connectivity and out_dtype == np.uint8:
-            raise ValueError("connectivity=True needs int32 labels")
-        if self.min_region_size > 0 and out_dtype == np.uint8:
-            raise ValueError("min_region_size > 0 needs int32 labels")
+        out_dtype = self._check_args(imgs, mode, out_dtype)
         b, h, w, _ = imgs.shape
-        if h < 8 or w < 8:
-            raise ValueError("images must be at least 8x8")
-        check_position_range(self.position_weight, h, w)
-        if self.n_superpixels > 0:
-            self._superpixel_check(h, w, mode, out_dtype)
-        dist_on = False
-        if mode == "global":
-            import torch.distributed as td
-            dist_on = td.is_available() and td.is_initialized()
-        # (superpixels: a small call replays its graph like any other; a large one takes the plain path)
-        if not self.native or self.connectivity or self.min_region_size > 0 or dist_on or self.debug.force_collectives \
-                or self.group_size(b, h, w, mode) < b \
-                or (self.n_superpixels > 0 and (b * h * w > _GRAPH_MAX_PIXELS or self.debug.no_graph)):
-            dev = torch.from_numpy(np.asarray(imgs)).to(self.ops.device)   # plain path (test stand-ins, post-passes, collectives)
+        path = self._host_path(b, h, w, mode)
+        if path == "plain":                                        # (test stand-ins, post-passes, collectives, large §13 calls)
+            dev = torch.from_numpy(np.asarray(imgs)).to(self.ops.device)
             return self.segment_device(dev, mode).cpu().numpy().astype(out_dtype, copy=False)
-
-        ops, dev = self.ops, self.ops.device
-        if b * h * w <= _GRAPH_MAX_PIXELS and not self.debug.no_graph:
+        if path == "graph":
             return self._segment_small(imgs, mode, out_dtype)
+        ops, opt, dev = self.ops, self._opt, self.ops.device
         st = self._host_state(b, h, w)
         ws = self._workspace(b, h, w, mode)
-        per_img = ops.lib.gcs_feature_slab_bytes(1, h, w, self.bank.n_scales, self.bank.n_orient)
         cur = torch.cuda.current_stream(dev)
         n_chunks = min(b, 4)
         bounds = [(b * i) // n_chunks for i in range(n_chunks + 1)]
@@ -1279,16 +1320,10 @@ class Segmenter:
                     st["dev_in"][g0:g1].copy_(st["pin_in"][g0:g1], non_blocking=True)
                     st["ev"][i].record(st["copy"])
                 cur.wait_event(st["ev"][i])
-                chunk = st["dev_in"][g0:g1]
-                if self.chroma_gain > 0:                           # (a chunk of 481 x 321 images starts at any byte)
-                    chunk = self._opponent(chunk, ws["colour"][g0:g1])
-                ops.gabor_features(chunk, ws["feats"][g0 * per_img:])
-            if self.smoothing > 0:                                 # every chunk's Gabor stage is in front of it on `cur`
-                ops.smooth_features(ws["feats"], b, h, w, scratch=ws["smooth"])
-            self._position(ws["feats"], b, h, w)                   # once for the batch, behind every chunk's Gabor stage
+                _step_features(ops, opt, ws, st["dev_in"][g0:g1], b, h, w, chunk=(g0, g1))
+            _step_features(ops, opt, ws, None, b, h, w)            # once for the batch, behind every chunk's Gabor stage on `cur`
             dev_out = st["dev_out"] if out_dtype == np.uint8 else st["dev_out32"]
-            lloyd(ops, ws["feats"], b, h, w, self.k, self.n_iter, mode, ws["labels"], ws["partials"],
-                  ws["cent"], ws["sums"], raster=dev_out, debug=self.debug, fold=ws.get("fold"))
+            _step_cluster(ops, opt, ws, dev_out, b, h, w, mode, self.debug)
             # The result is a FRESH pinned host buffer per call, handed to the caller as the base of the returned
             # array (torch's caching host allocator recycles it once the caller drops the array): the device-to-host
             # copy lands directly in caller-owned memory, with no pageable copy and no first-touch page faults.
@@ -1306,19 +1341,8 @@ class Segmenter:
         batch n+1 is copied into pinned memory and uploaded and the labels of batch n-1 are downloaded into a fresh pinned
         array that the caller owns, both by the copy engines (gcs_download: see there). A result is handed out ``depth``
         batches after its input was taken (sooner when the input ends)."""
-        out_dtype = np.dtype(out_dtype)
-        if out_dtype not in (np.dtype(np.int32), np.dtype(np.uint8)):
-            raise ValueError("out_dtype must be int32 or uint8")
-        if mode not in ("per_image", "global"):
-            raise ValueError("mode must be 'per_image' or 'global'")
-        dist_on = False
-        if mode == "global":
-            import torch.distributed as td
-            dist_on = td.is_available() and td.is_initialized()
-        if self.n_superpixels > 0 and mode != "per_image":
-            raise ValueError("n_superpixels > 0: centres are per image, mode must be 'per_image'")
-        if not self.native or self.connectivity or self.min_region_size > 0 or dist_on or self.debug.force_collectives \
-                or self.n_superpixels > 0:
+        out_dtype = self._check_args(None, mode, out_dtype)
+        if not self._may_pipeline(mode):
             for imgs in batches:                                   # no pipeline for post-passes / collectives / stand-ins / §13
                 yield self.segment_batch(imgs, mode, out_dtype)
             return
@@ -1342,53 +1366,20 @@ class Segmenter:
         ent = self._graphs.get(key)
         with torch.cuda.device(dev):
             if ent is None:
-                ws = self._tail_workspace(b, h, w, mode)
+                # every buffer the graph touches belongs to the entry (all allocated here, outside the capture)
+                ws = self._tail_workspace(b, h, w, mode, private=out_dtype)
                 dev_in = torch.empty((b, h, w, 3), dtype=torch.uint8, device=dev)
                 dev_out = torch.empty((b, h, w), dtype=torch.uint8 if out_dtype == np.uint8 else torch.int32, device=dev)
-                # SPEC.md §13: the canonical tensor, the stage's workspace and its int32 label map belong to the entry too
-                sp = None
-                if self.n_superpixels > 0:
-                    sp = self.ops.superpixel_buffers(b, h, w, self.n_superpixels) + superpixel_grid(h, w, self.n_superpixels)[1:] \
-                        + (self.spatial_weight, dev_out if out_dtype != np.uint8 else torch.empty((b, h, w), dtype=torch.int32, device=dev))
-                # SPEC.md §14: the tree's workspace and outputs, and R (None: the stage is off)
-                rt = None
-                if self.n_regions > 0:
-                    rt = self.ops.region_tree_buffers(b, h, w, sp[2] * sp[3]) + (self.n_regions,)
                 pin_in = torch.empty((b, h, w, 3), dtype=torch.uint8, pin_memory=True)
-                # the graph bakes raw pointers in: every buffer it touches, the Gabor scratch included, belongs to the
-                # entry and lives exactly as long as the graph does (the shared scratch of HipOps is replaced, and its
-                # block recycled, whenever a later call needs a larger one)
-                scratch = self.ops.gabor_scratch(b, h, w)
-                smooth = ws.get("smooth")                  # (allocated with the workspace, outside the capture)
-                colour = ws.get("colour")                  # (the same: SPEC.md §11's transformed batch)
 
                 # (the closure must not capture `self`: the entry lives in self._graphs, and a Segmenter inside a reference
                 # cycle is freed - with its graphs, streams, pinned and device buffers - only when the cyclic collector
                 # happens to run, not when the last user drops it)
-                ops, k, n_iter, debug = self.ops, self.k, self.n_iter, self.debug
-                position = self.position_weight > 0
+                ops, opt, debug = self.ops, self._opt, self.debug
 
                 def step():
-                    if colour is not None:
-                        ops.colour_opponent(dev_in, colour)
-                    ops.gabor_features(dev_in if colour is None else colour, ws["feats"], scratch=scratch)
-                    if smooth is not None:
-                        ops.smooth_features(ws["feats"], b, h, w, scratch=smooth)
-                    if position:
-                        ops.position_features(ws["feats"], b, h, w)
-                    if sp is not None:
-                        canon, spws, ny, nx, lam, out32 = sp
-                        ops.features_unpack(ws["feats"], b, h, w, out=canon)
-                        ops.superpixels(canon, b, h, w, ny, nx, lam, n_iter, out32, spws)
-                        if rt is not None:
-                            rtws, merges, costs, alive, n_regions = rt
-                            ops.region_tree(canon, out32, b, h, w, ny * nx, rtws, merges, costs, alive)
-                            ops.region_tree_cut(out32, merges, alive, b, h, w, ny * nx, n_regions, out32)
-                        if out32 is not dev_out:
-                            dev_out.copy_(out32)           # (K, or min(K, R), <= 256 was checked: the narrowing keeps every label)
-                        return
-                    lloyd(ops, ws["feats"], b, h, w, k, n_iter, mode, ws["labels"], ws["partials"], ws["cent"],
-                          ws["sums"], raster=dev_out, debug=debug, fold=ws.get("fold"))
+                    _step_features(ops, opt, ws, dev_in, b, h, w)
+                    _step_cluster(ops, opt, ws, dev_out, b, h, w, mode, debug)
                 dev_in.zero_()
                 step()                                     # eager once: first-use work (side-stream creation) outside the capture
                 # (a STREAM wait - the step joins its side stream back into this one: a device-wide synchronize is refused while
@@ -1402,7 +1393,8 @@ class Segmenter:
                     _CAPTURES.fell_back(key, "torch.cuda.graph raised RuntimeError")
                     graph = None
                     torch.cuda.current_stream(dev).synchronize()
-                ent = dict(graph=graph, step=step, ws=ws, dev_in=dev_in, dev_out=dev_out, pin_in=pin_in, scratch=scratch, sp=sp, rt=rt)
+                ent = dict(graph=graph, step=step, ws=ws, dev_in=dev_in, dev_out=dev_out, pin_in=pin_in, scratch=ws["scratch"],
+                           rt=ws.get("rt"))          # (the tree buffers of SPEC.md §14, None when that stage is off)
                 if len(self._graphs) >= 4:                 # evicted plans leave through the guard: never inside an open capture
                     _CAPTURES.retire([self._graphs.pop(next(iter(self._graphs)))])
                 self._graphs[key] = ent
@@ -1466,15 +1458,10 @@ class Segmenter:
         batch = int(batch)
         if batch < 1:
             raise ValueError("batch must be >= 1")
-        out_dtype = np.dtype(out_dtype)
-        if out_dtype not in (np.dtype(np.int32), np.dtype(np.uint8)):
-            raise ValueError("out_dtype must be int32 or uint8")
+        out_dtype = self._check_args(None, "per_image", out_dtype)
         groups, ready, nxt = {}, {}, 0
         pipes, tags = {}, {}                   # per shape: the pipeline of its FULL batches and the image indices in flight
-        if self.min_region_size > 0 and out_dtype == np.uint8:
-            raise ValueError("min_region_size > 0 needs int32 labels")
-        piped = self.native and not self.connectivity and self.min_region_size == 0 and not self.debug.force_collectives \
-            and self.n_superpixels == 0
+        piped = self._may_pipeline("per_image")
 
         def emit(idx, labels):
             for i, lab in zip(idx, labels):
@@ -1549,12 +1536,11 @@ class _StreamPipe:
         self.n = 0
         self.pending = []                                          # (download event, result array) in input order
 
-    def _open(self, b, h, w):
+    def _open(self, imgs):
         torch = _torch()
         seg, dev, n_slots = self.seg, self.seg.ops.device, self.n_slots
-        if h < 8 or w < 8:
-            raise ValueError("images must be at least 8x8")
-        check_position_range(seg.position_weight, h, w)
+        b, h, w, _ = imgs.shape
+        seg._check_args(imgs, self.mode)                           # (once per stream; out_dtype: the entry point has checked it)
         if seg.group_size(b, h, w, self.mode) < b:
             raise ValueError("batch too large for one feature slab: use smaller batches")
         self.shape = (b, h, w)
@@ -1593,7 +1579,7 @@ class _StreamPipe:
         b, h, w, _ = imgs.shape
         with torch.cuda.device(dev):
             if self.st is None:
-                self._open(b, h, w)
+                self._open(imgs)
             elif (b, h, w) != self.shape:
                 raise ValueError(f"batch {self.n} has shape {(b, h, w)}, the stream was opened with {self.shape}")
             st, ws, n, n_slots = self.st, self.ws, self.n, self.n_slots
@@ -1610,13 +1596,8 @@ class _StreamPipe:
             cur.wait_event(st["ev_up"][i])
             if n >= n_slots:
                 cur.wait_event(st["ev_down"][i])                   # dev_out[i] has been downloaded
-            ops.gabor_features(seg._opponent(st["dev_in"][i], ws["colour"]) if seg.chroma_gain > 0 else st["dev_in"][i],
-                               ws["feats"])
-            if seg.smoothing > 0:
-                ops.smooth_features(ws["feats"], b, h, w, scratch=ws["smooth"])
-            seg._position(ws["feats"], b, h, w)
-            lloyd(ops, ws["feats"], b, h, w, seg.k, seg.n_iter, self.mode, ws["labels"], ws["partials"], ws["cent"],
-                  ws["sums"], raster=st["dev_out"][i], debug=seg.debug, fold=ws.get("fold"))
+            _step_features(ops, seg._opt, ws, st["dev_in"][i], b, h, w)
+            _step_cluster(ops, seg._opt, ws, st["dev_out"][i], b, h, w, self.mode, seg.debug)
             st["ev_done"][i].record(cur)
             land = torch.empty((b, h, w), dtype=self.t_dtype, pin_memory=True)   # caller-owned; torch recycles it once dropped
             with torch.cuda.stream(st["down"]):

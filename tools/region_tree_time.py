@@ -48,6 +48,7 @@ def _median_ms(torch, fn, reps=REPS, warm=WARM):
 def _setup(torch):
     """The plan, the batch's canonical features and superpixel maps, and the same for a constant batch."""
     from gabor_color_image_segmentation_amd import Segmenter, superpixel_grid
+    from gabor_color_image_segmentation_amd.segmenter import _step_cluster, _step_features
     from gabor_color_image_segmentation_amd.synthetic import synthetic_batch
     imgs = torch.from_numpy(synthetic_batch(BATCH, H, W, seed=0)).cuda()
     seg = Segmenter(n_superpixels=N, spatial_weight=LAM, n_regions=R, **BANK)
@@ -55,9 +56,9 @@ def _setup(torch):
     cases = {}
     for name, batch in (("real", imgs), ("constant", torch.full_like(imgs, 128))):
         ws = seg._tail_workspace(BATCH, H, W, "per_image")
-        seg._features(batch, ws, BATCH, H, W)
+        _step_features(seg.ops, seg._opt, ws, batch, BATCH, H, W)
         lab = torch.empty((BATCH, H, W), dtype=torch.int32, device="cuda")
-        seg._superpixel_stage(ws, BATCH, H, W, lab)
+        _step_cluster(seg.ops, seg._opt, ws, lab, BATCH, H, W, "per_image", seg.debug, tree=False)      # the §13 map alone
         cases[name] = (ws["sp"][0], lab, seg.ops.region_tree_buffers(BATCH, H, W, ny * nx))
     return seg, imgs, ny * nx, cases
 

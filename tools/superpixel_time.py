@@ -38,6 +38,7 @@ def main(batch=64, h=481, w=321, n=300, lam=576, reps=25, warm=4):
     sys.path.insert(0, ROOT)
     import torch
     from gabor_color_image_segmentation_amd import Segmenter, superpixel_grid
+    from gabor_color_image_segmentation_amd.segmenter import _step_features
     from gabor_color_image_segmentation_amd.synthetic import synthetic_batch
     bank = dict(n_orient=5, color_weight=0.125, chroma_gain=4)
     imgs = torch.from_numpy(synthetic_batch(batch, h, w, seed=0)).cuda()
@@ -45,7 +46,7 @@ def main(batch=64, h=481, w=321, n=300, lam=576, reps=25, warm=4):
     ops, d = seg.ops, seg.bank.n_features
     s, ny, nx = superpixel_grid(h, w, n)
     ws = seg._workspace(batch, h, w, "per_image")
-    seg._features(imgs, ws, batch, h, w)
+    _step_features(ops, seg._opt, ws, imgs, batch, h, w)
     canon, spws = ops.superpixel_buffers(batch, h, w, n)
     out = torch.empty((batch, h, w), dtype=torch.int32, device="cuda")
     res = dict(batch=batch, shape=[h, w], n_superpixels=n, spatial_weight=lam, S=s, grid=[ny, nx], D=d, n_iter=seg.n_iter, reps=reps,
