@@ -35,7 +35,10 @@ boundary recall, precision, F, PRI, VoI, covering and regions; `--superpixels 30
 `--regions R[,R...] --sweep`: boundary recall, precision and F of every listed R from ONE contour map per batch (SPEC.md §15:
 `Segmenter.contour_map_device`) and one pass over it (`evaluate_gpu.boundary_sweep_resident`) instead of a cut and a scorer call per R,
 then OIS (every image at its own best R) and ODS (one R for the whole set) over the list; the map describes the raw cuts, so
-`--min-region-size` is not applied. Without `--sweep` the per-cut path above stays: the region metrics need it.
+`--min-region-size` is not applied.
+`--regions R[,R...] --sweep --agreement`: PRI, VoI and covering columns beside them, from the same tree (SPEC.md §16: the contingency
+tables of the superpixels once per batch, the table of every cut from the merge list, `evaluate_gpu.region_sweep_resident`), and the ODS /
+OIS of each of the three (VoI: the lowest). Without `--sweep` the per-cut path above stays: `--min-region-size` needs the label maps.
 """
 import os
 import sys
@@ -175,33 +178,42 @@ def region_rows(n, lam, n_orient, cw, g, merge, regions):
             "%.4f" % float(np.mean([x[k] for x in rows[r]])) for k in keys), float(np.mean([x["regions"] for x in rows[r]]))))
 
 
-def sweep_rows(n, lam, n_orient, cw, g, regions):
+def sweep_rows(n, lam, n_orient, cw, g, regions, agreement=False):
     import numpy as np
     import torch
     from gabor_color_image_segmentation_amd import Segmenter
     from gabor_color_image_segmentation_amd.evaluate import ods_ois
-    from gabor_color_image_segmentation_amd.evaluate_gpu import boundary_sweep_resident, sweep_scores
+    from gabor_color_image_segmentation_amd.evaluate_gpu import boundary_sweep_resident, region_sweep_resident, sweep_agreement, sweep_scores
     from gabor_color_image_segmentation_amd.groundtruth import PackedTruth
     gold = os.path.join(ROOT, "tests", "golden")
     pack = np.load(os.path.join(gold, "bsd_val_images.npz"))
     truth = PackedTruth(os.path.join(gold, "bsd500_truth.npz"))
     ids = [str(i) for i in pack["ids"]]
     seg = Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, n_superpixels=n, spatial_weight=lam)
-    rows = []
+    rows, agree = [], []
     for shape in sorted({pack["img_" + i].shape[:2] for i in ids}):
         group = [i for i in ids if pack["img_" + i].shape[:2] == shape]
-        contours, alive = seg.contours_device(torch.from_numpy(np.stack([pack["img_" + i] for i in group])).cuda())
+        labels, merges, _, alive = seg.region_tree_device(torch.from_numpy(np.stack([pack["img_" + i] for i in group])).cuda())
+        contours = seg.contour_map_device(labels, merges, alive)
         dt = truth.to_device(group)                      # one map and one pass over it per batch, whatever the number of R
         rows += sweep_scores(boundary_sweep_resident(contours, alive, dt), alive.cpu().numpy(), dt.bd_counts.cpu().numpy(), dt.first,
                              regions)
-    print("| n | lambda | n_orient | w | g | R | R | P | F |")
-    print("|---|---|---|---|---|---|---|---|---|")
+        if agreement:                                    # the leaf tables once, every coarser table from the merge list (SPEC.md §16)
+            agree += sweep_agreement(*region_sweep_resident(labels, merges, alive, dt, regions), dt.first, shape[0] * shape[1], regions)
+    keys = ("recall", "precision", "fmeasure") + (("PRI", "VoI", "covering") if agreement else ())
+    if agreement:
+        rows = [[dict(s, **a) for s, a in zip(row, arow)] for row, arow in zip(rows, agree)]
+    print("| n | lambda | n_orient | w | g | R | R | P | F |" + (" PRI | VoI | covering |" if agreement else ""))
+    print("|---|---|---|---|---|---|---|---|---|" + ("---|---|---|" if agreement else ""))
     for j, r in enumerate(regions):
         print("| %d | %d | %d | %g | %d | %d | %s |" % (n, lam, n_orient, cw, g, r, " | ".join(
-            "%.4f" % float(np.mean([row[j][k] for row in rows])) for k in ("recall", "precision", "fmeasure"))))
+            "%.4f" % float(np.mean([row[j][k] for row in rows])) for k in keys)))
     best = ods_ois([[s["fmeasure"] for s in row] for row in rows], regions)
     print("ODS %.4f at R = %d   OIS %.4f   (%d images, R in %s)" % (best["ODS"], best["ODS_regions"], best["OIS"], len(rows),
                                                                     ",".join(str(r) for r in regions)))
+    for key in keys[3:]:                                 # VoI: lower is better
+        best = ods_ois([[s[key] for s in row] for row in rows], regions, best="min" if key == "VoI" else "max")
+        print("%-8s ODS %.4f at R = %d   OIS %.4f" % (key, best["ODS"], best["ODS_regions"], best["OIS"]))
 
 
 if __name__ == '__main__':
@@ -211,7 +223,7 @@ if __name__ == '__main__':
         if "--regions" in sys.argv and "--sweep" in sys.argv:
             sweep_rows(one("--superpixels", int, 300), one("--spatial-weight", int, 576), one("--n-orient", int, 6),
                        one("--color-weight", float, 0.0), one("--chroma-gain", int, 0),
-                       [int(v) for v in one("--regions", str, "8").split(",")])
+                       [int(v) for v in one("--regions", str, "8").split(",")], agreement="--agreement" in sys.argv)
             sys.exit(0)
         if "--regions" in sys.argv:
             region_rows(one("--superpixels", int, 300), one("--spatial-weight", int, 576), one("--n-orient", int, 6),

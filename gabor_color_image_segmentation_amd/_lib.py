@@ -78,6 +78,8 @@ SIGNATURES = {
     "gcs_region_tree_contours_workspace_bytes": (_sz, [_i, _i]),
     "gcs_region_tree_contours": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "gcs_boundary_sweep_resident": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "gcs_region_sweep_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "gcs_region_sweep": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
 }
 
 

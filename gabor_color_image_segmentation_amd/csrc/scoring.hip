@@ -963,22 +963,19 @@ __device__ __forceinline__ V ag_wave_sum(V v) {
     return v;
 }
 
-__global__ __launch_bounds__(AG_THREADS) void region_agreement_kernel(const unsigned *__restrict__ hist,
-                                                                      const int32_t *__restrict__ img_of,
-                                                                      const int32_t *__restrict__ seg_max, int n_seg,
-                                                                      int stride, unsigned *__restrict__ scratch,
-                                                                      unsigned long long *__restrict__ sums,
-                                                                      double *__restrict__ terms) {
+// The reduction of ONE table h [.][stride], rows 0 .. rows-1, by the whole workgroup (AG_THREADS threads, all of them call it): a_s
+// [rows] and b_s [stride] are the table's scratch, out_sums [4] / out_terms [4] its outputs. Shared by region_agreement_kernel (one
+// table per workgroup) and region_sweep_kernel (one table per workgroup and cut). Ends with the outputs written by threads 0 .. 7; a
+// caller that calls it again puts a __syncthreads() in between.
+__device__ __forceinline__ void ag_table_reduce(const unsigned *__restrict__ h, int rows, int stride, unsigned *__restrict__ a_s,
+                                                unsigned *__restrict__ b_s, unsigned long long *__restrict__ out_sums,
+                                                double *__restrict__ out_terms) {
     __shared__ unsigned s_w[2][AG_WAVES][AG_CHUNK];            // sweep 1: [0] column sums; sweep 2: [0] best n, [1] best u
     __shared__ unsigned s_b[AG_CHUNK];
     __shared__ unsigned long long s_u[AG_WAVES][4];
     __shared__ double s_d[AG_WAVES][4];
-    const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     static_assert(AG_ROWS <= 64, "one lane per row of a step");
-    int rows = n_seg;
-    if (seg_max) rows = min(n_seg, max(0, seg_max[img_of ? img_of[t] : 0] + 1));
-    const unsigned *h = hist + (size_t)t * n_seg * stride;
-    unsigned *a_s = scratch + (size_t)t * (n_seg + stride), *b_s = a_s + n_seg;
     unsigned long long n_tot = 0, sa2 = 0, sb2 = 0, sn2 = 0;
     double sal = 0.0, sbl = 0.0, snl = 0.0, cov = 0.0;
 
@@ -1122,13 +1119,26 @@ __global__ __launch_bounds__(AG_THREADS) void region_agreement_kernel(const unsi
         if (tid < 4) {
             unsigned long long v = 0;
             for (int w = 0; w < AG_WAVES; ++w) v += s_u[w][k];
-            sums[(size_t)t * 4 + k] = v;
+            out_sums[k] = v;
         } else {
             double v = 0.0;
             for (int w = 0; w < AG_WAVES; ++w) v += s_d[w][k];
-            terms[(size_t)t * 4 + k] = v;
+            out_terms[k] = v;
         }
     }
+}
+
+__global__ __launch_bounds__(AG_THREADS) void region_agreement_kernel(const unsigned *__restrict__ hist,
+                                                                      const int32_t *__restrict__ img_of,
+                                                                      const int32_t *__restrict__ seg_max, int n_seg,
+                                                                      int stride, unsigned *__restrict__ scratch,
+                                                                      unsigned long long *__restrict__ sums,
+                                                                      double *__restrict__ terms) {
+    const int t = blockIdx.x;
+    int rows = n_seg;
+    if (seg_max) rows = min(n_seg, max(0, seg_max[img_of ? img_of[t] : 0] + 1));
+    unsigned *a_s = scratch + (size_t)t * (n_seg + stride);
+    ag_table_reduce(hist + (size_t)t * n_seg * stride, rows, stride, a_s, a_s + n_seg, sums + (size_t)t * 4, terms + (size_t)t * 4);
 }
 
 extern "C" size_t gcs_region_agreement_scratch_bytes(int T, int n_segments, int n_truth_labels) {
@@ -1146,5 +1156,165 @@ extern "C" int gcs_region_agreement(const uint32_t *hist, const int32_t *img_of,
     hipLaunchKernelGGL(region_agreement_kernel, dim3(T), dim3(AG_THREADS), 0, stream, hist, img_of, seg_max, n_segments,
                        n_truth_labels, static_cast<unsigned *>(scratch), reinterpret_cast<unsigned long long *>(sums), terms);
     GCS_CHECK_LAUNCH("gcs_region_agreement");
+    return GCS_OK;
+}
+
+// ================================================= region metrics of every cut of a region tree at once (SPEC.md §16)
+// Every group of a cut is a union of superpixels, so its row of the contingency table is the sum of its superpixels' rows: the leaf
+// tables (gcs_region_counts_batch[_u8] with n_segments = K) are made once from the pixels and every coarser table follows from the
+// merge list by adding rows. ONE workgroup per annotator map t of image b = img_of[t], the requested cuts in their (decreasing) order
+// of R, so the table only ever gets coarser and is coarsened IN PLACE:
+//   1. death[q] = the row that absorbs label q, with its absorber (one LDS word, (row << 12) | absorber). A row counts when it has
+//      0 <= a < b < K and both are reps at that step; which rows count depends on the rows before them only, so the rule is iterated
+//      from "every well-formed row counts" until nothing changes (a list gcs_region_tree wrote: the first check already agrees; any
+//      list: at most K - 1 rounds, row t is settled after round t + 1). No serial walk over the rows.
+//   2. per cut, tau = max(0, alive - R): parent[q] = death[q] < tau ? absorber : q, pointer jumping (ceil(log2 K) rounds) gives every
+//      label's group rep; the rows absorbed since the previous cut (tau_prev <= death < tau) are added into their rep's row, element
+//      by element with integer atomics (exact in any order; a rep is never absorbed in the same cut, so no row is read and written),
+//      and emptied.
+//   3. the table is reduced by ag_table_reduce, the function gcs_region_agreement runs: every float sum in an order fixed by the
+//      table indices alone, no running float sums carried from cut to cut.
+constexpr int RS_K_MAX = 4096, RS_CUTS_MAX = 64, RS_PER = RS_K_MAX / AG_THREADS, RS_UNROLL = 4;
+constexpr unsigned RS_NONE = 0xffffffffu;                      // never absorbed: its row field is above every row index
+
+__global__ __launch_bounds__(AG_THREADS) void region_sweep_kernel(unsigned *hist, const int32_t *__restrict__ merges,
+                                                                  const int32_t *__restrict__ alive_p,
+                                                                  const int32_t *__restrict__ img_of,
+                                                                  const int32_t *__restrict__ regions, int B, int T, int K, int stride,
+                                                                  int n_cuts, unsigned *scratch, unsigned long long *sums,
+                                                                  double *terms) {
+    __shared__ unsigned s_dk[RS_K_MAX];
+    __shared__ unsigned short s_root[RS_K_MAX];
+    __shared__ int s_changed;
+    const int t = blockIdx.x, tid = threadIdx.x;
+    const int b = img_of[t];
+    const bool img_ok = (unsigned)b < (unsigned)B;             // an image index outside the batch: the leaf table at every cut
+    unsigned *h = hist + (size_t)t * K * stride;
+    unsigned *a_s = scratch + (size_t)t * (K + stride), *b_s = a_s + K;
+    const int alive = img_ok ? alive_p[b] : 0;
+    const int n_rows = img_ok ? K - 1 : 0;
+    const int32_t *rows = merges + (img_ok ? (size_t)b * (K - 1) * 2 : 0);   // (not read with n_rows = 0: NULL with K = 1)
+
+    // ---- 1. which rows count, and what absorbs every label
+    int ra[RS_PER], rc[RS_PER];
+    unsigned formed = 0;
+#pragma unroll
+    for (int j = 0; j < RS_PER; ++j) {
+        const int r = tid + j * AG_THREADS;
+        ra[j] = rc[j] = 0;
+        if (r < n_rows) {
+            ra[j] = rows[2 * r];
+            rc[j] = rows[2 * r + 1];
+            if (ra[j] >= 0 && ra[j] < rc[j] && rc[j] < K) formed |= 1u << j;
+        }
+    }
+    unsigned counted = formed;
+    for (;;) {
+        for (int q = tid; q < K; q += AG_THREADS) s_dk[q] = RS_NONE;
+        if (tid == 0) s_changed = 0;
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < RS_PER; ++j)
+            if ((counted >> j) & 1u) atomicMin(&s_dk[rc[j]], ((unsigned)(tid + j * AG_THREADS) << 12) | (unsigned)ra[j]);
+        __syncthreads();
+        unsigned now = 0;
+#pragma unroll
+        for (int j = 0; j < RS_PER; ++j) {
+            const unsigned r = (unsigned)(tid + j * AG_THREADS);
+            if (((formed >> j) & 1u) && (s_dk[ra[j]] >> 12) >= r && (s_dk[rc[j]] >> 12) >= r) now |= 1u << j;
+        }
+        if (now != counted) s_changed = 1;                     // (every writer stores the same value)
+        counted = now;
+        __syncthreads();
+        const int changed = s_changed;
+        __syncthreads();                                       // everyone has read the flag before the next round clears it
+        if (!changed) break;
+    }
+
+    // ---- 2. and 3. per cut: coarsen the table in place, reduce it
+    const int LV = K > 1 ? 32 - __builtin_clz((unsigned)(K - 1)) : 0;       // ceil(log2 K): a chain has at most K - 1 links
+    const long long cells = (long long)K * stride;
+    int tau_prev = 0;
+    for (int ci = 0; ci < n_cuts; ++ci) {
+        const long long want = (long long)alive - (long long)regions[ci];
+        const int tau = (int)(want < 0 ? 0 : want > n_rows ? n_rows : want);
+        if (tau > tau_prev) {                                  // (a list that is not decreasing never un-merges: no launch can check it)
+            for (int q = tid; q < K; q += AG_THREADS) {
+                const unsigned d = s_dk[q];
+                s_root[q] = (d >> 12) < (unsigned)tau ? (unsigned short)(d & 0xfffu) : (unsigned short)q;
+            }
+            __syncthreads();
+            for (int it = 0; it < LV; ++it) {
+                unsigned short pp[RS_PER];
+#pragma unroll
+                for (int j = 0; j < RS_PER; ++j) {
+                    const int q = tid + j * AG_THREADS;
+                    pp[j] = q < K ? s_root[s_root[q]] : (unsigned short)0;
+                }
+                __syncthreads();
+#pragma unroll
+                for (int j = 0; j < RS_PER; ++j) {
+                    const int q = tid + j * AG_THREADS;
+                    if (q < K) s_root[q] = pp[j];
+                }
+                __syncthreads();
+            }
+            // the cells of the rows absorbed in this cut, RS_UNROLL of them per thread with their loads in flight together
+            for (long long i0 = tid; i0 < cells; i0 += (long long)AG_THREADS * RS_UNROLL) {
+                unsigned v[RS_UNROLL];
+                long long dst[RS_UNROLL];
+#pragma unroll
+                for (int u = 0; u < RS_UNROLL; ++u) {
+                    const long long i = i0 + (long long)u * AG_THREADS;
+                    v[u] = 0u;
+                    dst[u] = 0;
+                    if (i < cells) {
+                        const int q = (int)(i / stride);
+                        const unsigned d = s_dk[q] >> 12;
+                        if (d >= (unsigned)tau_prev && d < (unsigned)tau) {
+                            v[u] = h[i];
+                            dst[u] = i + ((long long)s_root[q] - q) * stride;
+                        }
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < RS_UNROLL; ++u)
+                    if (v[u]) {
+                        atomicAdd(&h[dst[u]], v[u]);
+                        h[i0 + (long long)u * AG_THREADS] = 0u;
+                    }
+            }
+            tau_prev = tau;
+        }
+        __syncthreads();                                       // (with its workgroup-scope fences: this workgroup's atomics and stores
+                                                               // are visible to its own loads below; nobody else reads the table)
+        ag_table_reduce(h, K, stride, a_s, b_s, sums + ((size_t)ci * T + t) * 4, terms + ((size_t)ci * T + t) * 4);
+        __syncthreads();
+    }
+}
+
+static bool region_sweep_shape_ok(int T, int K, int n_truth_labels, int n_cuts) {
+    return T >= 1 && T <= 1000000 && K >= 1 && K <= RS_K_MAX && n_truth_labels >= 1 && n_cuts >= 1 && n_cuts <= RS_CUTS_MAX &&
+           (long long)T * K * n_truth_labels < 0x80000000LL;
+}
+
+extern "C" size_t gcs_region_sweep_workspace_bytes(int T, int K, int n_truth_labels, int n_cuts) {
+    if (!region_sweep_shape_ok(T, K, n_truth_labels, n_cuts)) return 0;
+    return (size_t)T * ((size_t)K + n_truth_labels) * sizeof(uint32_t);    // per map: the row and column sums of the table in hand
+}
+
+extern "C" int gcs_region_sweep(uint32_t *leaf_hist, const int32_t *merges, const int32_t *alive, const int32_t *img_of,
+                                const int32_t *regions, int B, int T, int K, int n_truth_labels, int n_cuts, void *workspace,
+                                uint64_t *sums_out, double *terms_out, gcs_stream_t stream) {
+    if (!leaf_hist || !alive || !img_of || !regions || !workspace || !sums_out || !terms_out || (K > 1 && !merges))
+        return gcs_fail(GCS_EINVAL, "gcs_region_sweep: NULL pointer");
+    if (B < 1 || B > 65535 || T < 1 || T > 1000000 || K < 1 || K > RS_K_MAX || n_truth_labels < 1 || n_cuts < 1 || n_cuts > RS_CUTS_MAX)
+        return gcs_fail(GCS_EINVAL, "gcs_region_sweep: bad shape (1 <= B <= 65535, 1 <= T <= 1000000, 1 <= K <= 4096, 1 <= n_cuts <= 64)");
+    if (!region_sweep_shape_ok(T, K, n_truth_labels, n_cuts))
+        return gcs_fail(GCS_EINVAL, "gcs_region_sweep: T * K * n_truth_labels must be below 2^31");
+    hipLaunchKernelGGL(region_sweep_kernel, dim3(T), dim3(AG_THREADS), 0, stream, leaf_hist, merges, alive, img_of, regions, B, T, K,
+                       n_truth_labels, n_cuts, static_cast<unsigned *>(workspace), reinterpret_cast<unsigned long long *>(sums_out),
+                       terms_out);
+    GCS_CHECK_LAUNCH("gcs_region_sweep");
     return GCS_OK;
 }

@@ -216,10 +216,14 @@ def region_agreement(labels, segments_truth) -> dict:
 
 # ---- the whole hierarchy at once (SPEC.md §15)
 
-def ods_ois(f_table, regions) -> dict:
+def ods_ois(f_table, regions, best="max") -> dict:
     """``f_table[b][j]`` = F of image b at ``regions[j]`` -> ``{"OIS", "ODS", "ODS_regions", "OIS_regions"}``: OIS = the mean over the
     images of each image's best F, ODS = the best mean F of one R for the whole set (on ties the smallest R), ``OIS_regions`` = each
-    image's best R (smallest on ties). Plain Python floats, summed in image order."""
+    image's best R (smallest on ties). Plain Python floats, summed in image order. ``best="min"``: the best score is the lowest one
+    (VoI, SPEC.md §16); ties still go to the smallest R."""
+    if best not in ("max", "min"):
+        raise ValueError('best must be "max" or "min"')
+    pick = max if best == "max" else min                                   # both keep the first of equals
     regions = [int(r) for r in regions]
     rows = [[float(v) for v in row] for row in f_table]
     if not rows or not regions or any(len(row) != len(regions) for row in rows):
@@ -227,7 +231,7 @@ def ods_ois(f_table, regions) -> dict:
     order = sorted(range(len(regions)), key=lambda j: regions[j])           # ties go to the smallest R: visit R in increasing order
     best_r, ois = [], 0.0
     for row in rows:
-        j = max(order, key=lambda q: row[q])                               # max keeps the first of equals
+        j = pick(order, key=lambda q: row[q])                              # max / min keep the first of equals
         best_r.append(regions[j])
         ois += row[j]
     means = []
@@ -236,5 +240,5 @@ def ods_ois(f_table, regions) -> dict:
         for row in rows:
             m += row[j]
         means.append(m / len(rows))
-    jd = max(order, key=lambda q: means[q])
+    jd = pick(order, key=lambda q: means[q])
     return {"OIS": ois / len(rows), "ODS": means[jd], "ODS_regions": regions[jd], "OIS_regions": best_r}

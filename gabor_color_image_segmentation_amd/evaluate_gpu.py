@@ -575,3 +575,81 @@ def sweep_scores(hists, alive, bd_counts, first, regions) -> list:
         t0, t1 = int(first[i]), int(first[i + 1])
         out.append([scores_from_counts(np.concatenate([c[i:i + 1], c[b + 3 * t0:b + 3 * t1]])) for c in counts])
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# The region metrics of every cut of a region tree at once (SPEC.md §16): the leaf tables from one pass over the pixels, every
+# coarser table from the merge list by adding rows.
+
+SWEEP_CUTS = 64                                                  # the most cuts one gcs_region_sweep call takes
+
+
+def region_sweep_resident(labels, merges, alive, truth: DeviceTruth, regions):
+    """labels (B,H,W) int32, merges (B, K-1, 2) int32, alive (B,) int32: the device tensors ``Segmenter.region_tree_device`` returned;
+    truth: the resident ground truth of the same images; regions: 1 .. 64 distinct integers in 1 .. 4096, in any order. Returns host
+    arrays ``(sums uint64 [len(regions)][T][4], terms float64 [len(regions)][T][4])`` in the caller's order of ``regions``: per cut and
+    annotator map what gcs_region_agreement writes for the contingency table of ``cut_regions_device(labels, merges, alive, R)``
+    (the raw cuts: ``connectivity`` and ``min_region_size`` are not reflected). Two launches (the leaf tables with K rows; the
+    sweep) and one download. Buffers of its own: ``truth``'s result block and its one-submission rule are not touched."""
+    import torch
+    if labels.dtype != torch.int32 or labels.dim() != 3:
+        raise ValueError("labels must be a (B,H,W) int32 tensor")
+    b, h, w = labels.shape
+    if (b, h, w) != (truth.b, truth.h, truth.w) or labels.device != truth.device:
+        raise ValueError("label batch does not match the resident truth (images, shape or device)")
+    if merges.dtype != torch.int32 or merges.dim() != 3 or merges.shape[0] != b or merges.shape[2] != 2 or \
+            not 1 <= merges.shape[1] + 1 <= SWEEP_LEVELS:
+        raise ValueError(f"merges must be a (B, K - 1, 2) int32 tensor with K in 1..{SWEEP_LEVELS}")
+    if alive.dtype != torch.int32 or tuple(alive.shape) != (b,):
+        raise ValueError("alive must be a (B,) int32 tensor")
+    if merges.device != truth.device or alive.device != truth.device:
+        raise ValueError("merges / alive are not on the device of the resident truth")
+    try:
+        regs = [int(r) for r in regions]
+        same = all(r == q for r, q in zip(regs, regions))
+    except (TypeError, ValueError):
+        raise ValueError("regions must be a list of integers") from None
+    if not same or not 1 <= len(regs) <= SWEEP_CUTS or len(set(regs)) != len(regs) or min(regs) < 1 or max(regs) > SWEEP_LEVELS:
+        raise ValueError(f"regions must be 1..{SWEEP_CUTS} distinct integers in 1..{SWEEP_LEVELS}")
+    if h * w < 2:
+        raise ValueError(f"region agreement needs at least 2 pixels, got {h * w}")
+    k, t, stride, n = merges.shape[1] + 1, truth.t, truth.stride, len(regs)
+    if t * k * stride > 0x3fffffff:
+        raise ValueError(f"the leaf tables [{t}][{k}][{stride}] exceed 2^30 counters")
+    order = sorted(range(n), key=lambda j: -regs[j])             # the call wants R strictly decreasing
+    labels, merges, alive = labels.contiguous(), merges.contiguous(), alive.contiguous()
+    lib = _lib.load()
+    with torch.cuda.device(truth.device):
+        dev = truth.device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        hist = torch.empty(t * k * stride, dtype=torch.int32, device=dev)
+        side = torch.empty(2 * b * k, dtype=torch.int32, device=dev)             # area | perimeter of the leaves: not used here
+        counts = lib.gcs_region_counts_batch_u8 if truth.u8 else lib.gcs_region_counts_batch
+        _lib.check(counts(labels.data_ptr(), truth.maps.data_ptr(), truth.first_d.data_ptr(), b, t, truth.a_max, h, w, k, stride,
+                          hist.data_ptr(), side.data_ptr(), side.data_ptr() + 4 * b * k, stream), "gcs_region_counts_batch")
+        regs_d = torch.tensor([regs[j] for j in order], dtype=torch.int32).to(dev)
+        ws = torch.empty(lib.gcs_region_sweep_workspace_bytes(t, k, stride, n), dtype=torch.uint8, device=dev)
+        out = torch.empty(2 * n * t * 4, dtype=torch.int64, device=dev)          # sums uint64 [n][t][4] | terms double [n][t][4]
+        _lib.check(lib.gcs_region_sweep(hist.data_ptr(), merges.data_ptr() if k > 1 else None, alive.data_ptr(),
+                                        truth.img_of_d.data_ptr(), regs_d.data_ptr(), b, t, k, stride, n, ws.data_ptr(),
+                                        out.data_ptr(), out.data_ptr() + n * t * 32, stream), "gcs_region_sweep")
+        raw = out.cpu().numpy()
+    sums = np.empty((n, t, 4), np.uint64)
+    terms = np.empty((n, t, 4), np.float64)
+    sums[order] = raw[:n * t * 4].view(np.uint64).reshape(n, t, 4)
+    terms[order] = raw[n * t * 4:].view(np.float64).reshape(n, t, 4)
+    return sums, terms
+
+
+def sweep_agreement(sums, terms, first, n_pixels, regions) -> list:
+    """Per image a list with one ``{"PRI", "VoI", "covering"}`` per R of ``regions``, from the arrays of ``region_sweep_resident``:
+    ``agreement_from_sums`` per cut, so the floats are those of every other path of SPEC.md §8 on the same sums. Raises, per cut,
+    if a table did not count every pixel (N_t != n_pixels: a label outside 0 .. K-1)."""
+    sums, terms = np.asarray(sums), np.asarray(terms)
+    n = len(regions)
+    if sums.ndim != 3 or sums.shape != terms.shape or sums.shape[0] != n or sums.shape[2] != 4:
+        raise ValueError("sums / terms must be [len(regions)][T][4] arrays")
+    if int(np.asarray(first)[-1]) != sums.shape[1]:
+        raise ValueError("first does not describe the annotator maps of sums / terms")
+    per_cut = [agreement_from_sums(sums[j], terms[j], first, n_pixels) for j in range(n)]
+    return [[per_cut[j][i] for j in range(n)] for i in range(len(first) - 1)]

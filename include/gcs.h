@@ -438,6 +438,35 @@ int gcs_region_tree_contours(const int32_t *labels_dev, const int32_t *merges_de
 int gcs_boundary_sweep_resident(const int32_t *contours_dev, const void *truth_planes_dev, const int32_t *img_of_dev, int B, int T,
                                 int H, int W, int K, uint32_t *hist_out_dev, gcs_stream_t stream);
 
+/* ---- region metrics of every cut of the region tree at once (SPEC.md §16) --------------------------- */
+
+/* Every group of a cut is a union of superpixels, so its row of the contingency table is the sum of its superpixels' rows. The leaf
+ * tables leaf_hist_dev uint32 [T][K][n_truth_labels] (gcs_region_counts_batch[_u8] with n_segments = K on the label map of
+ * gcs_region_tree) are made once from the pixels; for annotator map t of image b = img_of_dev[t] and every R = regions_dev[c] the
+ * table of the cut is the leaf table with the first tau = max(0, alive_b - R) rows of image b's merge list applied (a row with
+ * a < b, both reps at that step, adds row b into row a and empties row b; (-1, -1) rows and rows not of that form are skipped, as in
+ * gcs_region_tree_contours), and the call writes what gcs_region_agreement writes for that table:
+ *   sums_out_dev  uint64 [n_cuts][T][4] = { N, sum a_i^2, sum b_j^2, sum n_ij^2 }
+ *   terms_out_dev double [n_cuts][T][4] = { sum a log2 a, sum b log2 b, sum n log2 n, sum_j b_j n*_j / u*_j }
+ * through the same per-table reduction (float sums in an order fixed by the table indices alone, no float atomics: the same inputs
+ * give the same bits from run to run; every cut is evaluated from its own table, no float is carried from cut to cut).
+ *   gcs_region_sweep_workspace_bytes  host only: per map the row and column sums of the table in hand. 0 for a bad argument.
+ *   gcs_region_sweep                  one launch on `stream`, a workgroup per annotator map. No allocation, no host synchronisation
+ *                                     (capturable). leaf_hist_dev is CONSUMED: coarsened in place, it holds the table of the last cut
+ *                                     afterwards. regions_dev int32 [n_cuts] must be strictly decreasing (the cuts are nested, the
+ *                                     table only ever gets coarser); it is read on the device, so the call cannot check it: an entry
+ *                                     that is not below its predecessor gets the sums of a coarser table, nothing is read or written
+ *                                     out of range. R >= alive gives the leaf table itself. img_of_dev int32 [T]: an entry outside
+ *                                     0 .. B-1 gets the leaf table at every cut. Workspace and outputs may hold anything on entry;
+ *                                     every output element is written. With K = 1 merges_dev is not read and may be NULL.
+ * GCS_EINVAL, with nothing launched: a NULL pointer (merges_dev may be NULL with K = 1), B outside 1..65535, T outside 1..1000000,
+ * K outside 1..4096, n_truth_labels < 1, n_cuts outside 1..64, T * K * n_truth_labels >= 2^31.
+ * Added within ABI 18: new entry points change no existing call, so GCS_ABI_VERSION did not move. */
+size_t gcs_region_sweep_workspace_bytes(int T, int K, int n_truth_labels, int n_cuts);
+int gcs_region_sweep(uint32_t *leaf_hist_dev, const int32_t *merges_dev, const int32_t *alive_dev, const int32_t *img_of_dev,
+                     const int32_t *regions_dev, int B, int T, int K, int n_truth_labels, int n_cuts, void *workspace_dev,
+                     uint64_t *sums_out_dev, double *terms_out_dev, gcs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
