@@ -1,5 +1,6 @@
 // scoring.hip — evaluation-side kernels of libgcs.so (gfx950): boundary recall / precision counts
-// (/root/reference/BSD_metrics/metrics.py:58-96), region tables (metrics.py:102-201) and connected regions (SPEC.md §7).
+// (/root/reference/BSD_metrics/metrics.py:58-96), region tables (metrics.py:102-201), region agreement (SPEC.md §8) and the two
+// sweeps over a region tree's cuts (SPEC.md §15, §16). Connected regions and the small-region merge: regions.hip.
 // Nothing here allocates, frees or synchronises; every entry point enqueues on the caller's stream.
 #include <limits.h>
 
@@ -228,26 +229,10 @@ __global__ __launch_bounds__(256) void bits_popcount_kernel(const unsigned long 
     if (threadIdx.x == 0) out[blockIdx.x] = (unsigned long long)s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
 }
 
-// 5 x 5 dilation of one word of a bd plane (rows of `wp` words, H rows), see bits_dilate_kernel
-__device__ __forceinline__ unsigned long long bits_dilate_word(const unsigned long long *__restrict__ plane, int H, int wp, int y,
-                                                               int wx, unsigned long long last_mask) {
-    unsigned long long acc = 0;
-    for (int dy = -2; dy <= 2; ++dy) {
-        const int yy = y + dy;
-        if (yy < 0 || yy >= H) continue;
-        const unsigned long long *r = plane + (long long)yy * wp;
-        const unsigned long long w = r[wx], pv = wx > 0 ? r[wx - 1] : 0ull, nx = wx + 1 < wp ? r[wx + 1] : 0ull;
-        acc |= w | (w << 1) | (w << 2) | (w >> 1) | (w >> 2) | (pv >> 63) | (pv >> 62) | (nx << 63) | (nx << 62);
-    }
-    return wx == wp - 1 ? acc & last_mask : acc;
-}
-
 // One workgroup per output plane q (no atomics, no zeroing): q < B: counts[q] = sum bd(L_q); else annotator t = q - B of image
 // b = img_of[t]: counts[B + 3t] = sum dil5(bd(L_b)) & bd(T_t), [B + 3t + 1] = sum bd(T_t) (prepared), [B + 3t + 2] = sum bd(L_b) &
-// dil5(bd(T_t)). Annotator planes [2][T][words] (bd, then dil5). Label planes: [2][B][words], or (INLINE) the bd planes alone,
-// dilated word by word right here (a label plane is dilated once per annotator of its image, 15 loads instead of one from a few
-// KB that sit in L2: cheaper than the launch it saves).
-template <bool INLINE>   // INLINE: dilate the label planes word by word here (one launch less; measured 28 us against 5 + 8: not used)
+// dil5(bd(T_t)). Annotator planes [2][T][words] (bd, then dil5); label planes [2][B][words].
+// (Dilating the label planes word by word in here instead, one launch less, measured 28 us against 5 + 8: not done.)
 __global__ __launch_bounds__(256) void bits_counts_kernel(const unsigned long long *__restrict__ lab,
                                                           const unsigned long long *__restrict__ tru,
                                                           const unsigned long long *__restrict__ tru_bd_counts,
@@ -255,8 +240,7 @@ __global__ __launch_bounds__(256) void bits_counts_kernel(const unsigned long lo
                                                           unsigned long long *__restrict__ counts) {
     __shared__ unsigned s_sum[2][4];
     const int q = blockIdx.x, tid = threadIdx.x;
-    const int wp = bits_wp(W), words = H * wp;
-    const unsigned long long last_mask = (W & 63) ? ((1ull << (W & 63)) - 1) : ~0ull;
+    const int words = H * bits_wp(W);
     unsigned c0 = 0, c1 = 0;
     if (q < B) {
         const unsigned long long *l = lab + (size_t)q * words;
@@ -266,8 +250,7 @@ __global__ __launch_bounds__(256) void bits_counts_kernel(const unsigned long lo
         const unsigned long long *lbd = lab + (size_t)b * words, *ldil = lab + ((size_t)B + b) * words;
         const unsigned long long *tbd = tru + (size_t)t * words, *tdil = tru + ((size_t)T + t) * words;
         for (int i = tid; i < words; i += 256) {
-            const unsigned long long ld = INLINE ? bits_dilate_word(lbd, H, wp, i / wp, i % wp, last_mask) : ldil[i];
-            c0 += __popcll(ld & tbd[i]);
+            c0 += __popcll(ldil[i] & tbd[i]);
             c1 += __popcll(lbd[i] & tdil[i]);
         }
     }
@@ -336,6 +319,24 @@ extern "C" int gcs_truth_prepare(const uint16_t *truth, int T, int H, int W, voi
     return GCS_OK;
 }
 
+// The label side of the resident boundary scorer, three launches: bd(L) bit planes (+ the label maxima into seg_max, which the
+// caller has zeroed, or NULL) | their dilation | the counts. scratch: the label planes [2][B][words].
+static int bits_counts_launch(const int32_t *labels, const void *truth_planes, const uint64_t *truth_bd_counts, const int32_t *img_of,
+                              int B, int T, int H, int W, void *scratch, uint64_t *counts, int32_t *seg_max, hipStream_t stream,
+                              const char *who) {
+    const long long nw = (long long)B * H * bits_wp(W);
+    unsigned long long *bd = static_cast<unsigned long long *>(scratch), *dil = bd + nw;
+    hipLaunchKernelGGL(bits_boundary_kernel<int32_t>, dim3(grid_for(nw, 4, 16384)), dim3(256), 0, stream, labels, B, H, W, bd, seg_max);
+    GCS_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(bits_dilate_kernel, dim3(grid_for(nw, 256, 16384)), dim3(256), 0, stream, bd, B, H, W, dil);
+    GCS_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(bits_counts_kernel, dim3(B + T), dim3(256), 0, stream, bd, static_cast<const unsigned long long *>(truth_planes),
+                       reinterpret_cast<const unsigned long long *>(truth_bd_counts), img_of, B, T, H, W,
+                       reinterpret_cast<unsigned long long *>(counts));
+    GCS_CHECK_LAUNCH(who);
+    return GCS_OK;
+}
+
 extern "C" int gcs_boundary_counts_resident(const int32_t *labels, const void *truth_planes, const uint64_t *truth_bd_counts,
                                             const int32_t *img_of, int B, int T, int H, int W, void *scratch, uint64_t *counts,
                                             int32_t *seg_max, gcs_stream_t stream) {
@@ -343,22 +344,12 @@ extern "C" int gcs_boundary_counts_resident(const int32_t *labels, const void *t
         return gcs_fail(GCS_EINVAL, "gcs_boundary_counts_resident: NULL pointer");
     if (B <= 0 || T <= 0 || B + T > 1000000 || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL)
         return gcs_fail(GCS_EINVAL, "gcs_boundary_counts_resident: bad shape");
-    const int words = H * bits_wp(W);
-    const long long nw = (long long)B * words;
-    unsigned long long *bd = static_cast<unsigned long long *>(scratch), *dil = bd + nw;
     if (seg_max) {
         hipError_t e = hipMemsetAsync(seg_max, 0, (size_t)B * sizeof(int32_t), stream);
         if (e != hipSuccess) return gcs_hip_fail(e, "gcs_boundary_counts_resident(memset)");
     }
-    hipLaunchKernelGGL(bits_boundary_kernel<int32_t>, dim3(grid_for(nw, 4, 16384)), dim3(256), 0, stream, labels, B, H, W, bd, seg_max);
-    GCS_CHECK_LAUNCH("gcs_boundary_counts_resident(boundaries)");
-    hipLaunchKernelGGL(bits_dilate_kernel, dim3(grid_for(nw, 256, 16384)), dim3(256), 0, stream, bd, B, H, W, dil);
-    GCS_CHECK_LAUNCH("gcs_boundary_counts_resident(dilation)");
-    hipLaunchKernelGGL(bits_counts_kernel<false>, dim3(B + T), dim3(256), 0, stream, bd, static_cast<const unsigned long long *>(truth_planes),
-                       reinterpret_cast<const unsigned long long *>(truth_bd_counts), img_of, B, T, H, W,
-                       reinterpret_cast<unsigned long long *>(counts));
-    GCS_CHECK_LAUNCH("gcs_boundary_counts_resident");
-    return GCS_OK;
+    return bits_counts_launch(labels, truth_planes, truth_bd_counts, img_of, B, T, H, W, scratch, counts, seg_max, stream,
+                              "gcs_boundary_counts_resident");
 }
 
 // ================================================= boundary counts of every cut of a region tree at once (SPEC.md §15)
@@ -471,264 +462,6 @@ extern "C" int gcs_boundary_sweep_resident(const int32_t *contours, const void *
     return GCS_OK;
 }
 
-// ================================================================== connected regions (§8f-4)
-// SPEC.md §7: 4-connected components of equal labels, renumbered 0,1,2,... in raster order of each
-// component's first pixel (so "Regions" = max+1 at /root/reference/BSD_metrics/metrics.py:51 counts
-// connected regions, as it does for the SLIC output the slot holds today). Lock-free union-find:
-// parents only ever decrease (atomicMin), a root is the smallest pixel index of its component, and a
-// failed link (someone re-parented the node meanwhile) retries from the displaced parent, so no
-// equivalence is lost even when a find reads a stale pointer.
-__device__ __forceinline__ int cc_find(const int *parent, int x) {
-    for (;;) {
-        const int p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (p == x) return x;
-        x = p;
-    }
-}
-
-__device__ __forceinline__ void cc_unite(int *parent, int a, int b) {
-    for (;;) {
-        a = cc_find(parent, a);
-        b = cc_find(parent, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }   // link the larger root under the smaller
-        const int old = atomicMin(&parent[a], b);
-        if (old == a) return;
-        a = old;                                          // a was re-parented meanwhile: merge that chain too
-    }
-}
-
-__global__ void cc_union_kernel(const int32_t *__restrict__ labels, int H, int W, int *__restrict__ parent) {
-    const int P = H * W;
-    const int32_t *lab = labels + (size_t)blockIdx.y * P;
-    int *par = parent + (size_t)blockIdx.y * P;
-    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < P; p += gridDim.x * blockDim.x) {
-        const int y = p / W, x = p % W;
-        const int32_t l = lab[p];
-        if (x + 1 < W && lab[p + 1] == l) cc_unite(par, p, p + 1);
-        if (y + 1 < H && lab[p + W] == l) cc_unite(par, p, p + W);
-    }
-}
-
-__global__ void cc_local_init_kernel(int H, int W, int *__restrict__ parent) {
-    const int P = H * W;
-    int *par = parent + (size_t)blockIdx.y * P;
-    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < P; p += gridDim.x * blockDim.x) par[p] = p;
-}
-
-// one workgroup per image: flatten, count roots per contiguous chunk, scan, hand out ids in raster order
-__global__ __launch_bounds__(1024) void cc_rank_kernel(int H, int W, int *__restrict__ parent, int *__restrict__ rootid) {
-    __shared__ int s_cnt[1024];
-    const int P = H * W;
-    int *par = parent + (size_t)blockIdx.x * P;
-    int *rid = rootid + (size_t)blockIdx.x * P;
-    const int tid = threadIdx.x;
-    const int chunk = (P + 1023) / 1024;
-    const int lo = min(P, tid * chunk), hi = min(P, lo + chunk);
-    int cnt = 0;
-    for (int p = lo; p < hi; ++p) cnt += par[p] == p;
-    s_cnt[tid] = cnt;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {          // Hillis-Steele inclusive scan
-        const int v = tid >= off ? s_cnt[tid - off] : 0;
-        __syncthreads();
-        s_cnt[tid] += v;
-        __syncthreads();
-    }
-    int id = s_cnt[tid] - cnt;                           // exclusive prefix = first id of this chunk
-    for (int p = lo; p < hi; ++p)
-        if (par[p] == p) rid[p] = id++;
-}
-
-__global__ void cc_relabel_kernel(int H, int W, const int *__restrict__ parent, const int *__restrict__ rootid,
-                                  int32_t *__restrict__ out) {
-    const int P = H * W;
-    const int *par = parent + (size_t)blockIdx.y * P;
-    const int *rid = rootid + (size_t)blockIdx.y * P;
-    int32_t *o = out + (size_t)blockIdx.y * P;
-    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < P; p += gridDim.x * blockDim.x) {
-        int r = par[p];
-        while (par[r] != r) r = par[r];                  // the union kernel has finished: plain loads are current
-        o[p] = rid[r];
-    }
-}
-
-extern "C" size_t gcs_connected_scratch_bytes(int B, int H, int W) {
-    if (B <= 0 || H <= 0 || W <= 0) return 0;
-    return (size_t)2 * B * H * W * sizeof(int32_t);
-}
-
-extern "C" int gcs_connected_regions(const int32_t *labels, int B, int H, int W, void *scratch, int32_t *out,
-                                     gcs_stream_t stream) {
-    if (!labels || !scratch || !out) return gcs_fail(GCS_EINVAL, "gcs_connected_regions: NULL pointer");
-    if (B <= 0 || B > 65535 || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL)
-        return gcs_fail(GCS_EINVAL, "gcs_connected_regions: bad shape");
-    const int P = H * W;
-    int *parent = static_cast<int *>(scratch);
-    int *rootid = parent + (size_t)B * P;
-    const dim3 grid(min(1024, (P + 255) / 256), B), block(256);
-    hipLaunchKernelGGL(cc_local_init_kernel, grid, block, 0, stream, H, W, parent);
-    GCS_CHECK_LAUNCH("gcs_connected_regions(init)");
-    hipLaunchKernelGGL(cc_union_kernel, grid, block, 0, stream, labels, H, W, parent);
-    GCS_CHECK_LAUNCH("gcs_connected_regions(union)");
-    hipLaunchKernelGGL(cc_rank_kernel, dim3(B), dim3(1024), 0, stream, H, W, parent, rootid);
-    GCS_CHECK_LAUNCH("gcs_connected_regions(rank)");
-    hipLaunchKernelGGL(cc_relabel_kernel, grid, block, 0, stream, H, W, parent, rootid, out);
-    GCS_CHECK_LAUNCH("gcs_connected_regions");
-    return GCS_OK;
-}
-
-// ================================================================== small-region merging (SPEC.md §9)
-// Starts from the union-find forest of the connected regions and keeps it: a region's id is its root, which cc_unite keeps
-// at the smallest pixel index of the set, i.e. the region's first pixel. One round = four launches on a flattened forest
-// (parent[p] = root of p): sizes by horizontal runs, each absorbable region's best neighbour by 64-bit atomicMax, the union of
-// every absorbable root with its pick, a flatten. size[] and best[] are non-zero at roots only; the union kernel clears
-// them after use, so the next round starts from zeros. act[r][b] = 1 when round r merged something in image b: a later round
-// of an image whose previous round merged nothing returns at once. The rounds the halving bound allows are all enqueued.
-__device__ __forceinline__ bool mr_idle(const int *act, int round, int B, int b) {
-    return round > 0 && act[(size_t)(round - 1) * B + b] == 0;
-}
-
-__global__ void mr_init_kernel(int H, int W, int B, int n_rounds, int *__restrict__ parent, unsigned *__restrict__ size,
-                               unsigned long long *__restrict__ best, int *__restrict__ act) {
-    const int P = H * W, b = blockIdx.y;
-    int *par = parent + (size_t)b * P;
-    unsigned *sz = size + (size_t)b * P;
-    unsigned long long *bs = best + (size_t)b * P;
-    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < P; p += gridDim.x * blockDim.x) {
-        par[p] = p;
-        sz[p] = 0;
-        bs[p] = 0;
-    }
-    if (blockIdx.x == 0 && (int)threadIdx.x < n_rounds) act[(size_t)threadIdx.x * B + b] = 0;
-}
-
-__global__ void mr_flatten_kernel(int H, int W, int B, int round, int *__restrict__ parent, const int *__restrict__ act) {
-    const int P = H * W, b = blockIdx.y;
-    if (round >= 0 && act[(size_t)round * B + b] == 0) return;     // nothing was united: the forest is still flat
-    int *par = parent + (size_t)b * P;
-    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < P; p += gridDim.x * blockDim.x) {
-        int r = par[p];
-        while (par[r] != r) r = par[r];                  // concurrent shortcuts only ever point at the same root
-        par[p] = r;
-    }
-}
-
-// the first pixel of each horizontal run of one region adds the run's length: one atomic per run, not per pixel
-__global__ void mr_size_kernel(int H, int W, int B, int round, const int *__restrict__ parent, unsigned *__restrict__ size,
-                               const int *__restrict__ act) {
-    const int P = H * W, b = blockIdx.y;
-    if (mr_idle(act, round, B, b)) return;
-    const int *par = parent + (size_t)b * P;
-    unsigned *sz = size + (size_t)b * P;
-    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < P; p += gridDim.x * blockDim.x) {
-        const int x = p % W, r = par[p];
-        if (x > 0 && par[p - 1] == r) continue;
-        int len = 1;
-        while (x + len < W && par[p + len] == r) ++len;
-        atomicAdd(&sz[r], (unsigned)len);
-    }
-}
-
-// key of region r as a neighbour: larger size first, then the smaller root (= the earlier first pixel)
-__device__ __forceinline__ unsigned long long mr_key(const unsigned *sz, int r) {
-    return ((unsigned long long)sz[r] << 32) | (0xFFFFFFFFu - (unsigned)r);
-}
-
-__global__ void mr_best_kernel(int H, int W, int B, int round, unsigned min_size, const int *__restrict__ parent,
-                               const unsigned *__restrict__ size, unsigned long long *__restrict__ best,
-                               const int *__restrict__ act) {
-    const int P = H * W, b = blockIdx.y;
-    if (mr_idle(act, round, B, b)) return;
-    const int *par = parent + (size_t)b * P;
-    const unsigned *sz = size + (size_t)b * P;
-    unsigned long long *bs = best + (size_t)b * P;
-    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < P; p += gridDim.x * blockDim.x) {
-        const int x = p % W, ra = par[p];
-        const bool a_small = sz[ra] < min_size;
-        #pragma unroll
-        for (int dir = 0; dir < 2; ++dir) {
-            const int q = dir == 0 ? p + 1 : p + W;
-            if (dir == 0 ? x + 1 >= W : q >= P) continue;
-            const int rb = par[q];
-            if (rb == ra) continue;
-            if (a_small) atomicMax(&bs[ra], mr_key(sz, rb));
-            if (sz[rb] < min_size) atomicMax(&bs[rb], mr_key(sz, ra));
-        }
-    }
-}
-
-__global__ void mr_union_kernel(int H, int W, int B, int round, int *__restrict__ parent, unsigned *__restrict__ size,
-                                unsigned long long *__restrict__ best, int *__restrict__ act) {
-    const int P = H * W, b = blockIdx.y;
-    if (mr_idle(act, round, B, b)) return;
-    int *par = parent + (size_t)b * P;
-    unsigned *sz = size + (size_t)b * P;
-    unsigned long long *bs = best + (size_t)b * P;
-    bool merged = false;
-    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < P; p += gridDim.x * blockDim.x) {
-        if (sz[p] == 0) continue;                        // not a root
-        const unsigned long long k = bs[p];
-        sz[p] = 0;
-        if (k == 0) continue;                            // not absorbable (big enough, or the whole image)
-        bs[p] = 0;
-        cc_unite(par, p, (int)(0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull)));
-        merged = true;
-    }
-    if (merged) act[(size_t)round * B + b] = 1;          // every writer stores the same value
-}
-
-extern "C" size_t gcs_merge_scratch_bytes(int B, int H, int W, int min_size) {
-    if (B <= 0 || B > 65535 || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL || min_size < 0) return 0;
-    // best (u64) | parent | rootid | size per pixel, then one flag per (round, image)
-    return (size_t)B * H * W * (sizeof(unsigned long long) + 3 * sizeof(int32_t)) + (size_t)32 * B * sizeof(int32_t);
-}
-
-extern "C" int gcs_merge_small_regions(const int32_t *labels, int B, int H, int W, int min_size, void *scratch, int32_t *out,
-                                       gcs_stream_t stream) {
-    if (!labels || !scratch || !out) return gcs_fail(GCS_EINVAL, "gcs_merge_small_regions: NULL pointer");
-    if (B <= 0 || B > 65535 || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL)
-        return gcs_fail(GCS_EINVAL, "gcs_merge_small_regions: bad shape");
-    if (min_size < 0) return gcs_fail(GCS_EINVAL, "gcs_merge_small_regions: min_size < 0");
-    if (static_cast<const void *>(labels) == static_cast<const void *>(out))
-        return gcs_fail(GCS_EINVAL, "gcs_merge_small_regions: out may not alias labels");
-    const int P = H * W;
-    const size_t n = (size_t)B * P;
-    unsigned long long *best = static_cast<unsigned long long *>(scratch);
-    int *parent = reinterpret_cast<int *>(best + n);
-    int *rootid = parent + n;
-    unsigned *size = reinterpret_cast<unsigned *>(rootid + n);
-    int *act = reinterpret_cast<int *>(size + n);
-    // every round at least halves the absorbable regions (SPEC.md §9): floor(log2(P)) + 1 rounds suffice; none for m <= 1
-    int n_rounds = 0;
-    if (min_size > 1)
-        for (unsigned v = (unsigned)P; v; v >>= 1) ++n_rounds;
-    const dim3 grid(min(1024, (P + 255) / 256), B), block(256);
-    hipLaunchKernelGGL(mr_init_kernel, grid, block, 0, stream, H, W, B, n_rounds, parent, size, best, act);
-    GCS_CHECK_LAUNCH("gcs_merge_small_regions(init)");
-    hipLaunchKernelGGL(cc_union_kernel, grid, block, 0, stream, labels, H, W, parent);
-    GCS_CHECK_LAUNCH("gcs_merge_small_regions(union)");
-    if (n_rounds > 0) {
-        hipLaunchKernelGGL(mr_flatten_kernel, grid, block, 0, stream, H, W, B, -1, parent, act);
-        GCS_CHECK_LAUNCH("gcs_merge_small_regions(flatten)");
-    }
-    for (int r = 0; r < n_rounds; ++r) {
-        hipLaunchKernelGGL(mr_size_kernel, grid, block, 0, stream, H, W, B, r, parent, size, act);
-        GCS_CHECK_LAUNCH("gcs_merge_small_regions(size)");
-        hipLaunchKernelGGL(mr_best_kernel, grid, block, 0, stream, H, W, B, r, (unsigned)min_size, parent, size, best, act);
-        GCS_CHECK_LAUNCH("gcs_merge_small_regions(best)");
-        hipLaunchKernelGGL(mr_union_kernel, grid, block, 0, stream, H, W, B, r, parent, size, best, act);
-        GCS_CHECK_LAUNCH("gcs_merge_small_regions(merge)");
-        hipLaunchKernelGGL(mr_flatten_kernel, grid, block, 0, stream, H, W, B, r, parent, act);
-        GCS_CHECK_LAUNCH("gcs_merge_small_regions(flatten)");
-    }
-    hipLaunchKernelGGL(cc_rank_kernel, dim3(B), dim3(1024), 0, stream, H, W, parent, rootid);
-    GCS_CHECK_LAUNCH("gcs_merge_small_regions(rank)");
-    hipLaunchKernelGGL(cc_relabel_kernel, grid, block, 0, stream, H, W, parent, rootid, out);
-    GCS_CHECK_LAUNCH("gcs_merge_small_regions");
-    return GCS_OK;
-}
-
 // ======================================================================= region tables (§8f-2)
 // Integer part of /root/reference/BSD_metrics/metrics.py:102-146 (label x annotator contingency table and region
 // areas) and :160-181 (4-neighbour perimeter: image-border pixels, or pixels with a different 4-neighbour). One
@@ -806,13 +539,18 @@ static int region_counts_launch(const int32_t *labels, const TT *truth, const in
     return GCS_OK;
 }
 
+// The shape rules the region-table entry points share (the single-image entry passes B = 1, T = max_annotators = A).
+static bool region_shape_ok(int B, int T, int max_annotators, int H, int W, int n_segments, int n_truth_labels, bool u8) {
+    return B > 0 && B <= 65535 && T > 0 && max_annotators > 0 && H > 0 && W > 0 && (long long)H * W <= 0x7fffffffLL &&
+           n_segments > 0 && n_truth_labels > 0 && !(u8 && n_truth_labels > 256) &&
+           (long long)T * n_segments * n_truth_labels <= 0x3fffffffLL;
+}
+
 extern "C" int gcs_region_counts(const int32_t *labels, const uint16_t *truth, int A, int H, int W, int n_segments,
                                  int n_truth_labels, uint32_t *hist, uint32_t *area, uint32_t *perim,
                                  gcs_stream_t stream) {
     if (!labels || !truth || !hist || !area || !perim) return gcs_fail(GCS_EINVAL, "gcs_region_counts: NULL pointer");
-    if (A <= 0 || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL || n_segments <= 0 || n_truth_labels <= 0 ||
-        (long long)A * n_segments * n_truth_labels > 0x3fffffffLL)
-        return gcs_fail(GCS_EINVAL, "gcs_region_counts: bad shape");
+    if (!region_shape_ok(1, A, A, H, W, n_segments, n_truth_labels, false)) return gcs_fail(GCS_EINVAL, "gcs_region_counts: bad shape");
     return region_counts_launch(labels, truth, nullptr, 1, A, A, H, W, n_segments, n_truth_labels, hist, area, perim, stream,
                                 "gcs_region_counts");
 }
@@ -822,8 +560,7 @@ extern "C" int gcs_region_counts_batch(const int32_t *labels, const uint16_t *tr
                                        uint32_t *area, uint32_t *perim, gcs_stream_t stream) {
     if (!labels || !truth || !first || !hist || !area || !perim)
         return gcs_fail(GCS_EINVAL, "gcs_region_counts_batch: NULL pointer");
-    if (B <= 0 || B > 65535 || T <= 0 || max_annotators <= 0 || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL ||
-        n_segments <= 0 || n_truth_labels <= 0 || (long long)T * n_segments * n_truth_labels > 0x3fffffffLL)
+    if (!region_shape_ok(B, T, max_annotators, H, W, n_segments, n_truth_labels, false))
         return gcs_fail(GCS_EINVAL, "gcs_region_counts_batch: bad shape");
     return region_counts_launch(labels, truth, first, B, T, max_annotators, H, W, n_segments, n_truth_labels, hist, area,
                                 perim, stream, "gcs_region_counts_batch");
@@ -891,8 +628,7 @@ extern "C" int gcs_region_counts_batch_u8(const int32_t *labels, const uint8_t *
                                           uint32_t *area, uint32_t *perim, gcs_stream_t stream) {
     if (!labels || !truth8 || !first || !hist || !area || !perim)
         return gcs_fail(GCS_EINVAL, "gcs_region_counts_batch_u8: NULL pointer");
-    if (B <= 0 || B > 65535 || T <= 0 || max_annotators <= 0 || H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL ||
-        n_segments <= 0 || n_truth_labels <= 0 || n_truth_labels > 256 || (long long)T * n_segments * n_truth_labels > 0x3fffffffLL)
+    if (!region_shape_ok(B, T, max_annotators, H, W, n_segments, n_truth_labels, true))
         return gcs_fail(GCS_EINVAL, "gcs_region_counts_batch_u8: bad shape");
     return region_counts_launch(labels, truth8, first, B, T, max_annotators, H, W, n_segments, n_truth_labels, hist, area,
                                 perim, stream, "gcs_region_counts_batch_u8");
@@ -908,12 +644,9 @@ extern "C" int gcs_score_batch_resident(const int32_t *labels, const void *truth
     if (!labels || !truth_planes || !truth_bd_counts || !truth_maps || !first || !img_of || !scratch || !hist || !counts || !seg_max ||
         !area || !perim || !under || !under_np)
         return gcs_fail(GCS_EINVAL, "gcs_score_batch_resident: NULL pointer");
-    if (B <= 0 || B > 65535 || T <= 0 || B + T > 1000000 || max_annotators <= 0 || H <= 0 || W <= 0 ||
-        (long long)H * W > 0x7fffffffLL || n_segments <= 0 || n_truth_labels <= 0 || (truth_is_u8 && n_truth_labels > 256) ||
-        (long long)T * n_segments * n_truth_labels > 0x3fffffffLL || (long long)B * n_segments > 0x3fffffffLL)
+    if (!region_shape_ok(B, T, max_annotators, H, W, n_segments, n_truth_labels, truth_is_u8 != 0) || B + T > 1000000 ||
+        (long long)B * n_segments > 0x3fffffffLL)
         return gcs_fail(GCS_EINVAL, "gcs_score_batch_resident: bad shape");
-    const int words = H * bits_wp(W);
-    const long long nw = (long long)B * words;
     ZeroList z;
     z.p[0] = hist; z.n[0] = (unsigned)((size_t)T * n_segments * n_truth_labels);
     z.p[1] = area; z.n[1] = (unsigned)((size_t)B * n_segments);       // (B * n_segments < 2^30: checked above)
@@ -921,19 +654,14 @@ extern "C" int gcs_score_batch_resident(const int32_t *labels, const void *truth
     z.p[3] = reinterpret_cast<unsigned *>(seg_max); z.n[3] = (unsigned)B;
     hipLaunchKernelGGL(zero_kernel, dim3(grid_for((long long)z.n[0], 256, 1024)), dim3(256), 0, stream, z);
     GCS_CHECK_LAUNCH("gcs_score_batch_resident(zero)");
-    unsigned long long *bd = static_cast<unsigned long long *>(scratch);
-    hipLaunchKernelGGL(bits_boundary_kernel<int32_t>, dim3(grid_for(nw, 4, 16384)), dim3(256), 0, stream, labels, B, H, W, bd, seg_max);
-    GCS_CHECK_LAUNCH("gcs_score_batch_resident(boundaries)");
-    hipLaunchKernelGGL(bits_dilate_kernel, dim3(grid_for(nw, 256, 16384)), dim3(256), 0, stream, bd, B, H, W, bd + nw);
-    GCS_CHECK_LAUNCH("gcs_score_batch_resident(dilation)");
-    hipLaunchKernelGGL(bits_counts_kernel<false>, dim3(B + T), dim3(256), 0, stream, bd, static_cast<const unsigned long long *>(truth_planes),
-                       reinterpret_cast<const unsigned long long *>(truth_bd_counts), img_of, B, T, H, W,
-                       reinterpret_cast<unsigned long long *>(counts));
-    GCS_CHECK_LAUNCH("gcs_score_batch_resident(counts)");
-    int rc = truth_is_u8 ? region_counts_launch(labels, static_cast<const uint8_t *>(truth_maps), first, B, T, max_annotators, H, W,
-                                                n_segments, n_truth_labels, hist, area, perim, stream, "gcs_score_batch_resident(regions)", true)
-                         : region_counts_launch(labels, static_cast<const uint16_t *>(truth_maps), first, B, T, max_annotators, H, W,
-                                                n_segments, n_truth_labels, hist, area, perim, stream, "gcs_score_batch_resident(regions)", true);
+    int rc = bits_counts_launch(labels, truth_planes, truth_bd_counts, img_of, B, T, H, W, scratch, counts, seg_max, stream,
+                                "gcs_score_batch_resident(boundary)");
+    if (rc != GCS_OK) return rc;
+    auto regions = [&](auto *maps) {                           // the tables are zeroed above
+        return region_counts_launch(labels, maps, first, B, T, max_annotators, H, W, n_segments, n_truth_labels, hist, area, perim,
+                                    stream, "gcs_score_batch_resident(regions)", true);
+    };
+    rc = truth_is_u8 ? regions(static_cast<const uint8_t *>(truth_maps)) : regions(static_cast<const uint16_t *>(truth_maps));
     if (rc != GCS_OK) return rc;
     hipLaunchKernelGGL(region_reduce_kernel, dim3(T), dim3(256), 0, stream, hist, area, img_of, n_segments, n_truth_labels,
                        reinterpret_cast<unsigned long long *>(under), reinterpret_cast<unsigned long long *>(under_np));

@@ -1,22 +1,152 @@
-"""Scoring on the GPU: boundary recall / precision / F and the region metrics
-(undersegmentation, compactness, density: §8f rank 2).
+"""Scoring on the GPU: the kernels give integer counts and tables, the float arithmetic of the reference
+(BSD_metrics/metrics.py:58-201; region agreement: SPEC.md §8) runs here in the reference's order, so the floats are its floats.
+Four layers, each with the C entry points it calls:
 
-Same quantities as ``evaluate.metrics.set_boundary_recall/precision`` — i.e. as
-/root/reference/BSD_metrics/metrics.py:58-96 — with the stencils and the masked sums done by
-``gcs_boundary_counts`` (integer counts) and the reference's float divisions / per-annotator
-mean done here in the reference's order, so the results are identical floats. Lets large
-batches be scored without a device->host round trip of the label maps.
+1. One image, truth uploaded per call: ``boundary_counts_device`` / ``boundary_scores_device`` (gcs_boundary_counts),
+   ``region_counts_device`` (gcs_region_counts), ``region_agreement_device`` (gcs_region_counts, gcs_region_agreement),
+   ``all_scores_device`` (gcs_boundary_counts, gcs_region_counts).
+2. A batch, truth uploaded per call: ``all_scores_batch_device`` (gcs_boundary_counts_batch, gcs_region_counts_batch,
+   gcs_region_agreement with agreement=True).
+3. A batch on resident truth: ``DeviceTruth`` (gcs_truth_prepare), ``submit_scores_batch_resident`` /
+   ``all_scores_batch_resident`` (gcs_score_batch_resident, gcs_region_agreement with agreement=True).
+4. Every cut of a region tree on resident truth: ``boundary_sweep_resident`` (gcs_boundary_sweep_resident) with
+   ``sweep_counts`` / ``sweep_scores``; ``region_sweep_resident`` (gcs_region_counts_batch[_u8], gcs_region_sweep) with
+   ``sweep_agreement``.
+
+The host arithmetic exists once: ``_boundary_scores``, ``_region_scores_batch`` and ``evaluate.agreement_from_sums``.
 """
 from __future__ import annotations
 
 import weakref
+from collections import namedtuple
+from math import pi
 
 import numpy as np
 
-from math import pi
-
 from . import _lib
 from .evaluate import agreement_from_sums
+
+SWEEP_LEVELS = 4096                                              # the most labels a region tree has (SPEC.md §14)
+SWEEP_CUTS = 64                                                  # the most cuts one gcs_region_sweep call takes
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Argument checks
+
+def _need_labels(labels, ndim, what="labels"):
+    import torch
+    if labels.dtype != torch.int32 or labels.dim() != ndim:
+        raise ValueError(f"{what} must be {'an (H,W)' if ndim == 2 else 'a (B,H,W)'} int32 tensor")
+
+
+def _need_truths(truths, labels):
+    if truths.dim() != 3 or truths.shape[1:] != labels.shape or truths.element_size() != 2:
+        raise ValueError("truths must be an (A,H,W) 16-bit tensor matching labels")
+
+
+def _need_match(shape, device, truth, what):
+    if tuple(shape) != (truth.b, truth.h, truth.w) or device != truth.device:
+        raise ValueError(f"{what} batch does not match the resident truth (images, shape or device)")
+
+
+def _need_two_pixels(h, w):
+    if h * w < 2:
+        raise ValueError(f"region agreement needs at least 2 pixels, got {h * w}")
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Host arithmetic
+
+def _boundary_scores(g, ann) -> dict:
+    """metrics.py:69-74 and :88-96 on Python floats (the same IEEE doubles, no NumPy scalar boxing per operation): g = sum bd(L),
+    ann = per annotator [recall numerator, recall denominator, precision numerator], flat."""
+    a = len(ann) // 3
+    recall = 0
+    precision = 0
+    for i in range(0, 3 * a, 3):                                 # in annotator order
+        recall += ann[i] / ann[i + 1]                            # ZeroDivisionError as metrics.py:72
+        precision += ann[i + 2] / g                              # ZeroDivisionError as metrics.py:94
+    recall /= a
+    precision /= a
+    s = recall + precision
+    return {"recall": recall, "precision": precision, "fmeasure": 0.0 if s == 0 else 2.0 * precision * recall / s}
+
+
+def scores_from_counts(counts) -> dict:
+    """metrics.py:69-74 and :88-96 arithmetic on the integer counts [1 + 3A] (plain Python floats)."""
+    c = np.asarray(counts).astype(np.float64).tolist()           # rounds as float(np.uint64) does
+    return _boundary_scores(c[0], c[1:])
+
+
+def _region_scores_batch(under, under_np, area, perim, first, nx, ny):
+    """metrics.py:128-146 and :188-201 for a batch: under / under_np [T] = the integer sums of metrics.py:129-130, :137-139
+    (exact in any order), area / perim [B][n_seg]. The sums of fractions keep the reference's order, term by term
+    (metrics.py:131, :140, :194-201)."""
+    b = len(first) - 1
+    u_t = under.astype(np.float64) / (nx * ny)
+    unp_t = under_np.astype(np.float64) / (nx * ny)
+    max_area = float(nx * ny)
+    a64 = area.astype(np.int64)
+    per = perim.astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        terms = 4 * pi * (a64 / max_area) * a64 / (per * per)                    # metrics.py:199, element by element
+    out = []
+    u_t, unp_t, first = u_t.tolist(), unp_t.tolist(), np.asarray(first).tolist()  # Python floats, as in _boundary_scores
+    terms, has = terms.tolist(), (per > 0).tolist()
+    for i in range(b):
+        t0, t1 = first[i], first[i + 1]
+        under_i = 0.
+        under_np_i = 0.
+        for t in range(t0, t1):                                                  # metrics.py:131,140: += in annotator order
+            under_i += u_t[t]
+            under_np_i += unp_t[t]
+        compactness = 0
+        for term, ok in zip(terms[i], has[i]):                                   # metrics.py:194-201: index order
+            if ok:
+                compactness += term
+        out.append({"underseg": under_i / (t1 - t0), "undersegNP": under_np_i / (t1 - t0), "compactness": float(compactness)})
+    return out
+
+
+def region_scores_from_counts(hist, area, perim, n_truth, nx, ny) -> dict:
+    """metrics.py:128-146 and :188-201 arithmetic on the integer tables of one image, giving the reference's floats.
+    ``n_truth[a]`` = max(truth_a) + 1 (metrics.py:116): only those columns of annotator a exist there."""
+    area64 = np.asarray(area).astype(np.int64)
+    under, under_np = [], []
+    for a in range(hist.shape[0]):
+        h = hist[a][:, :int(n_truth[a])].astype(np.int64)
+        under.append(int(np.sum(area64 - h.max(axis=1))))                        # metrics.py:129-130
+        under_np.append(int(np.sum(np.minimum(h, h.sum(axis=1)[:, None] - h))))  # metrics.py:137-139
+    return _region_scores_batch(np.array(under, np.int64), np.array(under_np, np.int64), area64[None], np.asarray(perim)[None],
+                                [0, hist.shape[0]], nx, ny)[0]
+
+
+def _agreement_arrays(raw, n):
+    """A downloaded agreement block of n maps, ``sums uint64 [n][4] | terms float64 [n][4]`` -> the two arrays."""
+    return raw[:n * 4].view(np.uint64).reshape(n, 4), raw[n * 4:n * 8].view(np.float64).reshape(n, 4)
+
+
+def _batch_scores(counts, seg_max, reg, first, n_pixels, agree=None) -> list:
+    """The dicts of a batch from its counts [B + 3T] (gcs.h layout), label maxima, region scores and agreement scores."""
+    b = len(first) - 1
+    cf = np.asarray(counts).astype(np.float64).tolist()
+    first = np.asarray(first).tolist()
+    out = []
+    for i in range(b):
+        out.append({"regions": int(seg_max[i]) + 1,                              # metrics.py:51
+                    **_boundary_scores(cf[i], cf[b + 3 * first[i]:b + 3 * first[i + 1]]), **reg[i],
+                    "density": cf[i] / float(n_pixels),                          # metrics.py:157
+                    **(agree[i] if agree is not None else {})})
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# 1. One image, truth uploaded per call
+
+def _truth_stack(segments_truth, device):
+    import torch
+    t = np.stack([np.asarray(s).astype(np.uint16) for s in segments_truth])
+    return t, torch.from_numpy(np.ascontiguousarray(t.view(np.int16))).to(device)
 
 
 def boundary_counts_device(labels, truths):
@@ -24,10 +154,8 @@ def boundary_counts_device(labels, truths):
     Returns the uint64 counts [1 + 3A] as a host numpy array."""
     import torch
     lib = _lib.load()
-    if labels.dtype != torch.int32 or labels.dim() != 2:
-        raise ValueError("labels must be an (H,W) int32 tensor")
-    if truths.dim() != 3 or truths.shape[1:] != labels.shape or truths.element_size() != 2:
-        raise ValueError("truths must be an (A,H,W) 16-bit tensor matching labels")
+    _need_labels(labels, 2)
+    _need_truths(truths, labels)
     a, h, w = truths.shape
     labels, truths = labels.contiguous(), truths.contiguous()
     scratch = torch.empty(lib.gcs_boundary_scratch_bytes(a, h, w), dtype=torch.uint8, device=labels.device)
@@ -38,102 +166,46 @@ def boundary_counts_device(labels, truths):
     return counts.cpu().numpy().astype(np.uint64)
 
 
-def scores_from_counts(counts) -> dict:
-    """metrics.py:69-74 and :88-96 arithmetic on the integer counts (plain Python floats)."""
-    a = (len(counts) - 1) // 3
-    recall = 0
-    precision = 0
-    global_score = float(counts[0])
-    for i in range(a):
-        recall += float(counts[1 + 3 * i]) / float(counts[2 + 3 * i])        # ZeroDivisionError as metrics.py:72
-        precision += float(counts[3 + 3 * i]) / global_score                 # ZeroDivisionError as metrics.py:94
-    recall /= a
-    precision /= a
-    s = recall + precision
-    return {"recall": recall, "precision": precision,
-            "fmeasure": 0.0 if s == 0 else 2.0 * precision * recall / s}
-
-
 def boundary_scores_device(labels, segments_truth) -> dict:
     """labels: (H,W) int32 device tensor (e.g. a row of Segmenter.segment_device);
     segments_truth: list of (H,W) integer arrays (groundtruth.get_segment_from_filename)."""
-    import torch
     if len(segments_truth) == 0:
         raise ZeroDivisionError("no annotator maps (metrics.py:74 divides by len(img_truth))")
-    t = np.stack([np.asarray(s).astype(np.uint16) for s in segments_truth]).view(np.int16)
-    truths = torch.from_numpy(np.ascontiguousarray(t)).to(labels.device)
-    return scores_from_counts(boundary_counts_device(labels, truths))
+    return scores_from_counts(boundary_counts_device(labels, _truth_stack(segments_truth, labels.device)[1]))
 
 
-def _truth_stack(segments_truth, device):
+def _region_tables(labels, truths, n_segments, n_truth_labels):
+    """gcs_region_counts on checked tensors: the device tables (hist [A,n_segments,n_truth_labels], area, perimeters)."""
     import torch
-    t = np.stack([np.asarray(s).astype(np.uint16) for s in segments_truth])
-    return t, torch.from_numpy(np.ascontiguousarray(t.view(np.int16))).to(device)
-
-
-def region_counts_device(labels, truths, n_segments, n_truth_labels):
-    """labels: (H,W) int32 device tensor with values < n_segments; truths: (A,H,W) 16-bit device tensor with
-    values < n_truth_labels. Returns host arrays (hist [A,n_segments,n_truth_labels], area, perimeters)."""
-    import torch
-    lib = _lib.load()
-    if labels.dtype != torch.int32 or labels.dim() != 2:
-        raise ValueError("labels must be an (H,W) int32 tensor")
-    if truths.dim() != 3 or truths.shape[1:] != labels.shape or truths.element_size() != 2:
-        raise ValueError("truths must be an (A,H,W) 16-bit tensor matching labels")
     a, h, w = truths.shape
     labels, truths = labels.contiguous(), truths.contiguous()
     hist = torch.empty((a, n_segments, n_truth_labels), dtype=torch.int32, device=labels.device)
     area = torch.empty(n_segments, dtype=torch.int32, device=labels.device)
     perim = torch.empty(n_segments, dtype=torch.int32, device=labels.device)
-    _lib.check(lib.gcs_region_counts(labels.data_ptr(), truths.data_ptr(), a, h, w, int(n_segments),
-                                     int(n_truth_labels), hist.data_ptr(), area.data_ptr(), perim.data_ptr(),
-                                     torch.cuda.current_stream(labels.device).cuda_stream), "gcs_region_counts")
-    return hist.cpu().numpy(), area.cpu().numpy(), perim.cpu().numpy()
+    _lib.check(_lib.load().gcs_region_counts(labels.data_ptr(), truths.data_ptr(), a, h, w, int(n_segments),
+                                             int(n_truth_labels), hist.data_ptr(), area.data_ptr(), perim.data_ptr(),
+                                             torch.cuda.current_stream(labels.device).cuda_stream), "gcs_region_counts")
+    return hist, area, perim
 
 
-def region_scores_from_counts(hist, area, perim, n_truth, nx, ny) -> dict:
-    """metrics.py:128-146 and :188-201 arithmetic on the integer tables, giving the reference's floats.
-    ``n_truth[a]`` = max(truth_a) + 1 (metrics.py:116): only those columns of annotator a exist there.
-
-    Where the reference adds up integer-valued terms (all far below 2^53: every order gives the same float64) the loops over
-    segments are array operations here; where it adds up fractions (per annotator, per segment of the compactness) the order of
-    the reference's loops is kept, term by term. (The per-segment Python loops of round 3 cost 0.24 ms per image - more than
-    the kernels that produce the tables.)"""
-    area_f = area.astype(np.float64)
-    under = 0.
-    under_np = 0.
-    for a in range(hist.shape[0]):
-        h = hist[a][:, :int(n_truth[a])].astype(np.float64)
-        u = float(np.sum(area_f - h.max(axis=1)))                # metrics.py:129-130: integer-valued terms, exact in any order
-        u /= nx * ny
-        under += u
-        unp = float(np.sum(np.minimum(h, h.sum(axis=1)[:, None] - h)))   # metrics.py:137-139: integers, any order
-        unp /= nx * ny
-        under_np += unp
-    under /= hist.shape[0]
-    under_np /= hist.shape[0]
-    # metrics.py:194-201: compactness += 4 pi (a / max_area) a / perimeter^2 over the segments with a perimeter, in index order.
-    # Element by element the same float64 operations in the same order as the reference's scalar expression (perimeter^2 is
-    # an integer below 2^53: exact however it is computed); the sum itself stays a left-to-right loop.
-    max_area = float(nx * ny)
-    a64 = area.astype(np.int64)
-    per = perim.astype(np.float64)
-    has = per > 0
-    terms = 4 * pi * (a64[has] / max_area) * a64[has] / (per[has] * per[has])
-    compactness = 0
-    for t in terms:
-        compactness += t
-    return {"underseg": float(under), "undersegNP": float(under_np), "compactness": float(compactness)}
+def region_counts_device(labels, truths, n_segments, n_truth_labels):
+    """labels: (H,W) int32 device tensor with values < n_segments; truths: (A,H,W) 16-bit device tensor with
+    values < n_truth_labels. Returns host arrays (hist [A,n_segments,n_truth_labels], area, perimeters)."""
+    _need_labels(labels, 2)
+    _need_truths(truths, labels)
+    return tuple(x.cpu().numpy() for x in _region_tables(labels, truths, n_segments, n_truth_labels))
 
 
-def _agreement_launch(hist, img_of_d, seg_max_d, t, n_seg, stride, sums_ptr, terms_ptr, stream, device):
-    """gcs_region_agreement on device tables hist [t][n_seg][stride] (its scratch goes back to the stream-ordered allocator)."""
+def _agreement_launch(hist, img_of_d, seg_max_d, t, n_seg, stride, out):
+    """gcs_region_agreement on device tables hist [t][n_seg][stride] into the block ``out`` (int64 [8 t]: sums | terms); its
+    scratch goes back to the stream-ordered allocator."""
     import torch
     lib = _lib.load()
-    scratch = torch.empty(lib.gcs_region_agreement_scratch_bytes(t, n_seg, stride), dtype=torch.uint8, device=device)
+    scratch = torch.empty(lib.gcs_region_agreement_scratch_bytes(t, n_seg, stride), dtype=torch.uint8, device=hist.device)
     _lib.check(lib.gcs_region_agreement(hist.data_ptr(), img_of_d.data_ptr() if img_of_d is not None else None,
                                         seg_max_d.data_ptr() if seg_max_d is not None else None, t, n_seg, stride,
-                                        scratch.data_ptr(), sums_ptr, terms_ptr, stream), "gcs_region_agreement")
+                                        scratch.data_ptr(), out.data_ptr(), out.data_ptr() + t * 32,
+                                        torch.cuda.current_stream(hist.device).cuda_stream), "gcs_region_agreement")
 
 
 def region_agreement_device(labels, segments_truth) -> dict:
@@ -142,29 +214,16 @@ def region_agreement_device(labels, segments_truth) -> dict:
     import torch
     if len(segments_truth) == 0:
         raise ZeroDivisionError("no annotator maps")
-    if labels.dtype != torch.int32 or labels.dim() != 2:
-        raise ValueError("labels must be an (H,W) int32 tensor")
+    _need_labels(labels, 2)
     t, truths = _truth_stack(segments_truth, labels.device)
     h, w = labels.shape
-    if h * w < 2:
-        raise ValueError(f"region agreement needs at least 2 pixels, got {h * w}")
+    _need_two_pixels(h, w)
     a = len(t)
     n_seg = int(labels.max().item()) + 1
-    stride = int(t.max()) + 1
-    dev = labels.device
-    labels = labels.contiguous()
-    hist = torch.empty((a, n_seg, stride), dtype=torch.int32, device=dev)
-    area = torch.empty(n_seg, dtype=torch.int32, device=dev)
-    perim = torch.empty(n_seg, dtype=torch.int32, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    lib = _lib.load()
-    _lib.check(lib.gcs_region_counts(labels.data_ptr(), truths.data_ptr(), a, h, w, n_seg, stride, hist.data_ptr(),
-                                     area.data_ptr(), perim.data_ptr(), stream), "gcs_region_counts")
-    out = torch.empty(a * 8, dtype=torch.int64, device=dev)        # sums uint64 [a][4] | terms double [a][4]
-    _agreement_launch(hist, None, None, a, n_seg, stride, out.data_ptr(), out.data_ptr() + a * 32, stream, dev)
-    raw = out.cpu().numpy()
-    return agreement_from_sums(raw[:a * 4].view(np.uint64).reshape(a, 4), raw[a * 4:].view(np.float64).reshape(a, 4),
-                               [0, a], h * w)[0]
+    hist, area, perim = _region_tables(labels, truths, n_seg, int(t.max()) + 1)
+    out = torch.empty(a * 8, dtype=torch.int64, device=labels.device)
+    _agreement_launch(hist, None, None, a, n_seg, hist.shape[2], out)
+    return agreement_from_sums(*_agreement_arrays(out.cpu().numpy(), a), [0, a], h * w)[0]
 
 
 def all_scores_device(labels, segments_truth) -> dict:
@@ -185,6 +244,9 @@ def all_scores_device(labels, segments_truth) -> dict:
     return out
 
 
+# ------------------------------------------------------------------------------------------------------------------------
+# 2. A batch, truth uploaded per call
+
 def all_scores_batch_device(labels, truth, first=None, img_of=None, n_truth=None, n_segments=None, agreement=False) -> list:
     """Every number of ``evaluate.metrics.get_metrics()`` for a whole batch of device label maps in THREE launches
     (boundary maps, boundary counts, region tables) and one device-to-host copy per table, instead of a scoring call
@@ -193,13 +255,13 @@ def all_scores_batch_device(labels, truth, first=None, img_of=None, n_truth=None
     labels: (B,H,W) int32 device tensor; truth / first / img_of / n_truth: ``PackedTruth.stack(ids)`` (or the same
     layout built by hand): all annotator maps of image 0, then of image 1, ...; n_segments: max label + 1 over the
     batch (default: read from the labels; metrics.py:51 per image is the image's own max + 1, applied below).
-    agreement=True: each dict also gets "PRI", "VoI" and "covering" (SPEC.md §8) from one more launch on the same tables."""
+    agreement=True: each dict also gets "PRI", "VoI" and "covering" (SPEC.md §8) from one more launch on the same tables.
+    A ``DeviceTruth`` as ``truth``: ``all_scores_batch_resident``."""
     import torch
-    if isinstance(truth, DeviceTruth):                       # resident ground truth (round 5): nothing of it is uploaded or re-derived
+    if isinstance(truth, DeviceTruth):
         return all_scores_batch_resident(labels, truth, n_segments, agreement=agreement)
     lib = _lib.load()
-    if labels.dtype != torch.int32 or labels.dim() != 3:
-        raise ValueError("labels must be a (B,H,W) int32 tensor")
+    _need_labels(labels, 3)
     b, h, w = labels.shape
     truth = np.ascontiguousarray(truth, np.uint16)
     t = truth.shape[0]
@@ -228,38 +290,46 @@ def all_scores_batch_device(labels, truth, first=None, img_of=None, n_truth=None
     _lib.check(lib.gcs_region_counts_batch(labels.data_ptr(), truth_d.data_ptr(), first_d.data_ptr(), b, t, a_max, h, w,
                                            n_seg, stride, hist.data_ptr(), area.data_ptr(), perim.data_ptr(), stream),
                "gcs_region_counts_batch")
+    agree = None
     if agreement:
-        if h * w < 2:
-            raise ValueError(f"region agreement needs at least 2 pixels, got {h * w}")
-        agr = torch.empty(t * 8, dtype=torch.int64, device=dev)           # sums uint64 [t][4] | terms double [t][4]
-        seg_max_d = seg_max_dev.to(torch.int32).contiguous()
-        _agreement_launch(hist, img_of_d, seg_max_d, t, n_seg, stride, agr.data_ptr(), agr.data_ptr() + t * 32, stream, dev)
-        raw = agr.cpu().numpy()
-        agree = agreement_from_sums(raw[:t * 4].view(np.uint64).reshape(t, 4), raw[t * 4:].view(np.float64).reshape(t, 4),
-                                    first, h * w)
+        _need_two_pixels(h, w)
+        agr = torch.empty(t * 8, dtype=torch.int64, device=dev)
+        _agreement_launch(hist, img_of_d, seg_max_dev.to(torch.int32).contiguous(), t, n_seg, stride, agr)
+        agree = agreement_from_sums(*_agreement_arrays(agr.cpu().numpy(), t), first, h * w)
     counts = counts.cpu().numpy().astype(np.uint64)
     hist, area, perim = hist.cpu().numpy(), area.cpu().numpy(), perim.cpu().numpy()
-    out = []
+    reg = []
     for i in range(b):
-        t0, t1 = int(first[i]), int(first[i + 1])
-        c = np.concatenate([counts[i:i + 1], counts[b + 3 * t0:b + 3 * t1]])   # the single-image layout [1 + 3A]
-        n_i = int(seg_max[i]) + 1                                                # metrics.py:51
-        res = {"regions": n_i}
-        res.update(scores_from_counts(c))
-        res.update(region_scores_from_counts(hist[t0:t1, :n_i], area[i, :n_i], perim[i, :n_i], n_truth[t0:t1], h, w))
-        res["density"] = float(c[0]) / float(h * w)
-        if agreement:
-            res.update(agree[i])
-        out.append(res)
-    return out
+        t0, t1, n_i = int(first[i]), int(first[i + 1]), int(seg_max[i]) + 1      # metrics.py:51: the image's own max + 1
+        reg.append(region_scores_from_counts(hist[t0:t1, :n_i], area[i, :n_i], perim[i, :n_i], n_truth[t0:t1], h, w))
+    return _batch_scores(counts, seg_max, reg, first, h * w, agree)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
-# Resident ground truth (round 5). metrics.py:48-49 derives find_boundaries(truth) anew for every image it scores and
-# groundtruth.py:44-48 rescans the split directories per id; round 4's batched scorer still uploaded the annotator maps (40 MB per
-# 24 images) and re-derived their boundary / dilated planes on every call - 67 % of a segment + score loop. The maps are
-# constants of the data set: a DeviceTruth holds them on the device once, as uint8 maps (region tables) and as bit planes of
-# bd(T) and dil5(bd(T)) with the counts sum bd(T) (gcs_truth_prepare), and a scoring call touches nothing else of them.
+# 3. Resident ground truth. metrics.py:48-49 derives find_boundaries(truth) anew for every image it scores and groundtruth.py:44-48
+# rescans the split directories per id; the batched scorer above still uploads the annotator maps (40 MB per 24 images) and
+# re-derives their boundary / dilated planes on every call - 67 % of a segment + score loop. The maps are constants of the data
+# set: a DeviceTruth holds them on the device once, as uint8 maps (region tables) and as bit planes of bd(T) and dil5(bd(T)) with
+# the counts sum bd(T) (gcs_truth_prepare), and a scoring call touches nothing else of them.
+
+def _block_layout(b, t, cap, agreement):
+    """The result block of a resident scoring call: ({slot: (byte offset, bytes)}, total bytes), every slot on a 16-byte
+    boundary. The agreement slot (sums uint64 [t][4] | terms float64 [t][4]) comes LAST: the offsets before it do not depend on
+    it, and a call without agreement copies only the part before it."""
+    sizes = [("counts", (b + 3 * t) * 8), ("under", t * 8), ("under_np", t * 8), ("seg_max", b * 4), ("area", b * cap * 4),
+             ("perim", b * cap * 4)] + ([("agreement", t * 64)] if agreement else [])
+    offs, o = {}, 0
+    for name, nbytes in sizes:
+        offs[name] = (o, nbytes)
+        o += (nbytes + 15) // 16 * 16
+    return offs, o
+
+
+# cap: segments the tables are laid out for; dev / host: the device block and its pinned mirror, offs: their _block_layout, used:
+# the bytes in front of the agreement slot; scratch: the label maps' bit planes; hist: the contingency tables [t][cap][stride],
+# which never leave the device; agr_scratch: scratch of gcs_region_agreement, or None (a block without the agreement slot)
+_ResultBlock = namedtuple("_ResultBlock", "cap dev host offs scratch hist agr_scratch used")
+
 
 class DeviceTruth:
     """The annotator maps of a list of equally shaped images, resident on a device in the form the scorer consumes.
@@ -298,7 +368,7 @@ class DeviceTruth:
             self.first_d = torch.from_numpy(self.first).to(dev)
             self.img_of_d = torch.from_numpy(self.img_of).to(dev)
             torch.cuda.current_stream(dev).synchronize()       # t16 may go (uint8 case): the kernels that read it are done
-        self._out = None                                       # (capacity, device result block, pinned host block, views, ...)
+        self._out = None                                       # the _ResultBlock
         self._scratch = None
         self._pending = None                                   # weak reference to the submission that owns the result block
 
@@ -307,19 +377,17 @@ class DeviceTruth:
         p = self._pending() if self._pending is not None else None
         return p if p is not None and not p._collected else None
 
-    def _buffers(self, n_seg, agreement=False):
-        """ONE device block for everything a call returns (counts | under | under_np | seg_max | area | perim) and its pinned
-        mirror: one device-to-host copy of a few KB and one synchronisation per call instead of five; the contingency tables
-        stay on the device (gcs_region_reduce takes the two sums metrics.py:128-140 needs out of them).
+    def _buffers(self, n_seg, agreement=False) -> _ResultBlock:
+        """ONE device block for everything a call returns (_block_layout) and its pinned mirror: one device-to-host copy of a few
+        KB and one synchronisation per call instead of five; the contingency tables stay on the device (gcs_region_reduce takes
+        the two sums metrics.py:128-140 needs out of them).
 
         ONE entry per DeviceTruth (so one submission at a time: submit_scores_batch_resident refuses a second one while the
         first is uncollected), sized to a CAPACITY of segments (the next power of two, at least 8): a data-set loop over
         connected-region maps, whose label count differs from batch to batch, reuses it and reallocates - dropping the old
-        blocks - only when a batch needs more (the kernels take the capacity as their table stride; segments that do not occur
-        have area 0 and perimeter 0 and add nothing to any score). Returns (capacity, device block, pinned block, offsets,
-        bit-plane scratch, contingency tables, agreement scratch). agreement=True appends the per-map sums / terms of
-        gcs_region_agreement (SPEC.md §8) to the END of the block (the offsets before them do not move) and keeps its scratch;
-        a call without agreement copies only the part before them."""
+        blocks - only when a batch needs more, or needs the agreement slot and its scratch for the first time (the kernels take
+        the capacity as their table stride; segments that do not occur have area 0 and perimeter 0 and add nothing to any
+        score)."""
         import torch
         cap = 8                                                 # (k-means maps of the default k stay at their exact size)
         while cap < n_seg:
@@ -328,56 +396,23 @@ class DeviceTruth:
             self._scratch = torch.empty(_lib.load().gcs_bit_planes_bytes(self.b, self.h, self.w), dtype=torch.uint8,
                                         device=self.device)
         ent = self._out
-        if ent is None or ent[0] < cap or (agreement and ent[6] is None):
+        if ent is None or ent.cap < cap or (agreement and ent.agr_scratch is None):
             self._out = ent = None                              # the old blocks go back to the allocator first
-            b, t = self.b, self.t
-            sizes = [("counts", (b + 3 * t) * 8), ("under", t * 8), ("under_np", t * 8), ("seg_max", b * 4),
-                     ("area", b * cap * 4), ("perim", b * cap * 4)]
-            if agreement:
-                sizes += [("agr_sums", t * 32), ("agr_terms", t * 32)]
-            offs, o = {}, 0
-            for name, nbytes in sizes:
-                offs[name] = (o, nbytes)
-                o += (nbytes + 15) // 16 * 16
-            dev_blk = torch.empty(o, dtype=torch.uint8, device=self.device)
-            host_blk = torch.empty(o, dtype=torch.uint8, pin_memory=True)
-            hist = torch.empty(t * cap * self.stride, dtype=torch.int32, device=self.device)       # never leaves the device
+            offs, total = _block_layout(self.b, self.t, cap, agreement)
+            dev_blk = torch.empty(total, dtype=torch.uint8, device=self.device)
+            host_blk = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+            hist = torch.empty(self.t * cap * self.stride, dtype=torch.int32, device=self.device)
             agr_scratch = None
             if agreement:
-                agr_scratch = torch.empty(_lib.load().gcs_region_agreement_scratch_bytes(t, cap, self.stride), dtype=torch.uint8,
-                                          device=self.device)
-            ent = self._out = (cap, dev_blk, host_blk, offs, self._scratch, hist, agr_scratch)
+                agr_scratch = torch.empty(_lib.load().gcs_region_agreement_scratch_bytes(self.t, cap, self.stride),
+                                          dtype=torch.uint8, device=self.device)
+            ent = self._out = _ResultBlock(cap, dev_blk, host_blk, offs, self._scratch, hist, agr_scratch,
+                                           offs["agreement"][0] if agreement else total)
         return ent
 
 
-def _region_scores_batch(under, under_np, area, perim, first, nx, ny):
-    """``region_scores_from_counts`` for a whole batch: under / under_np uint64 [T] = the integer sums of gcs_region_reduce
-    (metrics.py:129-130, :137-139; exact in any order), area / perim [B][n_seg]. The sums of fractions keep the reference's
-    order, term by term (metrics.py:131, :140, :194-201)."""
-    b = len(first) - 1
-    u_t = under.astype(np.float64) / (nx * ny)
-    unp_t = under_np.astype(np.float64) / (nx * ny)
-    max_area = float(nx * ny)
-    a64 = area.astype(np.int64)
-    per = perim.astype(np.float64)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        terms = 4 * pi * (a64 / max_area) * a64 / (per * per)                    # metrics.py:199, element by element
-    out = []
-    u_t, unp_t, first = u_t.tolist(), unp_t.tolist(), np.asarray(first).tolist()  # Python floats: the same IEEE doubles, no
-    terms, has = terms.tolist(), (per > 0).tolist()                              # NumPy scalar boxing per addition
-    for i in range(b):
-        t0, t1 = first[i], first[i + 1]
-        under_i = 0.
-        under_np_i = 0.
-        for t in range(t0, t1):                                                  # metrics.py:131,140: += in annotator order
-            under_i += u_t[t]
-            under_np_i += unp_t[t]
-        compactness = 0
-        for term, ok in zip(terms[i], has[i]):                                   # metrics.py:194-201: index order
-            if ok:
-                compactness += term
-        out.append({"underseg": under_i / (t1 - t0), "undersegNP": under_np_i / (t1 - t0), "compactness": float(compactness)})
-    return out
+# host / offs / cap: the pinned result block, its layout and capacity; event: recorded behind the result copy
+_Submission = namedtuple("_Submission", "truth b h w n_seg cap host offs event agreement")
 
 
 class _PendingScores:
@@ -387,9 +422,8 @@ class _PendingScores:
     next batch against the SAME DeviceTruth. Submitting a batch against ANOTHER DeviceTruth before collecting this one is the
     intended pipelining: its kernels run under this one's host arithmetic."""
 
-    def __init__(self, truth, b, h, w, n_seg, host_blk, offs, event, cap=None, agreement=False):
-        self._a = (truth, b, h, w, n_seg, host_blk, offs, event, cap or n_seg)
-        self._agreement = agreement
+    def __init__(self, submission):
+        self._s = submission
         self._collected = False
 
     def result(self) -> list:
@@ -397,48 +431,25 @@ class _PendingScores:
         reference raises for a degenerate image)."""
         if self._collected:
             raise RuntimeError("this submission has been collected already: its result block may hold a later batch by now")
-        self._a[7].synchronize()                                     # the event recorded behind the result copy
+        self._s.event.synchronize()
         try:
             return self._finish()
         finally:
             self._collected = True
 
     def _finish(self) -> list:
-        truth, b, h, w, n_seg, host_blk, offs, event, cap = self._a
-        raw = host_blk.numpy()
+        s, offs = self._s, self._s.offs
+        raw = s.host.numpy()
         view = lambda k, dt: raw[offs[k][0]:offs[k][0] + offs[k][1]].view(dt)
-        counts = view("counts", np.uint64)
         seg_max = view("seg_max", np.int32)
-        if int(seg_max.max()) >= n_seg:
-            raise ValueError(f"a label map holds label {int(seg_max.max())} but n_segments = {n_seg}")
-        area = view("area", np.int32).reshape(b, cap)[:, :n_seg]     # tables are laid out at the capacity; columns >= n_seg are zero
-        perim = view("perim", np.int32).reshape(b, cap)[:, :n_seg]
-        reg = _region_scores_batch(view("under", np.uint64), view("under_np", np.uint64), area, perim, truth.first, h, w)
-        if self._agreement:
-            agree = agreement_from_sums(view("agr_sums", np.uint64).reshape(-1, 4), view("agr_terms", np.float64).reshape(-1, 4),
-                                        truth.first, h * w)
-        out = []
-        cf = counts.astype(np.float64).tolist()                      # counts < 2^53: exact; Python floats from here on
-        first = truth.first.tolist()
-        for i in range(b):
-            t0, t1 = first[i], first[i + 1]
-            g = cf[i]
-            recall = 0
-            precision = 0
-            for t in range(t0, t1):                                  # metrics.py:69-74, :88-96 in annotator order
-                recall += cf[b + 3 * t] / cf[b + 3 * t + 1]          # ZeroDivisionError as metrics.py:72
-                precision += cf[b + 3 * t + 2] / g                   # ZeroDivisionError as metrics.py:94
-            recall /= t1 - t0
-            precision /= t1 - t0
-            sm = recall + precision
-            res = {"regions": int(seg_max[i]) + 1, "recall": recall, "precision": precision,
-                   "fmeasure": 0.0 if sm == 0 else 2.0 * precision * recall / sm}
-            res.update(reg[i])
-            res["density"] = g / float(h * w)
-            if self._agreement:
-                res.update(agree[i])
-            out.append(res)
-        return out
+        if int(seg_max.max()) >= s.n_seg:
+            raise ValueError(f"a label map holds label {int(seg_max.max())} but n_segments = {s.n_seg}")
+        area = view("area", np.int32).reshape(s.b, s.cap)[:, :s.n_seg]     # laid out at the capacity; columns >= n_seg are zero
+        perim = view("perim", np.int32).reshape(s.b, s.cap)[:, :s.n_seg]
+        first = s.truth.first
+        reg = _region_scores_batch(view("under", np.uint64), view("under_np", np.uint64), area, perim, first, s.h, s.w)
+        agree = agreement_from_sums(*_agreement_arrays(view("agreement", np.int64), s.truth.t), first, s.h * s.w) if s.agreement else None
+        return _batch_scores(view("counts", np.uint64), seg_max, reg, first, s.h * s.w, agree)   # counts < 2^53: exact floats
 
 
 def submit_scores_batch_resident(labels, truth: DeviceTruth, n_segments=None, agreement=False) -> _PendingScores:
@@ -451,44 +462,39 @@ def submit_scores_batch_resident(labels, truth: DeviceTruth, n_segments=None, ag
     single copy."""
     import torch
     lib = _lib.load()
-    if labels.dtype != torch.int32 or labels.dim() != 3:
-        raise ValueError("labels must be a (B,H,W) int32 tensor")
+    _need_labels(labels, 3)
     b, h, w = labels.shape
-    if (b, h, w) != (truth.b, truth.h, truth.w) or labels.device != truth.device:
-        raise ValueError("label batch does not match the resident truth (images, shape or device)")
+    _need_match((b, h, w), labels.device, truth, "label")
     labels = labels.contiguous()
     n_seg = int(n_segments) if n_segments is not None else int(labels.max().item()) + 1
-    if agreement and h * w < 2:
-        raise ValueError(f"region agreement needs at least 2 pixels, got {h * w}")
+    if agreement:
+        _need_two_pixels(h, w)
     if truth._uncollected() is not None:
         raise RuntimeError("one result block per DeviceTruth: collect the earlier submission with .result() (or drop it) before "
                            "submitting the next batch against the same DeviceTruth")
-    cap, dev_blk, host_blk, offs, scratch, hist_d, agr_scratch = truth._buffers(n_seg, agreement)
-    base = dev_blk.data_ptr()
-    ptr = {k: base + o for k, (o, _) in offs.items()}
+    blk = truth._buffers(n_seg, agreement)
+    base = blk.dev.data_ptr()
+    ptr = {k: base + o for k, (o, _) in blk.offs.items()}
     with torch.cuda.device(truth.device):
         stream = torch.cuda.current_stream(truth.device)
         _lib.check(lib.gcs_score_batch_resident(labels.data_ptr(), truth.planes.data_ptr(), truth.bd_counts.data_ptr(),
                                                 truth.maps.data_ptr(), 1 if truth.u8 else 0, truth.first_d.data_ptr(),
-                                                truth.img_of_d.data_ptr(), b, truth.t, truth.a_max, h, w, cap, truth.stride,
-                                                scratch.data_ptr(), hist_d.data_ptr(), ptr["counts"], ptr["seg_max"], ptr["area"],
-                                                ptr["perim"], ptr["under"], ptr["under_np"], stream.cuda_stream),
+                                                truth.img_of_d.data_ptr(), b, truth.t, truth.a_max, h, w, blk.cap, truth.stride,
+                                                blk.scratch.data_ptr(), blk.hist.data_ptr(), ptr["counts"], ptr["seg_max"],
+                                                ptr["area"], ptr["perim"], ptr["under"], ptr["under_np"], stream.cuda_stream),
                    "gcs_score_batch_resident")
         if agreement:
-            _lib.check(lib.gcs_region_agreement(hist_d.data_ptr(), truth.img_of_d.data_ptr(), ptr["seg_max"], truth.t, cap,
-                                                truth.stride, agr_scratch.data_ptr(), ptr["agr_sums"], ptr["agr_terms"],
-                                                stream.cuda_stream), "gcs_region_agreement")
-            host_blk.copy_(dev_blk, non_blocking=True)
-        else:                                                   # the block may carry agreement slots of an earlier call
-            used = offs["perim"][0] + offs["perim"][1]
-            used = (used + 15) // 16 * 16
-            if used == dev_blk.numel():
-                host_blk.copy_(dev_blk, non_blocking=True)
-            else:
-                host_blk[:used].copy_(dev_blk[:used], non_blocking=True)
+            _lib.check(lib.gcs_region_agreement(blk.hist.data_ptr(), truth.img_of_d.data_ptr(), ptr["seg_max"], truth.t, blk.cap,
+                                                truth.stride, blk.agr_scratch.data_ptr(), ptr["agreement"],
+                                                ptr["agreement"] + truth.t * 32, stream.cuda_stream), "gcs_region_agreement")
+        used = blk.dev.numel() if agreement else blk.used       # the block may carry the agreement slot of an earlier call
+        if used == blk.dev.numel():
+            blk.host.copy_(blk.dev, non_blocking=True)
+        else:
+            blk.host[:used].copy_(blk.dev[:used], non_blocking=True)
         event = torch.cuda.Event()
         event.record(stream)
-    pending = _PendingScores(truth, b, h, w, n_seg, host_blk, offs, event, cap, agreement)
+    pending = _PendingScores(_Submission(truth, b, h, w, n_seg, blk.cap, blk.host, blk.offs, event, agreement))
     truth._pending = weakref.ref(pending)
     return pending
 
@@ -501,7 +507,8 @@ def all_scores_batch_resident(labels, truth: DeviceTruth, n_segments=None, agree
 
 
 # ------------------------------------------------------------------------------------------------------------------------
-# Every cut of a region tree at once (SPEC.md §15): three histograms of the contour map per image, one pass over the map.
+# 4a. Boundary scores of every cut of a region tree at once (SPEC.md §15): three histograms of the contour map per image, one
+# pass over the map.
 
 def boundary_sweep_resident(contours, alive, truth: DeviceTruth):
     """contours: (B,H,W) int32 device tensor of ``Segmenter.contour_map_device``; alive: the (B,) int32 tensor beside it; truth: the resident ground truth of the same images. Returns host arrays
@@ -510,11 +517,9 @@ def boundary_sweep_resident(contours, alive, truth: DeviceTruth):
     its one-submission rule are not touched."""
     import torch
     lib = _lib.load()
-    if contours.dtype != torch.int32 or contours.dim() != 3:
-        raise ValueError("contours must be a (B,H,W) int32 tensor")
+    _need_labels(contours, 3, "contours")
     b, h, w = contours.shape
-    if (b, h, w) != (truth.b, truth.h, truth.w) or contours.device != truth.device:
-        raise ValueError("contour batch does not match the resident truth (images, shape or device)")
+    _need_match((b, h, w), contours.device, truth, "contour")
     if tuple(alive.shape) != (b,):
         raise ValueError("alive must be a (B,) tensor")
     if h > 4096 or w > 4096:
@@ -529,9 +534,6 @@ def boundary_sweep_resident(contours, alive, truth: DeviceTruth):
         raw = hist.cpu().numpy().view(np.uint32)
     ann = raw[b:].reshape(truth.t, 2, k + 1)
     return raw[:b].copy(), ann[:, 0].copy(), ann[:, 1].copy()
-
-
-SWEEP_LEVELS = 4096                                              # the most labels a region tree has (SPEC.md §14)
 
 
 def sweep_counts(hists, alive, bd_counts, first, regions) -> np.ndarray:
@@ -565,24 +567,17 @@ def sweep_counts(hists, alive, bd_counts, first, regions) -> np.ndarray:
 def sweep_scores(hists, alive, bd_counts, first, regions) -> list:
     """Per image a list with one ``{"recall", "precision", "fmeasure"}`` per R of ``regions``: the floats
     ``all_scores_batch_resident`` gives for ``cut_regions_device(..., R)`` (the same integer counts through the same float
-    operations in the same order, ``scores_from_counts``). ZeroDivisionError where the reference raises it: a cut without a
+    operations in the same order, ``_boundary_scores``). ZeroDivisionError where the reference raises it: a cut without a
     boundary pixel (R = 1), an annotator map without one."""
-    counts = sweep_counts(hists, alive, bd_counts, first, regions)
-    first = np.asarray(first).astype(np.int64)
+    counts = sweep_counts(hists, alive, bd_counts, first, regions).astype(np.float64).tolist()
+    first = np.asarray(first).astype(np.int64).tolist()
     b = len(first) - 1
-    out = []
-    for i in range(b):
-        t0, t1 = int(first[i]), int(first[i + 1])
-        out.append([scores_from_counts(np.concatenate([c[i:i + 1], c[b + 3 * t0:b + 3 * t1]])) for c in counts])
-    return out
+    return [[_boundary_scores(c[i], c[b + 3 * first[i]:b + 3 * first[i + 1]]) for c in counts] for i in range(b)]
 
 
 # ------------------------------------------------------------------------------------------------------------------------
-# The region metrics of every cut of a region tree at once (SPEC.md §16): the leaf tables from one pass over the pixels, every
-# coarser table from the merge list by adding rows.
-
-SWEEP_CUTS = 64                                                  # the most cuts one gcs_region_sweep call takes
-
+# 4b. The region metrics of every cut of a region tree at once (SPEC.md §16): the leaf tables from one pass over the pixels,
+# every coarser table from the merge list by adding rows.
 
 def region_sweep_resident(labels, merges, alive, truth: DeviceTruth, regions):
     """labels (B,H,W) int32, merges (B, K-1, 2) int32, alive (B,) int32: the device tensors ``Segmenter.region_tree_device`` returned;
@@ -592,11 +587,9 @@ def region_sweep_resident(labels, merges, alive, truth: DeviceTruth, regions):
     (the raw cuts: ``connectivity`` and ``min_region_size`` are not reflected). Two launches (the leaf tables with K rows; the
     sweep) and one download. Buffers of its own: ``truth``'s result block and its one-submission rule are not touched."""
     import torch
-    if labels.dtype != torch.int32 or labels.dim() != 3:
-        raise ValueError("labels must be a (B,H,W) int32 tensor")
+    _need_labels(labels, 3)
     b, h, w = labels.shape
-    if (b, h, w) != (truth.b, truth.h, truth.w) or labels.device != truth.device:
-        raise ValueError("label batch does not match the resident truth (images, shape or device)")
+    _need_match((b, h, w), labels.device, truth, "label")
     if merges.dtype != torch.int32 or merges.dim() != 3 or merges.shape[0] != b or merges.shape[2] != 2 or \
             not 1 <= merges.shape[1] + 1 <= SWEEP_LEVELS:
         raise ValueError(f"merges must be a (B, K - 1, 2) int32 tensor with K in 1..{SWEEP_LEVELS}")
@@ -611,8 +604,7 @@ def region_sweep_resident(labels, merges, alive, truth: DeviceTruth, regions):
         raise ValueError("regions must be a list of integers") from None
     if not same or not 1 <= len(regs) <= SWEEP_CUTS or len(set(regs)) != len(regs) or min(regs) < 1 or max(regs) > SWEEP_LEVELS:
         raise ValueError(f"regions must be 1..{SWEEP_CUTS} distinct integers in 1..{SWEEP_LEVELS}")
-    if h * w < 2:
-        raise ValueError(f"region agreement needs at least 2 pixels, got {h * w}")
+    _need_two_pixels(h, w)
     k, t, stride, n = merges.shape[1] + 1, truth.t, truth.stride, len(regs)
     if t * k * stride > 0x3fffffff:
         raise ValueError(f"the leaf tables [{t}][{k}][{stride}] exceed 2^30 counters")
@@ -629,15 +621,15 @@ def region_sweep_resident(labels, merges, alive, truth: DeviceTruth, regions):
                           hist.data_ptr(), side.data_ptr(), side.data_ptr() + 4 * b * k, stream), "gcs_region_counts_batch")
         regs_d = torch.tensor([regs[j] for j in order], dtype=torch.int32).to(dev)
         ws = torch.empty(lib.gcs_region_sweep_workspace_bytes(t, k, stride, n), dtype=torch.uint8, device=dev)
-        out = torch.empty(2 * n * t * 4, dtype=torch.int64, device=dev)          # sums uint64 [n][t][4] | terms double [n][t][4]
+        out = torch.empty(2 * n * t * 4, dtype=torch.int64, device=dev)          # an agreement block of n t maps, cut-major
         _lib.check(lib.gcs_region_sweep(hist.data_ptr(), merges.data_ptr() if k > 1 else None, alive.data_ptr(),
                                         truth.img_of_d.data_ptr(), regs_d.data_ptr(), b, t, k, stride, n, ws.data_ptr(),
                                         out.data_ptr(), out.data_ptr() + n * t * 32, stream), "gcs_region_sweep")
         raw = out.cpu().numpy()
     sums = np.empty((n, t, 4), np.uint64)
     terms = np.empty((n, t, 4), np.float64)
-    sums[order] = raw[:n * t * 4].view(np.uint64).reshape(n, t, 4)
-    terms[order] = raw[n * t * 4:].view(np.float64).reshape(n, t, 4)
+    for dst, src in zip((sums, terms), _agreement_arrays(raw, n * t)):
+        dst[order] = src.reshape(n, t, 4)
     return sums, terms
 
 

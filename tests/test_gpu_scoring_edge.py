@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import scoring_edge
+from scoring_edge import _assemble, _np_counts, _np_planes, _np_reduce, _np_tables, _np_tables_batch
 
 pytestmark = pytest.mark.gpu
 CASES = scoring_edge.load()
@@ -49,71 +50,8 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-def _assemble(items):
-    """[(label map, annotator maps [A][H][W])] -> labs [B][H][W] int32, truth [T][H][W] uint16, first [B+1], img_of [T]."""
-    labs = np.stack([l for l, _ in items]).astype(np.int32)
-    truth = np.concatenate([t for _, t in items]).astype(np.uint16)
-    first = np.concatenate([[0], np.cumsum([len(t) for _, t in items])]).astype(np.int32)
-    img_of = np.repeat(np.arange(len(items)), [len(t) for _, t in items]).astype(np.int32)
-    return labs, truth, first, img_of
-
-
 def _by_shape(shape, want=lambda key, gold: True):
     return [(k, l, t, g) for k, l, t, g in CASES if k.startswith(shape + "/") and want(k, g)]
-
-
-# ------------------------------------------------------------------------------------------------ restatements (host)
-def _np_counts(labs, truth, img_of):
-    """counts [B + 3T] of gcs.h from scipy: sum bd(L_b); per map t of image b: sum dil5(bd(L_b)) & bd(T_t), sum bd(T_t),
-    sum bd(L_b) & dil5(bd(T_t))."""
-    from gabor_color_image_segmentation_amd import evaluate as ev
-    bd = [ev.find_boundaries(l) for l in labs]
-    dil = [ev._dilate(b, 5) for b in bd]
-    out = [int(b.sum()) for b in bd]
-    for t, b in zip(truth, img_of):
-        tb = ev.find_boundaries(t)
-        out += [int((dil[b] & tb).sum()), int(tb.sum()), int((bd[b] & ev._dilate(tb, 5)).sum())]
-    return np.array(out, np.int64)
-
-
-def _np_tables(lab, truths, n_seg, stride):
-    """hist [A][n_seg][stride], area, perim [n_seg] of one image: np.bincount and evaluate.metrics.perimeter. Pixels whose
-    label is >= n_seg are in no table; pixels whose annotator label is >= stride are missing from hist alone."""
-    from gabor_color_image_segmentation_amd.evaluate import metrics
-    lab = np.asarray(lab).astype(np.int64)
-    ok = lab < n_seg
-    area = np.bincount(lab[ok], minlength=n_seg)
-    m = metrics(None, lab, [])
-    m.perimeter()                                                    # per label 0 .. max(lab), neighbours compared on the full map
-    perim = np.zeros(n_seg, np.int64)
-    k = min(n_seg, len(m.perimeters))
-    perim[:k] = m.perimeters[:k].astype(np.int64)
-    hist = np.zeros((len(truths), n_seg, stride), np.int64)
-    for a, t in enumerate(truths):
-        t = np.asarray(t).astype(np.int64)
-        both = ok & (t < stride)
-        hist[a] = np.bincount(lab[both] * stride + t[both], minlength=n_seg * stride).reshape(n_seg, stride)
-    return hist, area, perim
-
-
-def _np_tables_batch(labs, truth, first, n_seg, stride):
-    parts = [_np_tables(labs[b], truth[first[b]:first[b + 1]], n_seg, stride) for b in range(len(labs))]
-    return (np.concatenate([p[0] for p in parts]), np.stack([p[1] for p in parts]), np.stack([p[2] for p in parts]))
-
-
-def _np_reduce(hist, area, img_of):
-    """under [T], under_np [T] of gcs_region_reduce from the tables (metrics.py:129-130, :137-139)."""
-    hist = hist.astype(np.int64)
-    under = (area.astype(np.int64)[img_of] - hist.max(axis=2)).sum(axis=1)
-    under_np = np.minimum(hist, hist.sum(axis=2, keepdims=True) - hist).sum(axis=(1, 2))
-    return under, under_np
-
-
-def _np_planes(maps):
-    """bd and dil5 planes [2][M][H][W] (bool) from scipy."""
-    from gabor_color_image_segmentation_amd import evaluate as ev
-    bd = np.stack([ev.find_boundaries(m) for m in maps])
-    return np.stack([bd, np.stack([ev._dilate(b, 5) for b in bd])])
 
 
 def _unpack(words, m, h, w):

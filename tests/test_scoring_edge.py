@@ -1,5 +1,7 @@
 """The scoring mirror against the reference's own metrics class at the edge shapes of tests/golden/scoring_edge_golden.json
-(1x70 ... 65x129: single rows and columns, tile and plane-word multiples and their neighbours), raising cases included."""
+(1x70 ... 65x129: single rows and columns, tile and plane-word multiples and their neighbours), raising cases included; and the
+GPU scorer's host arithmetic (evaluate_gpu) on the integer counts and tables NumPy / scipy give for the same cases."""
+import numpy as np
 import pytest
 
 from gabor_color_image_segmentation_amd.evaluate import metrics
@@ -40,3 +42,39 @@ def test_mirror_equals_the_reference_at_edge_shapes(key, lab, truth, ref):
         assert got[k] == ref[k], k                     # same integer counts, same float divisions
     for k in scoring_edge.CLOSE:
         assert got[k] == pytest.approx(ref[k], rel=1e-12), k
+
+
+@pytest.mark.parametrize("key,lab,truth,ref", CASES, ids=[c[0] for c in CASES])
+def test_scorer_host_arithmetic_equals_the_reference_at_edge_shapes(key, lab, truth, ref):
+    """The integer counts and tables of the restatements (what the kernels are held to, bit for bit, in test_gpu_scoring_edge.py)
+    through the single-image arithmetic (scores_from_counts, region_scores_from_counts) and, as a one-image batch, through the
+    batch arithmetic of the batched and resident scorers: the fixture's floats (its own EXACT / CLOSE split), the two forms equal
+    to each other; a zero denominator (a constant label map, an annotator map without a boundary, no annotators) raises what the
+    reference raised."""
+    from gabor_color_image_segmentation_amd import evaluate_gpu as eg
+    labs, stack, first, img_of = scoring_edge._assemble([(lab, truth)])
+    counts = scoring_edge._np_counts(labs, stack, img_of).astype(np.uint64)
+    seg_max, (h, w) = [int(lab.max())], lab.shape
+    if "raises" in ref:
+        with pytest.raises(scoring_edge.ERRORS[ref["raises"]]):
+            eg.scores_from_counts(counts)
+        with pytest.raises(scoring_edge.ERRORS[ref["raises"]]):
+            eg._batch_scores(counts, seg_max, [{}], first, h * w)
+        return
+    n_seg, n_truth = seg_max[0] + 1, [int(t.max()) + 1 for t in truth]
+    hist, area, perim = scoring_edge._np_tables(lab, truth, n_seg, max(n_truth))
+    single = {"regions": n_seg, **eg.scores_from_counts(counts), **eg.region_scores_from_counts(hist, area, perim, n_truth, h, w),
+              "density": float(counts[0]) / float(h * w)}
+    hist_b, area_b, perim_b = scoring_edge._np_tables_batch(labs, stack, first, n_seg, max(n_truth))
+    under, under_np = scoring_edge._np_reduce(hist_b, area_b, img_of)
+    reg = eg._region_scores_batch(under.astype(np.uint64), under_np.astype(np.uint64), area_b, perim_b, first, h, w)
+    (batch,) = eg._batch_scores(counts, seg_max, reg, first, h * w)
+    for got in (single, batch):
+        assert got["regions"] == ref["regions"]
+        for k in scoring_edge.EXACT:
+            assert got[k] == ref[k], k
+        for k in scoring_edge.CLOSE:
+            assert got[k] == pytest.approx(ref[k], rel=1e-12), k
+    for k in scoring_edge.CLOSE:
+        assert single[k] == batch[k], k
+    assert single["fmeasure"] == batch["fmeasure"]

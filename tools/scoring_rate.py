@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the batched GPU scorer (gcs_boundary_counts_batch + gcs_region_counts_batch behind
 evaluate_gpu.all_scores_batch_device on resident ground truth, evaluate_gpu.DeviceTruth) and of the segment + score loop (`examples/bsd_eval.py --val`) on the 24 packed BSD500
-val images: label maps stay on the device, ground truth comes from the 500-id pack. Prints one JSON line; `bench.py` embeds
-the same figures (`scoring`)."""
+val images: label maps stay on the device, ground truth comes from the 500-id pack. Prints one JSON line."""
 import json, os, sys, time
 import numpy as np
 import torch
