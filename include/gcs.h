@@ -191,6 +191,11 @@ int gcs_selftest_isqrt(unsigned n_max, unsigned *bad_dev, gcs_stream_t stream);
  * count, which can only lower the pixels per workgroup); B * H * W / that many pixels per workgroup must stay below the
  * int32 accumulator bound (262 144 pixels). 0 for a bad shape. */
 int gcs_selftest_native_parts(int B, int H, int W);
+/* Test hook (host only, added within ABI 18): which kernel gcs_kmeans_assign_accumulate / gcs_kmeans_assign_raster run for this
+ * bank and k, as a display name - split<KT,NR[,L0T]>, narrow<KT,NST>, wide<KT,NST>, wide8w<1,5>, native<NL,MINB,N0>, generic (a
+ * static string) -, or NULL for a shape, bank or k they refuse. gcs_kmeans_fused_workspace_bytes != 0 exactly for split<1,3> and
+ * split<1,3,2>. Launches nothing and touches no device. */
+const char *gcs_selftest_pass_kernel(int H, int W, int n_scales, int n_orient, int k);
 
 /* ---- boundary scoring of one image -------------------------------------- */
 

@@ -10,7 +10,7 @@ rows, the centroids in `cent` and in the array the pass writes, the array and th
 banks and images of tests/hot_banks.py (values >= 32768, flagged beside unflagged tiles), and the tests assert that their inputs
 hold all that.
 
-Mutants of csrc/kmeans.hip, each built in a scratch copy, run once against this file and once against
+Mutants of csrc/lloyd_mfma.hip, each built in a scratch copy, run once against this file and once against
 tests/test_gpu_self_updating_passes.py as it was before this file (failed tests: here / there):
 (1) the prologue's fold keeps the sum in 32 bits: 23 / 0; (2) `s / c` in place of `(2 s + c) / (2 c)`: 38 / 22; (3) an empty cluster
 reads the centroid array the pass writes: 39 / 1; (4) the prologue's clear drops the gridDim.y factor (per-image: set 0 only):

@@ -5,10 +5,10 @@ the public C ABI. Stage by stage, so that a failure names its kernel; everything
 oracle, tests/smooth_ref.py or plain int64 / Python integers, and every test asserts that its own inputs hold the values it
 is about (e.g. ``ref.max() >= 32768``).
 
-Lloyd-pass arms (csrc/kmeans.hip, lloyd_pass): the ids of PASS_CASES name the instantiation each (bank, k) selects. Of the 22
-instantiations, narrow<1,9>, narrow<1,10> and narrow<2,10> cannot be selected in the default build (a bank with D < 80 on
-three or more levels has at most 1 230 staging chunks per tile; they serve -DGCS_NO_SPLIT builds); the other 19 and the generic
-pass each have a case here.
+Lloyd-pass arms (csrc/lloyd_pass.h, gcs_pass_kernel): the ids of PASS_CASES name the instantiation each (bank, k) selects
+(tests/test_pass_kernel_choice.py holds them to it). Of the 22 instantiations, narrow<1,9>, narrow<1,10> and narrow<2,10> cannot be
+selected in the default build (a bank with D < 80 on three or more levels has at most 1 230 staging chunks per tile) and are
+compiled into -DGCS_NO_SPLIT builds only; the other 19 and the generic pass each have a case here.
 
 Mutants of the library, run once against this file and against the suite as it was before it (failed tests):
 (a) the split pass's TOP unpack keeps 3 bits: 15 here, none before; (b) the Gabor split store keeps 3 bits of the TOP nibble: 30,

@@ -140,7 +140,7 @@ def test_lds_bank_model_matches_the_deep_bank_kernel_constants():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, "gabor_color_image_segmentation_amd", "csrc", "kmeans.hip")).read()
+    src = open(os.path.join(root, "gabor_color_image_segmentation_amd", "csrc", "lloyd_native.hip")).read()
     m = re.search(r"NV_P1 = (\d+) \+ (\d+), NV_P2 = (\d+) \+ (\d+), NV_P3 = (\d+);", src)
     p1, p2 = int(m.group(1)) + int(m.group(2)), int(m.group(3)) + int(m.group(4))
     nsl = int(re.search(r"constexpr int NV_APAT_SLOTS = (\d+);", src).group(1))
@@ -155,7 +155,7 @@ def test_lds_bank_model_matches_the_deep_bank_kernel_constants():
     assert re.search(r"total\s+624", first), first
 
 
-def test_lds_bank_model_of_the_split_slab_pass_matches_its_constants_and_the_measured_conflicts():
+def test_lds_bank_model_of_the_split_slab_pass_matches_its_constants_and_the_measured_conflicts(built):
     """tools/design/lds_bank_model_narrow.py restates the LDS accesses of the split-slab Lloyd pass with level 1 kept compact
     (round 6) against the lane groups the LDS serves. Its pitches and swizzle are the kernel's; the transposed reads, the 16-byte
     update reads and the label reads are conflict-free; and the three builds of round 6 reproduce what SQ_LDS_BANK_CONFLICT measured
@@ -165,12 +165,15 @@ def test_lds_bank_model_of_the_split_slab_pass_matches_its_constants_and_the_mea
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, "gabor_color_image_segmentation_amd", "csrc", "kmeans.hip")).read()
+    csrc = os.path.join(root, "gabor_color_image_segmentation_amd", "csrc")
+    hdr, src = open(os.path.join(csrc, "lloyd_pass.h")).read(), open(os.path.join(csrc, "lloyd_mfma.hip")).read()
     model = open(os.path.join(root, "tools", "design", "lds_bank_model_narrow.py")).read()
-    assert "constexpr int KP_PITCH = KP_TP * 2 + 64;" in src and "KP_PITCH = KP_TP * 2 + 64" in model
-    assert "constexpr int KP_P1 = 128 + 48;" in src and "KP_P1 = 128 + 48" in model
+    assert "constexpr int KP_PITCH = KP_TP * 2 + 64;" in hdr and "KP_PITCH = KP_TP * 2 + 64" in model
+    assert "constexpr int KP_P1 = 128 + 48;" in hdr and "KP_P1 = 128 + 48" in model
     assert "((r >> 3) & 1) * 32" in src and "((r >> 3) & 1) * 32" in model                  # row_swz
-    assert "GCS_KP_LAUNCHS(1, 3, 2)" in src and "L0T = 0 if B64 else 2" in model            # 16-byte reads for two plane tiles
+    from gabor_color_image_segmentation_amd import _lib
+    assert _lib.load().gcs_selftest_pass_kernel(321, 481, 4, 6, 8) == b"split<1,3,2>"       # 16-byte reads for two plane tiles
+    assert "L0T = 0 if B64 else 2" in model
     tool = os.path.join(root, "tools", "design", "lds_bank_model_narrow.py")
 
     def run(*flags):

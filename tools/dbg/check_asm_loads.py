@@ -3,7 +3,7 @@
 global_load into v[a:b] and the s_waitcnt vmcnt(..) that follows it in the listing no instruction may read or write one of those
 registers (hipcc does not know the load is in flight: a register copy there would move stale data; round 6 met exactly that).
 Linear scan of the listing - the tile loop is laid out in program order -: a report, not a proof.
-usage: check_asm_loads.py kmeans-hip-amdgcn-amd-amdhsa-gfx950.s [kernel-name-substring]"""
+usage: check_asm_loads.py lloyd_mfma-hip-amdgcn-amd-amdhsa-gfx950.s [kernel-name-substring]   (`make asm`, tools/kres.sh lloyd_mfma)"""
 import re, sys
 
 path = sys.argv[1]

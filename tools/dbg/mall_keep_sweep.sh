@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round 6: how many bytes at the end of a sweep should the Lloyd passes load WITHOUT the nontemporal hint (csrc/kmeans.hip,
+# Round 6: how many bytes at the end of a sweep should the Lloyd passes load WITHOUT the nontemporal hint (csrc/lloyd_pass.h,
 # kp_nt_limit)? One variant build per budget (-DGCS_KP_MALL_KEEP_MB=n; 0 = every load nt, 100000 = every load plain), then
 # bench.py's steady state (4x6 bank, split-slab pass) and tools/stage_time.py (8x8 bank, deep-bank pass), two interleaved rounds.
 #   here:        bash tools/dbg/mall_keep_sweep.sh build            (build_ab/keep<n>.so)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Where does a wave of the narrow Lloyd pass spend a tile? (round 6)
+"""Where does a wave of the narrow Lloyd pass (csrc/lloyd_mfma.hip) spend a tile? (round 6)
 
     bash tools/build_variant.sh phases -DGCS_KP_PHASES && python tools/dbg/pass_phases.py build_ab/phases.so
 

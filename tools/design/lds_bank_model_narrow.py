@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """LDS bank-conflict model of the split-slab Lloyd pass with level 1 kept compact (kmeans_pass_mfma_kernel<1, 3, 5, 4, true, L0T>,
-csrc/kmeans.hip, `CL1`), access by access, for the 4x6 bank (36 level-0 planes, 36 level-1 planes, the count row, 7 rows of padding).
+csrc/lloyd_mfma.hip, `CL1`), access by access, for the 4x6 bank (36 level-0 planes, 36 level-1 planes, the count row, 7 rows of padding).
 
 Rules: MI355X_MICROARCH.md, section LDS (see tools/design/lds_bank_model.py). Prints the extra LDS cycles per TILE (four waves) that
 SQ_LDS_BANK_CONFLICT counts, for the layout that ships and, with flags, for its predecessors of round 6:

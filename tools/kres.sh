@@ -1,6 +1,6 @@
 #!/bin/bash
 # Compile one translation unit of libgcs.so with -save-temps under /tmp and print per-kernel VGPR / spill / LDS figures:
-#   tools/kres.sh kmeans [grep pattern] [extra hipcc flags]
+#   tools/kres.sh lloyd_mfma [grep pattern] [extra hipcc flags]      (kmeans, lloyd_mfma, lloyd_native, gabor, ...)
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 f=${1:-kmeans}; pat=${2:-.}; shift; shift
 mkdir -p /tmp/kres && cd /tmp/kres && rm -f $f-*
