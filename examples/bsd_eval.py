@@ -39,6 +39,9 @@ then OIS (every image at its own best R) and ODS (one R for the whole set) over 
 `--regions R[,R...] --sweep --agreement`: PRI, VoI and covering columns beside them, from the same tree (SPEC.md §16: the contingency
 tables of the superpixels once per batch, the table of every cut from the merge list, `evaluate_gpu.region_sweep_resident`), and the ODS /
 OIS of each of the three (VoI: the lowest). Without `--sweep` the per-cut path above stays: `--min-region-size` needs the label maps.
+`--regions R[,R...] --sweep --reference-metrics`: the reference's other columns beside them - underseg, undersegNP, compactness,
+density and regions - of every listed R from the same tree and contour map (SPEC.md §17: `evaluate_gpu.under_sweep_resident`,
+`cut_shapes_device`, `sweep_reference_scores`); combines with `--agreement`.
 """
 import os
 import sys
@@ -178,19 +181,21 @@ def region_rows(n, lam, n_orient, cw, g, merge, regions):
             "%.4f" % float(np.mean([x[k] for x in rows[r]])) for k in keys), float(np.mean([x["regions"] for x in rows[r]]))))
 
 
-def sweep_rows(n, lam, n_orient, cw, g, regions, agreement=False):
+def sweep_rows(n, lam, n_orient, cw, g, regions, agreement=False, reference=False):
     import numpy as np
     import torch
     from gabor_color_image_segmentation_amd import Segmenter
     from gabor_color_image_segmentation_amd.evaluate import ods_ois
-    from gabor_color_image_segmentation_amd.evaluate_gpu import boundary_sweep_resident, region_sweep_resident, sweep_agreement, sweep_scores
+    from gabor_color_image_segmentation_amd.evaluate_gpu import (boundary_sweep_resident, cut_shapes_device, region_sweep_resident,
+                                                                  sweep_agreement, sweep_reference_scores, sweep_scores,
+                                                                  under_sweep_resident)
     from gabor_color_image_segmentation_amd.groundtruth import PackedTruth
     gold = os.path.join(ROOT, "tests", "golden")
     pack = np.load(os.path.join(gold, "bsd_val_images.npz"))
     truth = PackedTruth(os.path.join(gold, "bsd500_truth.npz"))
     ids = [str(i) for i in pack["ids"]]
     seg = Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, n_superpixels=n, spatial_weight=lam)
-    rows, agree = [], []
+    rows, agree, ref = [], [], []
     for shape in sorted({pack["img_" + i].shape[:2] for i in ids}):
         group = [i for i in ids if pack["img_" + i].shape[:2] == shape]
         labels, merges, _, alive = seg.region_tree_device(torch.from_numpy(np.stack([pack["img_" + i] for i in group])).cuda())
@@ -200,18 +205,24 @@ def sweep_rows(n, lam, n_orient, cw, g, regions, agreement=False):
                              regions)
         if agreement:                                    # the leaf tables once, every coarser table from the merge list (SPEC.md §16)
             agree += sweep_agreement(*region_sweep_resident(labels, merges, alive, dt, regions), dt.first, shape[0] * shape[1], regions)
-    keys = ("recall", "precision", "fmeasure") + (("PRI", "VoI", "covering") if agreement else ())
-    if agreement:
-        rows = [[dict(s, **a) for s, a in zip(row, arow)] for row, arow in zip(rows, agree)]
-    print("| n | lambda | n_orient | w | g | R | R | P | F |" + (" PRI | VoI | covering |" if agreement else ""))
-    print("|---|---|---|---|---|---|---|---|---|" + ("---|---|---|" if agreement else ""))
+        if reference:                                    # the undersegmentation sums and the shape counts of every cut (SPEC.md §17)
+            ref += sweep_reference_scores(under_sweep_resident(labels, merges, alive, dt, regions),
+                                          *cut_shapes_device(labels, contours, merges, alive, regions), alive.cpu().numpy(), dt.first,
+                                          shape[0], shape[1], regions)
+    keys = ("recall", "precision", "fmeasure") + (("PRI", "VoI", "covering") if agreement else ()) + \
+        (("underseg", "undersegNP", "compactness", "density", "regions") if reference else ())
+    for extra in ([agree] if agreement else []) + ([ref] if reference else []):
+        rows = [[dict(s, **a) for s, a in zip(row, arow)] for row, arow in zip(rows, extra)]
+    print("| n | lambda | n_orient | w | g | R | R | P | F |" + (" PRI | VoI | covering |" if agreement else "") +
+          (" underseg | undersegNP | compactness | density | regions |" if reference else ""))
+    print("|---|---|---|---|---|---|---|---|---|" + ("---|---|---|" if agreement else "") + ("---|---|---|---|---|" if reference else ""))
     for j, r in enumerate(regions):
         print("| %d | %d | %d | %g | %d | %d | %s |" % (n, lam, n_orient, cw, g, r, " | ".join(
             "%.4f" % float(np.mean([row[j][k] for row in rows])) for k in keys)))
     best = ods_ois([[s["fmeasure"] for s in row] for row in rows], regions)
     print("ODS %.4f at R = %d   OIS %.4f   (%d images, R in %s)" % (best["ODS"], best["ODS_regions"], best["OIS"], len(rows),
                                                                     ",".join(str(r) for r in regions)))
-    for key in keys[3:]:                                 # VoI: lower is better
+    for key in keys[3:6] if agreement else ():           # VoI: lower is better
         best = ods_ois([[s[key] for s in row] for row in rows], regions, best="min" if key == "VoI" else "max")
         print("%-8s ODS %.4f at R = %d   OIS %.4f" % (key, best["ODS"], best["ODS_regions"], best["OIS"]))
 
@@ -223,7 +234,8 @@ if __name__ == '__main__':
         if "--regions" in sys.argv and "--sweep" in sys.argv:
             sweep_rows(one("--superpixels", int, 300), one("--spatial-weight", int, 576), one("--n-orient", int, 6),
                        one("--color-weight", float, 0.0), one("--chroma-gain", int, 0),
-                       [int(v) for v in one("--regions", str, "8").split(",")], agreement="--agreement" in sys.argv)
+                       [int(v) for v in one("--regions", str, "8").split(",")], agreement="--agreement" in sys.argv,
+                       reference="--reference-metrics" in sys.argv)
             sys.exit(0)
         if "--regions" in sys.argv:
             region_rows(one("--superpixels", int, 300), one("--spatial-weight", int, 576), one("--n-orient", int, 6),

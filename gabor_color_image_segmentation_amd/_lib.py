@@ -81,6 +81,10 @@ SIGNATURES = {
     "gcs_boundary_sweep_resident": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "gcs_region_sweep_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "gcs_region_sweep": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "gcs_region_sweep_under_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "gcs_region_sweep_under": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gcs_cut_shapes_workspace_bytes": (_sz, [_i, _i, _i]),
+    "gcs_cut_shapes": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -1,10 +1,12 @@
 // scoring.hip — evaluation-side kernels of libgcs.so (gfx950): boundary recall / precision counts
 // (/root/reference/BSD_metrics/metrics.py:58-96), region tables (metrics.py:102-201), region agreement (SPEC.md §8) and the two
-// sweeps over a region tree's cuts (SPEC.md §15, §16). Connected regions and the small-region merge: regions.hip.
+// sweeps over a region tree's cuts (SPEC.md §15, §16) with the undersegmentation sums of every cut (SPEC.md §17; the shape counts
+// of §17: cut_shapes.hip). Connected regions and the small-region merge: regions.hip.
 // Nothing here allocates, frees or synchronises; every entry point enqueues on the caller's stream.
 #include <limits.h>
 
 #include "common.h"
+#include "tree_cuts.h"
 
 // ======================================================================= boundary scoring (§8f-1)
 // Integer restatement of /root/reference/BSD_metrics/metrics.py:25-51,58-96 for ONE image:
@@ -364,8 +366,7 @@ extern "C" int gcs_boundary_counts_resident(const int32_t *labels, const void *t
 // The annotators of image b are the run of t with img_of[t] = b (img_of is non-decreasing: PackedTruth.stack's order). The
 // (1 + 2 A_b)(K + 1) counters of the image sit in LDS when they fit the launch's SW_LDS_COUNTERS and leave with one vector atomic
 // per non-zero counter; otherwise every count is a global atomic (slow, exact). Integer counts: any order, the same bits.
-constexpr int SW_TH = 16, SW_TW = 64, SW_HALO = 2;
-constexpr int SW_LDS_COUNTERS = 8192;
+constexpr int SW_TH = 16, SW_TW = 64, SW_HALO = 2;             // (SW_LDS_COUNTERS: tree_cuts.h)
 __global__ __launch_bounds__(256) void boundary_sweep_kernel(const int32_t *__restrict__ contours,
                                                              const unsigned long long *__restrict__ tru,
                                                              const int32_t *__restrict__ img_of, int B, int T, int H, int W, int K,
@@ -683,7 +684,7 @@ extern "C" int gcs_score_batch_resident(const int32_t *labels, const void *truth
 // Every float sum runs in an order fixed by the row / column INDEX alone (row mod 16 and its step, column mod 64 or mod 1024,
 // chunk), then a fixed shuffle tree and the waves in order: empty rows and columns (a table allocated at a capacity) add
 // nothing, so tables of the same maps at different shapes give the same bits. No float atomics.
-constexpr int AG_WAVES = 16, AG_THREADS = 64 * AG_WAVES, AG_CHUNK = 1024, AG_ROWS = 8;
+constexpr int AG_CHUNK = 1024, AG_ROWS = 8;                    // (AG_WAVES = 16, AG_THREADS = 1024: tree_cuts.h)
 
 template <typename V>
 __device__ __forceinline__ V ag_wave_sum(V v) {
@@ -892,27 +893,114 @@ extern "C" int gcs_region_agreement(const uint32_t *hist, const int32_t *img_of,
 // tables (gcs_region_counts_batch[_u8] with n_segments = K) are made once from the pixels and every coarser table follows from the
 // merge list by adding rows. ONE workgroup per annotator map t of image b = img_of[t], the requested cuts in their (decreasing) order
 // of R, so the table only ever gets coarser and is coarsened IN PLACE:
-//   1. death[q] = the row that absorbs label q, with its absorber (one LDS word, (row << 12) | absorber). A row counts when it has
-//      0 <= a < b < K and both are reps at that step; which rows count depends on the rows before them only, so the rule is iterated
-//      from "every well-formed row counts" until nothing changes (a list gcs_region_tree wrote: the first check already agrees; any
-//      list: at most K - 1 rounds, row t is settled after round t + 1). No serial walk over the rows.
-//   2. per cut, tau = max(0, alive - R): parent[q] = death[q] < tau ? absorber : q, pointer jumping (ceil(log2 K) rounds) gives every
-//      label's group rep; the rows absorbed since the previous cut (tau_prev <= death < tau) are added into their rep's row, element
-//      by element with integer atomics (exact in any order; a rep is never absorbed in the same cut, so no row is read and written),
-//      and emptied.
-//   3. the table is reduced by ag_table_reduce, the function gcs_region_agreement runs: every float sum in an order fixed by the
-//      table indices alone, no running float sums carried from cut to cut.
-constexpr int RS_K_MAX = 4096, RS_CUTS_MAX = 64, RS_PER = RS_K_MAX / AG_THREADS, RS_UNROLL = 4;
-constexpr unsigned RS_NONE = 0xffffffffu;                      // never absorbed: its row field is above every row index
+//   1. death[q] = the row that absorbs label q, with its absorber (rs_absorbers, tree_cuts.h).
+//   2. per cut, tau = max(0, alive - R): pointer jumping (rs_group_reps, tree_cuts.h) gives every label's group rep; the rows absorbed
+//      since the previous cut (tau_prev <= death < tau) are added into their rep's row, element by element with integer atomics
+//      (exact in any order; a rep is never absorbed in the same cut, so no row is read and written), and emptied.
+//   3. the table is reduced: by rs_under_reduce to { N, under, under_np } of SPEC.md §17 (UNDER: gcs_region_sweep_under), by
+//      ag_table_reduce, the function gcs_region_agreement runs (AGREE: gcs_region_sweep, and gcs_region_sweep_under when asked):
+//      every float sum in an order fixed by the table indices alone, no running float sums carried from cut to cut. The
+//      instantiation without AGREE does not carry ag_table_reduce's 132 KiB of LDS.
+constexpr int RS_UNROLL = 4;
+constexpr int RU_ROWS = 4, RU_COLS = 4;                        // rs_under_reduce: rows of a wave in flight, registers per lane and row
 
+// The three integer sums SPEC.md §17 takes from ONE table h [K][stride], by the whole workgroup: out = { N = sum_i a_i,
+// sum_i (a_i - max_j n_ij), sum_ij min(n_ij, a_i - n_ij) }, a_i the row sums of the table itself (metrics.py:129-131, :137-140).
+// A wave per row, lanes across the columns, maximum and row sum by cross-lane shuffles as in region_reduce_kernel; RU_ROWS rows of
+// a wave with their loads in flight together, and a row of at most 64 * RU_COLS columns (uint8 annotator maps) is read once and
+// kept in registers. Rows absorbed below tau are empty and are not read. Integers: exact in any order. s_p: [AG_WAVES][3] of LDS;
+// a caller that calls it again puts a __syncthreads() in between.
+__device__ __forceinline__ void rs_under_reduce(const unsigned *h, int K, int stride, const unsigned *s_dk, int tau,
+                                                unsigned long long (*s_p)[3], unsigned long long *out) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned long long n = 0, u = 0, np = 0;                   // (every lane of a wave carries the wave's share)
+    for (int q0 = wave; q0 < K; q0 += AG_WAVES * RU_ROWS) {
+        bool live[RU_ROWS];
+#pragma unroll
+        for (int r = 0; r < RU_ROWS; ++r) {
+            const int q = q0 + r * AG_WAVES;
+            live[r] = q < K && (s_dk[q] >> 12) >= (unsigned)tau;          // (uniform over the wave)
+        }
+        if (stride <= 64 * RU_COLS) {
+            unsigned v[RU_ROWS][RU_COLS];
+#pragma unroll
+            for (int r = 0; r < RU_ROWS; ++r)
+#pragma unroll
+                for (int j = 0; j < RU_COLS; ++j) {
+                    const int c = lane + 64 * j;
+                    v[r][j] = live[r] && c < stride ? h[(size_t)(q0 + r * AG_WAVES) * stride + c] : 0u;
+                }
+#pragma unroll
+            for (int r = 0; r < RU_ROWS; ++r) {
+                if (!live[r]) continue;
+                unsigned mx = 0, sum = 0;                      // a row sum is at most H * W < 2^31
+#pragma unroll
+                for (int j = 0; j < RU_COLS; ++j) {
+                    mx = max(mx, v[r][j]);
+                    sum += v[r][j];
+                }
+                for (int s = 32; s >= 1; s >>= 1) {
+                    mx = max(mx, (unsigned)__shfl_xor((int)mx, s));
+                    sum += (unsigned)__shfl_xor((int)sum, s);
+                }
+                unsigned mn = 0;                               // at most the row sum
+#pragma unroll
+                for (int j = 0; j < RU_COLS; ++j) mn += min(v[r][j], sum - v[r][j]);
+                for (int s = 32; s >= 1; s >>= 1) mn += (unsigned)__shfl_xor((int)mn, s);
+                n += sum;
+                u += sum - mx;
+                np += mn;
+            }
+        } else {
+#pragma unroll 1
+            for (int r = 0; r < RU_ROWS; ++r) {
+                if (!live[r]) continue;
+                const unsigned *row = h + (size_t)(q0 + r * AG_WAVES) * stride;
+                unsigned mx = 0, sum = 0;
+                for (int c = lane; c < stride; c += 64) {
+                    const unsigned x = row[c];
+                    mx = max(mx, x);
+                    sum += x;
+                }
+                for (int s = 32; s >= 1; s >>= 1) {
+                    mx = max(mx, (unsigned)__shfl_xor((int)mx, s));
+                    sum += (unsigned)__shfl_xor((int)sum, s);
+                }
+                unsigned mn = 0;
+                for (int c = lane; c < stride; c += 64) {
+                    const unsigned x = row[c];
+                    mn += min(x, sum - x);
+                }
+                for (int s = 32; s >= 1; s >>= 1) mn += (unsigned)__shfl_xor((int)mn, s);
+                n += sum;
+                u += sum - mx;
+                np += mn;
+            }
+        }
+    }
+    if (lane == 0) {
+        s_p[wave][0] = n;
+        s_p[wave][1] = u;
+        s_p[wave][2] = np;
+    }
+    __syncthreads();
+    if (tid < 3) {
+        unsigned long long v = 0;
+        for (int w = 0; w < AG_WAVES; ++w) v += s_p[w][tid];
+        out[tid] = v;
+    }
+}
+
+template <bool UNDER, bool AGREE>
 __global__ __launch_bounds__(AG_THREADS) void region_sweep_kernel(unsigned *hist, const int32_t *__restrict__ merges,
                                                                   const int32_t *__restrict__ alive_p,
                                                                   const int32_t *__restrict__ img_of,
                                                                   const int32_t *__restrict__ regions, int B, int T, int K, int stride,
-                                                                  int n_cuts, unsigned *scratch, unsigned long long *sums,
-                                                                  double *terms) {
+                                                                  int n_cuts, unsigned *scratch, unsigned long long *under,
+                                                                  unsigned long long *sums, double *terms) {
     __shared__ unsigned s_dk[RS_K_MAX];
     __shared__ unsigned short s_root[RS_K_MAX];
+    __shared__ unsigned long long s_p[UNDER ? AG_WAVES : 1][3];
     __shared__ int s_changed;
     const int t = blockIdx.x, tid = threadIdx.x;
     const int b = img_of[t];
@@ -924,69 +1012,15 @@ __global__ __launch_bounds__(AG_THREADS) void region_sweep_kernel(unsigned *hist
     const int32_t *rows = merges + (img_ok ? (size_t)b * (K - 1) * 2 : 0);   // (not read with n_rows = 0: NULL with K = 1)
 
     // ---- 1. which rows count, and what absorbs every label
-    int ra[RS_PER], rc[RS_PER];
-    unsigned formed = 0;
-#pragma unroll
-    for (int j = 0; j < RS_PER; ++j) {
-        const int r = tid + j * AG_THREADS;
-        ra[j] = rc[j] = 0;
-        if (r < n_rows) {
-            ra[j] = rows[2 * r];
-            rc[j] = rows[2 * r + 1];
-            if (ra[j] >= 0 && ra[j] < rc[j] && rc[j] < K) formed |= 1u << j;
-        }
-    }
-    unsigned counted = formed;
-    for (;;) {
-        for (int q = tid; q < K; q += AG_THREADS) s_dk[q] = RS_NONE;
-        if (tid == 0) s_changed = 0;
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < RS_PER; ++j)
-            if ((counted >> j) & 1u) atomicMin(&s_dk[rc[j]], ((unsigned)(tid + j * AG_THREADS) << 12) | (unsigned)ra[j]);
-        __syncthreads();
-        unsigned now = 0;
-#pragma unroll
-        for (int j = 0; j < RS_PER; ++j) {
-            const unsigned r = (unsigned)(tid + j * AG_THREADS);
-            if (((formed >> j) & 1u) && (s_dk[ra[j]] >> 12) >= r && (s_dk[rc[j]] >> 12) >= r) now |= 1u << j;
-        }
-        if (now != counted) s_changed = 1;                     // (every writer stores the same value)
-        counted = now;
-        __syncthreads();
-        const int changed = s_changed;
-        __syncthreads();                                       // everyone has read the flag before the next round clears it
-        if (!changed) break;
-    }
+    rs_absorbers(rows, n_rows, K, s_dk, &s_changed);
 
     // ---- 2. and 3. per cut: coarsen the table in place, reduce it
-    const int LV = K > 1 ? 32 - __builtin_clz((unsigned)(K - 1)) : 0;       // ceil(log2 K): a chain has at most K - 1 links
     const long long cells = (long long)K * stride;
     int tau_prev = 0;
     for (int ci = 0; ci < n_cuts; ++ci) {
-        const long long want = (long long)alive - (long long)regions[ci];
-        const int tau = (int)(want < 0 ? 0 : want > n_rows ? n_rows : want);
+        const int tau = rs_tau(alive, regions[ci], n_rows);
         if (tau > tau_prev) {                                  // (a list that is not decreasing never un-merges: no launch can check it)
-            for (int q = tid; q < K; q += AG_THREADS) {
-                const unsigned d = s_dk[q];
-                s_root[q] = (d >> 12) < (unsigned)tau ? (unsigned short)(d & 0xfffu) : (unsigned short)q;
-            }
-            __syncthreads();
-            for (int it = 0; it < LV; ++it) {
-                unsigned short pp[RS_PER];
-#pragma unroll
-                for (int j = 0; j < RS_PER; ++j) {
-                    const int q = tid + j * AG_THREADS;
-                    pp[j] = q < K ? s_root[s_root[q]] : (unsigned short)0;
-                }
-                __syncthreads();
-#pragma unroll
-                for (int j = 0; j < RS_PER; ++j) {
-                    const int q = tid + j * AG_THREADS;
-                    if (q < K) s_root[q] = pp[j];
-                }
-                __syncthreads();
-            }
+            rs_group_reps(s_dk, s_root, K, tau);
             // the cells of the rows absorbed in this cut, RS_UNROLL of them per thread with their loads in flight together
             for (long long i0 = tid; i0 < cells; i0 += (long long)AG_THREADS * RS_UNROLL) {
                 unsigned v[RS_UNROLL];
@@ -1016,8 +1050,14 @@ __global__ __launch_bounds__(AG_THREADS) void region_sweep_kernel(unsigned *hist
         }
         __syncthreads();                                       // (with its workgroup-scope fences: this workgroup's atomics and stores
                                                                // are visible to its own loads below; nobody else reads the table)
-        ag_table_reduce(h, K, stride, a_s, b_s, sums + ((size_t)ci * T + t) * 4, terms + ((size_t)ci * T + t) * 4);
-        __syncthreads();
+        if constexpr (UNDER) {
+            rs_under_reduce(h, K, stride, s_dk, tau_prev, s_p, under + ((size_t)ci * T + t) * 3);
+            __syncthreads();
+        }
+        if constexpr (AGREE) {
+            ag_table_reduce(h, K, stride, a_s, b_s, sums + ((size_t)ci * T + t) * 4, terms + ((size_t)ci * T + t) * 4);
+            __syncthreads();
+        }
     }
 }
 
@@ -1040,9 +1080,38 @@ extern "C" int gcs_region_sweep(uint32_t *leaf_hist, const int32_t *merges, cons
         return gcs_fail(GCS_EINVAL, "gcs_region_sweep: bad shape (1 <= B <= 65535, 1 <= T <= 1000000, 1 <= K <= 4096, 1 <= n_cuts <= 64)");
     if (!region_sweep_shape_ok(T, K, n_truth_labels, n_cuts))
         return gcs_fail(GCS_EINVAL, "gcs_region_sweep: T * K * n_truth_labels must be below 2^31");
-    hipLaunchKernelGGL(region_sweep_kernel, dim3(T), dim3(AG_THREADS), 0, stream, leaf_hist, merges, alive, img_of, regions, B, T, K,
-                       n_truth_labels, n_cuts, static_cast<unsigned *>(workspace), reinterpret_cast<unsigned long long *>(sums_out),
-                       terms_out);
+    hipLaunchKernelGGL((region_sweep_kernel<false, true>), dim3(T), dim3(AG_THREADS), 0, stream, leaf_hist, merges, alive, img_of,
+                       regions, B, T, K, n_truth_labels, n_cuts, static_cast<unsigned *>(workspace), nullptr,
+                       reinterpret_cast<unsigned long long *>(sums_out), terms_out);
     GCS_CHECK_LAUNCH("gcs_region_sweep");
+    return GCS_OK;
+}
+
+// ---- the same walk with the undersegmentation sums of every cut (SPEC.md §17), and the agreement outputs too when asked
+extern "C" size_t gcs_region_sweep_under_workspace_bytes(int T, int K, int n_truth_labels, int n_cuts) {
+    return gcs_region_sweep_workspace_bytes(T, K, n_truth_labels, n_cuts);
+}
+
+extern "C" int gcs_region_sweep_under(uint32_t *leaf_hist, const int32_t *merges, const int32_t *alive, const int32_t *img_of,
+                                      const int32_t *regions, int B, int T, int K, int n_truth_labels, int n_cuts, void *workspace,
+                                      uint64_t *under_out, uint64_t *sums_out, double *terms_out, gcs_stream_t stream) {
+    if (!leaf_hist || !alive || !img_of || !regions || !workspace || !under_out || (K > 1 && !merges))
+        return gcs_fail(GCS_EINVAL, "gcs_region_sweep_under: NULL pointer");
+    if (!sums_out != !terms_out)
+        return gcs_fail(GCS_EINVAL, "gcs_region_sweep_under: sums_out_dev and terms_out_dev are given together or both NULL");
+    if (B < 1 || B > 65535 || T < 1 || T > 1000000 || K < 1 || K > RS_K_MAX || n_truth_labels < 1 || n_cuts < 1 || n_cuts > RS_CUTS_MAX)
+        return gcs_fail(GCS_EINVAL, "gcs_region_sweep_under: bad shape (1 <= B <= 65535, 1 <= T <= 1000000, 1 <= K <= 4096, 1 <= n_cuts <= 64)");
+    if (!region_sweep_shape_ok(T, K, n_truth_labels, n_cuts))    // (the outputs: n_cuts * T * 4 <= 2.56e8 elements)
+        return gcs_fail(GCS_EINVAL, "gcs_region_sweep_under: T * K * n_truth_labels must be below 2^31");
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(T), dim3(AG_THREADS), 0, stream, leaf_hist, merges, alive, img_of, regions, B, T, K,
+                           n_truth_labels, n_cuts, static_cast<unsigned *>(workspace), reinterpret_cast<unsigned long long *>(under_out),
+                           reinterpret_cast<unsigned long long *>(sums_out), terms_out);
+    };
+    if (sums_out)
+        launch(region_sweep_kernel<true, true>);
+    else
+        launch(region_sweep_kernel<true, false>);
+    GCS_CHECK_LAUNCH("gcs_region_sweep_under");
     return GCS_OK;
 }

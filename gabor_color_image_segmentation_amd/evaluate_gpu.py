@@ -11,7 +11,8 @@ Four layers, each with the C entry points it calls:
    ``all_scores_batch_resident`` (gcs_score_batch_resident, gcs_region_agreement with agreement=True).
 4. Every cut of a region tree on resident truth: ``boundary_sweep_resident`` (gcs_boundary_sweep_resident) with
    ``sweep_counts`` / ``sweep_scores``; ``region_sweep_resident`` (gcs_region_counts_batch[_u8], gcs_region_sweep) with
-   ``sweep_agreement``.
+   ``sweep_agreement``; ``under_sweep_resident`` (gcs_region_counts_batch[_u8], gcs_region_sweep_under) and ``cut_shapes_device``
+   (gcs_cut_shapes) with ``sweep_reference_scores``; ``metrics_sweep_resident`` chains them all (SPEC.md §15 - §17).
 
 The host arithmetic exists once: ``_boundary_scores``, ``_region_scores_batch`` and ``evaluate.agreement_from_sums``.
 """
@@ -52,6 +53,53 @@ def _need_match(shape, device, truth, what):
 def _need_two_pixels(h, w):
     if h * w < 2:
         raise ValueError(f"region agreement needs at least 2 pixels, got {h * w}")
+
+
+def _need_cuts(regions):
+    """The checked list of R and the positions that put it into strictly decreasing order (what the sweep calls want)."""
+    try:
+        regs = [int(r) for r in regions]
+        same = all(r == q for r, q in zip(regs, regions))
+    except (TypeError, ValueError):
+        raise ValueError("regions must be a list of integers") from None
+    if not same or not 1 <= len(regs) <= SWEEP_CUTS or len(set(regs)) != len(regs) or min(regs) < 1 or max(regs) > SWEEP_LEVELS:
+        raise ValueError(f"regions must be 1..{SWEEP_CUTS} distinct integers in 1..{SWEEP_LEVELS}")
+    return regs, sorted(range(len(regs)), key=lambda j: -regs[j])
+
+
+def _need_tree(labels, merges, alive, device, whose, truth=None):
+    """The checks of a region tree's three tensors (``Segmenter.region_tree_device``), the labels against ``truth`` when given;
+    -> them, contiguous."""
+    import torch
+    _need_labels(labels, 3)
+    if truth is not None:
+        _need_match(labels.shape, labels.device, truth, "label")
+    b = labels.shape[0]
+    if merges.dtype != torch.int32 or merges.dim() != 3 or merges.shape[0] != b or merges.shape[2] != 2 or \
+            not 1 <= merges.shape[1] + 1 <= SWEEP_LEVELS:
+        raise ValueError(f"merges must be a (B, K - 1, 2) int32 tensor with K in 1..{SWEEP_LEVELS}")
+    if alive.dtype != torch.int32 or tuple(alive.shape) != (b,):
+        raise ValueError("alive must be a (B,) int32 tensor")
+    if merges.device != device or alive.device != device:
+        raise ValueError(f"merges / alive are not on the device of {whose}")
+    return labels.contiguous(), merges.contiguous(), alive.contiguous()
+
+
+def _need_contours(contours, labels):
+    _need_labels(contours, 3, "contours")
+    if contours.shape != labels.shape or contours.device != labels.device:
+        raise ValueError("contours must match labels (shape and device)")
+
+
+def _need_tree_and_cuts(labels, merges, alive, regions, truth):
+    """Every check of a sweep over a tree's contingency tables, before anything runs -> (labels, merges, alive, regs, order)."""
+    labels, merges, alive = _need_tree(labels, merges, alive, truth.device, "the resident truth", truth)
+    regs, order = _need_cuts(regions)
+    _need_two_pixels(*labels.shape[1:])
+    k = merges.shape[1] + 1
+    if truth.t * k * truth.stride > 0x3fffffff:
+        raise ValueError(f"the leaf tables [{truth.t}][{k}][{truth.stride}] exceed 2^30 counters")
+    return labels, merges, alive, regs, order
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -579,6 +627,29 @@ def sweep_scores(hists, alive, bd_counts, first, regions) -> list:
 # 4b. The region metrics of every cut of a region tree at once (SPEC.md §16): the leaf tables from one pass over the pixels,
 # every coarser table from the merge list by adding rows.
 
+def _leaf_tables(labels, merges, truth, stream):
+    """The contingency tables of the superpixels, uint32 [T][K][stride] on the device (one launch on ``stream``)."""
+    import torch
+    lib = _lib.load()
+    (b, h, w), k = labels.shape, merges.shape[1] + 1
+    hist = torch.empty(truth.t * k * truth.stride, dtype=torch.int32, device=truth.device)
+    side = torch.empty(2 * b * k, dtype=torch.int32, device=truth.device)        # area | perimeter of the leaves: not used
+    counts = lib.gcs_region_counts_batch_u8 if truth.u8 else lib.gcs_region_counts_batch
+    _lib.check(counts(labels.data_ptr(), truth.maps.data_ptr(), truth.first_d.data_ptr(), b, truth.t, truth.a_max, h, w, k,
+                      truth.stride, hist.data_ptr(), side.data_ptr(), side.data_ptr() + 4 * b * k, stream), "gcs_region_counts_batch")
+    return hist
+
+
+def _cuts_in_callers_order(arrays, n, t, order):
+    """Arrays [n * t][m] as a sweep wrote them (cut-major, R decreasing) -> new arrays [n][t][m] in the caller's order of R."""
+    out = []
+    for src in arrays:
+        dst = np.empty((n, t, src.shape[-1]), src.dtype)
+        dst[order] = src.reshape(n, t, -1)
+        out.append(dst)
+    return tuple(out)
+
+
 def region_sweep_resident(labels, merges, alive, truth: DeviceTruth, regions):
     """labels (B,H,W) int32, merges (B, K-1, 2) int32, alive (B,) int32: the device tensors ``Segmenter.region_tree_device`` returned;
     truth: the resident ground truth of the same images; regions: 1 .. 64 distinct integers in 1 .. 4096, in any order. Returns host
@@ -587,38 +658,14 @@ def region_sweep_resident(labels, merges, alive, truth: DeviceTruth, regions):
     (the raw cuts: ``connectivity`` and ``min_region_size`` are not reflected). Two launches (the leaf tables with K rows; the
     sweep) and one download. Buffers of its own: ``truth``'s result block and its one-submission rule are not touched."""
     import torch
-    _need_labels(labels, 3)
+    labels, merges, alive, regs, order = _need_tree_and_cuts(labels, merges, alive, regions, truth)
     b, h, w = labels.shape
-    _need_match((b, h, w), labels.device, truth, "label")
-    if merges.dtype != torch.int32 or merges.dim() != 3 or merges.shape[0] != b or merges.shape[2] != 2 or \
-            not 1 <= merges.shape[1] + 1 <= SWEEP_LEVELS:
-        raise ValueError(f"merges must be a (B, K - 1, 2) int32 tensor with K in 1..{SWEEP_LEVELS}")
-    if alive.dtype != torch.int32 or tuple(alive.shape) != (b,):
-        raise ValueError("alive must be a (B,) int32 tensor")
-    if merges.device != truth.device or alive.device != truth.device:
-        raise ValueError("merges / alive are not on the device of the resident truth")
-    try:
-        regs = [int(r) for r in regions]
-        same = all(r == q for r, q in zip(regs, regions))
-    except (TypeError, ValueError):
-        raise ValueError("regions must be a list of integers") from None
-    if not same or not 1 <= len(regs) <= SWEEP_CUTS or len(set(regs)) != len(regs) or min(regs) < 1 or max(regs) > SWEEP_LEVELS:
-        raise ValueError(f"regions must be 1..{SWEEP_CUTS} distinct integers in 1..{SWEEP_LEVELS}")
-    _need_two_pixels(h, w)
     k, t, stride, n = merges.shape[1] + 1, truth.t, truth.stride, len(regs)
-    if t * k * stride > 0x3fffffff:
-        raise ValueError(f"the leaf tables [{t}][{k}][{stride}] exceed 2^30 counters")
-    order = sorted(range(n), key=lambda j: -regs[j])             # the call wants R strictly decreasing
-    labels, merges, alive = labels.contiguous(), merges.contiguous(), alive.contiguous()
     lib = _lib.load()
     with torch.cuda.device(truth.device):
         dev = truth.device
         stream = torch.cuda.current_stream(dev).cuda_stream
-        hist = torch.empty(t * k * stride, dtype=torch.int32, device=dev)
-        side = torch.empty(2 * b * k, dtype=torch.int32, device=dev)             # area | perimeter of the leaves: not used here
-        counts = lib.gcs_region_counts_batch_u8 if truth.u8 else lib.gcs_region_counts_batch
-        _lib.check(counts(labels.data_ptr(), truth.maps.data_ptr(), truth.first_d.data_ptr(), b, t, truth.a_max, h, w, k, stride,
-                          hist.data_ptr(), side.data_ptr(), side.data_ptr() + 4 * b * k, stream), "gcs_region_counts_batch")
+        hist = _leaf_tables(labels, merges, truth, stream)
         regs_d = torch.tensor([regs[j] for j in order], dtype=torch.int32).to(dev)
         ws = torch.empty(lib.gcs_region_sweep_workspace_bytes(t, k, stride, n), dtype=torch.uint8, device=dev)
         out = torch.empty(2 * n * t * 4, dtype=torch.int64, device=dev)          # an agreement block of n t maps, cut-major
@@ -626,11 +673,7 @@ def region_sweep_resident(labels, merges, alive, truth: DeviceTruth, regions):
                                         truth.img_of_d.data_ptr(), regs_d.data_ptr(), b, t, k, stride, n, ws.data_ptr(),
                                         out.data_ptr(), out.data_ptr() + n * t * 32, stream), "gcs_region_sweep")
         raw = out.cpu().numpy()
-    sums = np.empty((n, t, 4), np.uint64)
-    terms = np.empty((n, t, 4), np.float64)
-    for dst, src in zip((sums, terms), _agreement_arrays(raw, n * t)):
-        dst[order] = src.reshape(n, t, 4)
-    return sums, terms
+    return _cuts_in_callers_order(_agreement_arrays(raw, n * t), n, t, order)
 
 
 def sweep_agreement(sums, terms, first, n_pixels, regions) -> list:
@@ -645,3 +688,121 @@ def sweep_agreement(sums, terms, first, n_pixels, regions) -> list:
         raise ValueError("first does not describe the annotator maps of sums / terms")
     per_cut = [agreement_from_sums(sums[j], terms[j], first, n_pixels) for j in range(n)]
     return [[per_cut[j][i] for j in range(n)] for i in range(len(first) - 1)]
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# 4c. The reference's region and shape metrics of every cut of a region tree at once (SPEC.md §17): the undersegmentation sums from
+# the walk of 4b, area / perimeter / boundary count from one pass over (labels, contour map).
+
+def under_sweep_resident(labels, merges, alive, truth: DeviceTruth, regions, agreement=False):
+    """The arguments of ``region_sweep_resident``, checked, ordered and buffered in the same way. Returns the host array ``counts uint64
+    [len(regions)][T][3] = {N_t, under, under_np}`` in the caller's order of ``regions``: per cut and annotator map the pixels its
+    contingency table counts and the two integer sums of metrics.py:129-131 and :137-140 for ``cut_regions_device(labels, merges,
+    alive, R)`` (the raw cuts). agreement=True: ``(counts, sums, terms)``, the last two what ``region_sweep_resident`` returns, bit
+    for bit, from the same walk. Two launches (the leaf tables; gcs_region_sweep_under) and one download."""
+    import torch
+    labels, merges, alive, regs, order = _need_tree_and_cuts(labels, merges, alive, regions, truth)
+    b, k, t, stride, n = labels.shape[0], merges.shape[1] + 1, truth.t, truth.stride, len(regs)
+    lib = _lib.load()
+    with torch.cuda.device(truth.device):
+        dev = truth.device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        hist = _leaf_tables(labels, merges, truth, stream)
+        regs_d = torch.tensor([regs[j] for j in order], dtype=torch.int32).to(dev)
+        ws = torch.empty(lib.gcs_region_sweep_under_workspace_bytes(t, k, stride, n), dtype=torch.uint8, device=dev)
+        out = torch.empty(n * t * (11 if agreement else 3), dtype=torch.int64, device=dev)   # under [n t][3] | sums | terms [n t][4]
+        agr = out.data_ptr() + n * t * 24
+        _lib.check(lib.gcs_region_sweep_under(hist.data_ptr(), merges.data_ptr() if k > 1 else None, alive.data_ptr(),
+                                              truth.img_of_d.data_ptr(), regs_d.data_ptr(), b, t, k, stride, n, ws.data_ptr(),
+                                              out.data_ptr(), agr if agreement else None, agr + n * t * 32 if agreement else None,
+                                              stream), "gcs_region_sweep_under")
+        raw = out.cpu().numpy()
+    arrays = [raw[:n * t * 3].view(np.uint64).reshape(n * t, 3)]
+    if agreement:
+        arrays += _agreement_arrays(raw[n * t * 3:], n * t)
+    got = _cuts_in_callers_order(arrays, n, t, order)
+    return got if agreement else got[0]
+
+
+def cut_shapes_device(labels, contours, merges, alive, regions):
+    """labels, merges, alive: the device tensors of ``Segmenter.region_tree_device``; contours: the (B,H,W) int32 tensor
+    ``Segmenter.contour_map_device`` made of them; regions: as in ``region_sweep_resident``. Returns host arrays ``(area uint32
+    [len(regions)][B][K], perim uint32 [len(regions)][B][K], boundary uint32 [len(regions)][B])`` in the caller's order of ``regions``:
+    per cut the pixel count and the perimeter (metrics.py:160-180) of every group, held at the group's smallest label (0 for every
+    other label), and the number of thick-boundary pixels (metrics.py:157), for the raw cuts. Three launches, one download."""
+    import torch
+    labels, merges, alive = _need_tree(labels, merges, alive, labels.device, "the labels")
+    _need_contours(contours, labels)
+    regs, order = _need_cuts(regions)
+    (b, h, w), k, n = labels.shape, merges.shape[1] + 1, len(regs)
+    if h > 4096 or w > 4096:
+        raise ValueError("the sweep takes images of at most 4096 x 4096 pixels")
+    contours = contours.contiguous()
+    lib = _lib.load()
+    with torch.cuda.device(labels.device):
+        dev = labels.device
+        regs_d = torch.tensor([regs[j] for j in order], dtype=torch.int32).to(dev)
+        ws = torch.empty(lib.gcs_cut_shapes_workspace_bytes(b, k, n), dtype=torch.uint8, device=dev)
+        out = torch.empty(n * b * (2 * k + 1), dtype=torch.int32, device=dev)    # area [n][b][k] | perim [n][b][k] | boundary [n][b]
+        _lib.check(lib.gcs_cut_shapes(labels.data_ptr(), contours.data_ptr(), merges.data_ptr() if k > 1 else None, alive.data_ptr(),
+                                      regs_d.data_ptr(), b, h, w, k, n, ws.data_ptr(), out.data_ptr(), out.data_ptr() + 4 * n * b * k,
+                                      out.data_ptr() + 8 * n * b * k, torch.cuda.current_stream(dev).cuda_stream), "gcs_cut_shapes")
+        raw = out.cpu().numpy().view(np.uint32)
+    area, perim = _cuts_in_callers_order((raw[:n * b * k].reshape(n * b, k), raw[n * b * k:2 * n * b * k].reshape(n * b, k)), n, b, order)
+    boundary = np.empty((n, b), np.uint32)
+    boundary[order] = raw[2 * n * b * k:].reshape(n, b)
+    return area, perim, boundary
+
+
+def sweep_reference_scores(counts, area, perim, boundary, alive, first, nx, ny, regions) -> list:
+    """Per image a list with one ``{"regions", "underseg", "undersegNP", "compactness", "density"}`` per R of ``regions``, from the
+    arrays of ``under_sweep_resident`` and ``cut_shapes_device``: the floats ``all_scores_batch_resident`` gives for
+    ``cut_regions_device(..., R)`` (the same integers through ``_region_scores_batch``, whose sums run in the reference's order: a cut
+    numbers its groups by increasing smallest label, the order of the rows here). ``regions`` = min(alive, R). Raises ValueError if a
+    table did not count every pixel (N_t != nx * ny: a label outside 0 .. K-1), as the scorer does for such a map."""
+    counts, area, perim, boundary = (np.asarray(x) for x in (counts, area, perim, boundary))
+    alive = np.asarray(alive).astype(np.int64).ravel().tolist()
+    first = np.asarray(first).astype(np.int64)
+    n, b = len(regions), len(first) - 1
+    if counts.ndim != 3 or counts.shape[0] != n or counts.shape[1] != int(first[-1]) or counts.shape[2] != 3:
+        raise ValueError("counts must be a [len(regions)][T][3] array with T = first[-1]")
+    if area.ndim != 3 or area.shape[:2] != (n, b) or perim.shape != area.shape or boundary.shape != (n, b) or len(alive) != b:
+        raise ValueError("area / perim [len(regions)][B][K], boundary [len(regions)][B] and alive [B] do not describe the same cuts")
+    if (counts[:, :, 0] != nx * ny).any():
+        j, t = (int(v[0]) for v in np.nonzero(counts[:, :, 0] != nx * ny))
+        raise ValueError(f"the table of annotator map {t} at R = {regions[j]} counts {int(counts[j, t, 0])} of {nx * ny} pixels: "
+                         "a label outside 0 .. K-1")
+    out = [[] for _ in range(b)]
+    for j, r in enumerate(regions):
+        reg = _region_scores_batch(counts[j, :, 1], counts[j, :, 2], area[j], perim[j], first, nx, ny)
+        bd = boundary[j].astype(np.float64).tolist()
+        for i in range(b):
+            out[i].append({"regions": min(alive[i], int(r)), **reg[i], "density": bd[i] / float(nx * ny)})   # metrics.py:51, :157
+    return out
+
+
+def metrics_sweep_resident(labels, merges, alive, contours, truth: DeviceTruth, regions, agreement=False) -> list:
+    """Per image a list with one dict per R of ``regions`` holding the seven keys of the reference's ``metrics.get_metrics()``
+    (regions, recall, precision, underseg, undersegNP, compactness, density) and ``fmeasure``; agreement=True adds PRI, VoI and
+    covering. The numbers ``all_scores_batch_resident(cut_regions_device(labels, merges, alive, R), truth, agreement=...)`` gives
+    for every R, from one tree and one contour map: ``boundary_sweep_resident`` + ``sweep_scores``, ``under_sweep_resident`` and
+    ``cut_shapes_device`` + ``sweep_reference_scores``, ``sweep_agreement``. Raises the reference's ZeroDivisionError where
+    ``sweep_scores`` does (a cut without a boundary pixel: R = 1), once the sweeps have run: only their counts show it. Every
+    argument is checked before the first launch."""
+    _need_tree_and_cuts(labels, merges, alive, regions, truth)
+    _need_contours(contours, labels)
+    if max(labels.shape[1:]) > 4096:
+        raise ValueError("the sweep takes images of at most 4096 x 4096 pixels")
+    got = under_sweep_resident(labels, merges, alive, truth, regions, agreement)
+    counts = got[0] if agreement else got
+    shapes = cut_shapes_device(labels, contours, merges, alive, regions)
+    hists = boundary_sweep_resident(contours, alive, truth)
+    alive_h = alive.cpu().numpy()
+    h, w = labels.shape[1:]
+    rows = sweep_scores(hists, alive_h, truth.bd_counts.cpu().numpy(), truth.first, regions)
+    ref = sweep_reference_scores(counts, *shapes, alive_h, truth.first, h, w, regions)
+    out = [[{**s, **r} for s, r in zip(srow, rrow)] for srow, rrow in zip(rows, ref)]
+    if agreement:
+        agree = sweep_agreement(got[1], got[2], truth.first, h * w, regions)
+        out = [[{**s, **a} for s, a in zip(row, arow)] for row, arow in zip(out, agree)]
+    return out

@@ -472,6 +472,51 @@ int gcs_region_sweep(uint32_t *leaf_hist_dev, const int32_t *merges_dev, const i
                      const int32_t *regions_dev, int B, int T, int K, int n_truth_labels, int n_cuts, void *workspace_dev,
                      uint64_t *sums_out_dev, double *terms_out_dev, gcs_stream_t stream);
 
+/* ---- the reference's region and shape metrics of every cut of the region tree at once (SPEC.md §17) --- */
+
+/* The integer part of underseg, undersegNP, compactness and density of /root/reference/BSD_metrics/metrics.py:128-201 for the cut at
+ * every R = regions_dev[c], from the inputs of gcs_region_sweep and the contour map of gcs_region_tree_contours; no pixel is
+ * relabelled. The host finishes the floats (evaluate_gpu.sweep_reference_scores).
+ *   gcs_region_sweep_under_workspace_bytes  host only: what gcs_region_sweep_workspace_bytes returns. 0 for a bad argument.
+ *   gcs_region_sweep_under           gcs_region_sweep's walk over the same inputs under the same rules (one launch, a workgroup per
+ *                                    annotator map, leaf_hist_dev CONSUMED, regions_dev strictly decreasing and read on the device: an
+ *                                    entry that is not below its predecessor gets the sums of a coarser table, nothing is read or
+ *                                    written out of range; an img_of_dev entry outside 0 .. B-1 gets the leaf table at every cut). Per
+ *                                    cut and annotator map, from the table of the cut with a_i its row sums:
+ *                                      under_out_dev uint64 [n_cuts][T][3] = { N = sum_i a_i, sum_i (a_i - max_j n_ij),
+ *                                                                              sum_ij min(n_ij, a_i - n_ij) }
+ *                                    sums_out_dev / terms_out_dev: both NULL, or both given: they then receive exactly what
+ *                                    gcs_region_sweep writes for the same inputs, bit for bit, from the same walk; under_out_dev does not
+ *                                    depend on them. No allocation, no host synchronisation (capturable). Workspace and outputs may hold
+ *                                    anything on entry; every output element is written.
+ *   gcs_cut_shapes_workspace_bytes   host only: per image uint32 bins [K][n_cuts + 1], area [K], bd [n_cuts + 1]. 0 for a bad argument.
+ *   gcs_cut_shapes                   three launches on `stream` (zero; one pass over labels_dev and contours_dev; a workgroup per image).
+ *                                    contours_dev int32 [B][H][W]: what gcs_region_tree_contours wrote for the same labels_dev,
+ *                                    merges_dev and alive_dev. With tau_c = max(0, alive_b - regions_dev[c]) and rep(q) the smallest
+ *                                    label of q's group in the cut c (the merge rows that count: as in gcs_region_sweep):
+ *                                      area_out_dev     uint32 [n_cuts][B][K]  [c][b][r] = #{pixels whose label's rep is r}
+ *                                      perim_out_dev    uint32 [n_cuts][B][K]  [c][b][r] = #{those on the image border or with U > tau_c}
+ *                                      boundary_out_dev uint32 [n_cuts][B]     [c][b]    = #{pixels with U > tau_c}
+ *                                    Labels that are absorbed or own no pixel have area 0 and perimeter 0. A pixel whose label is
+ *                                    outside 0 .. K-1 is counted in no area and no perimeter; it counts in boundary_out_dev by its U.
+ *                                    regions_dev int32 [n_cuts], strictly decreasing, read on the device: an entry that is not below its
+ *                                    predecessor gets its predecessor's (coarser) cut, nothing is read or written out of range. No
+ *                                    allocation, no host synchronisation (capturable). Workspace and outputs may hold anything on entry;
+ *                                    every output element is written. With K = 1 merges_dev is not read and may be NULL.
+ * GCS_EINVAL, with nothing launched: a NULL pointer (merges_dev may be NULL with K = 1; sums_out_dev and terms_out_dev may both be
+ * NULL, not one of them), B outside 1..65535, T outside 1..1000000, H or W outside 1..4096, K outside 1..4096, n_truth_labels < 1,
+ * n_cuts outside 1..64, T * K * n_truth_labels >= 2^31, B * H * W >= 2^31, B * (K * (n_cuts + 2) + n_cuts + 1) >= 2^31 (the
+ * workspace counters; the outputs are fewer).
+ * Added within ABI 18: new entry points change no existing call, so GCS_ABI_VERSION did not move. */
+size_t gcs_region_sweep_under_workspace_bytes(int T, int K, int n_truth_labels, int n_cuts);
+int gcs_region_sweep_under(uint32_t *leaf_hist_dev, const int32_t *merges_dev, const int32_t *alive_dev, const int32_t *img_of_dev,
+                           const int32_t *regions_dev, int B, int T, int K, int n_truth_labels, int n_cuts, void *workspace_dev,
+                           uint64_t *under_out_dev, uint64_t *sums_out_dev, double *terms_out_dev, gcs_stream_t stream);
+size_t gcs_cut_shapes_workspace_bytes(int B, int K, int n_cuts);
+int gcs_cut_shapes(const int32_t *labels_dev, const int32_t *contours_dev, const int32_t *merges_dev, const int32_t *alive_dev,
+                   const int32_t *regions_dev, int B, int H, int W, int K, int n_cuts, void *workspace_dev, uint32_t *area_out_dev,
+                   uint32_t *perim_out_dev, uint32_t *boundary_out_dev, gcs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,8 +95,8 @@ def _raw_calls(torch, lib, c):
     return leaf, sweep, lambda: hist.copy_(saved)
 
 
-def _per_cut(torch, s, res, prefix=""):
-    """The path the sweep replaces, per R: the cut, the scoring call with agreement=True (device time and host clock)."""
+def _per_cut(torch, s, res, prefix="", agreement=True):
+    """The path the sweep replaces, per R: the cut, the scoring call with ``agreement`` (device time and host clock)."""
     from gabor_color_image_segmentation_amd.evaluate_gpu import all_scores_batch_resident, submit_scores_batch_resident
     c = s["cases"][""]
     cut = torch.empty_like(c["lab"])
@@ -108,13 +108,13 @@ def _per_cut(torch, s, res, prefix=""):
         for _ in range(WARM + REPS):                     # the second event goes in behind the result copy, before the host waits for it
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            pending = submit_scores_batch_resident(cut, c["truth"], n_segments=r, agreement=True)
+            pending = submit_scores_batch_resident(cut, c["truth"], n_segments=r, agreement=agreement)
             e1.record()
             pending.result()
             e1.synchronize()
             times.append(e0.elapsed_time(e1))
         sc = (statistics.median(times[WARM:]),)
-        wl = _wall_ms(torch, lambda: all_scores_batch_resident(cut, c["truth"], n_segments=r, agreement=True))
+        wl = _wall_ms(torch, lambda: all_scores_batch_resident(cut, c["truth"], n_segments=r, agreement=agreement))
         res.update({"%sscore_ms_%d" % (prefix, r): sc[0], "%sscore_wall_ms_%d" % (prefix, r): wl[0]})
         dev += m[0] + sc[0]
         wall += m[0] + wl[0]
