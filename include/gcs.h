@@ -372,7 +372,9 @@ int gcs_position_features(uint16_t *feats_dev, int B, int H, int W, int n_scales
  *                                   2 <= n <= 4096. ny * nx may exceed 4096 (small S): the two calls below refuse such a grid.
  *   gcs_superpixel_workspace_bytes  host only: bytes of workspace_dev for the grid of (H, W, n): per image the centres, their positions
  *                                   and one [K][D + 3] row set of uint64 sums (features, y, x, count). 0 for a bad argument. Contents are
- *                                   undefined before and after a call (nothing to zero).
+ *                                   undefined before and after a call (nothing to zero). For a caller-chosen ny x nx grid: the call lays
+ *                                   the workspace out by its own K = ny * nx, so the size for any n whose grid has at least that many
+ *                                   centres suffices.
  *   gcs_superpixel_segment          enqueues the whole schedule on `stream`: init (centre (i, j) := the pixel at cy = floor((2i+1) H /
  *                                   (2 ny)), cx = floor((2j+1) W / (2 nx))), then n_iter assign passes with an update launch behind all
  *                                   but the last: 2 n_iter launches (+1 with centres_out_dev). No allocation, no host synchronisation

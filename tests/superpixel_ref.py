@@ -46,24 +46,35 @@ def candidates(h, w, ny, nx):
     return np.stack(out)
 
 
-def assign(x, cent, cy, cx, ny, nx, lam, cand=None):
+def assign(x, cent, cy, cx, ny, nx, lam, cand=None, info=None):
     """x (D, H, W), cent (K, D), cy / cx (K,), all int64 -> labels (H, W) int64: the argmin over the existing 3 x 3 candidates of
-    sum_d (x_d - c_d)^2 + lam ((y - cy)^2 + (x - cx)^2), ties to the lowest centre index."""
+    sum_d (x_d - c_d)^2 + lam ((y - cy)^2 + (x - cx)^2), ties to the lowest centre index. ``info``, a dict, receives what the tests'
+    witnesses need and the labels do not: ``tied`` = the pixels whose least distance two or more distinct centres attain, ``dmax`` =
+    the largest distance of a pixel and an existing candidate, ``smax`` = the largest spatial term of one."""
     d, h, w = x.shape
     if cand is None:
         cand = candidates(h, w, ny, nx)
     yy, xx = np.mgrid[0:h, 0:w].astype(np.int64)
     best = np.full((h, w), np.iinfo(np.int64).max, np.int64)
     lab = np.full((h, w), -1, np.int64)
+    at_best = np.zeros((h, w), np.int64)             # candidates at the least distance so far (they are distinct centres)
+    dmax = smax = 0
     for q in cand:                                   # di-major, dj-minor: increasing centre index
         ok = q >= 0
         qq = np.where(ok, q, 0)
         dist = lam * ((yy - cy[qq]) ** 2 + (xx - cx[qq]) ** 2)
+        if info is not None and ok.any():
+            smax = max(smax, int(dist[ok].max()))
         for p in range(d):                           # plane by plane: no (H, W, D) temporary
             dist = dist + (x[p] - cent[qq, p]) ** 2
+        if info is not None and ok.any():
+            dmax = max(dmax, int(dist[ok].max()))
+            at_best = np.where(ok & (dist < best), 1, np.where(ok & (dist == best), at_best + 1, at_best))
         better = ok & ((dist < best) | ((dist == best) & (q < lab)))
         best = np.where(better, dist, best)
         lab = np.where(better, q, lab)
+    if info is not None:
+        info.update(tied=int((at_best >= 2).sum()), dmax=dmax, smax=smax)
     return lab
 
 
@@ -91,9 +102,13 @@ def _isum(idx, vals, k):
     return out
 
 
-def superpixels(x, n, lam=576, n_iter=10, return_centres=False):
-    """Canonical features x (D, H, W) (uint16 values) -> labels (H, W) int32 of SPEC.md §13: init, then n_iter assigns with an update
-    behind all but the last. With ``return_centres``: also (K, D + 2) int64 = the D features, cy, cx the last assign used."""
+def superpixels_on_grid(x, ny, nx, lam=576, n_iter=10, return_centres=False, trace=None):
+    """Canonical features x (D, H, W) (uint16 values) -> labels (H, W) int32 of SPEC.md §13 on the caller's ny x nx grid (any 1 <= ny
+    <= H, 1 <= nx <= W with ny * nx <= 4096, as gcs_superpixel_segment takes it): init, then n_iter assigns with an update behind all
+    but the last. With ``return_centres``: also (K, D + 2) int64 = the D features, cy, cx the last assign used.
+    ``trace``, a list, receives one dict per pass: ``empty`` = the centres the pass gave no pixel, ``empty_ids`` = which, ``tied`` =
+    the pixels whose least distance two or more distinct centres attain, ``dmax`` / ``smax`` = the largest distance / spatial term of
+    a pixel and a candidate. The labels and centres do not depend on it."""
     x = np.asarray(x).astype(np.int64)
     d, h, w = x.shape
     if not (isinstance(lam, (int, np.integer)) and 1 <= lam <= LAMBDA_MAX):
@@ -102,18 +117,32 @@ def superpixels(x, n, lam=576, n_iter=10, return_centres=False):
         raise ValueError("n_iter must be >= 1")
     if d > D_MAX:
         raise ValueError("D must be at most 207")
-    _, ny, nx = grid(h, w, n)
+    if not (1 <= h <= SIDE_MAX and 1 <= w <= SIDE_MAX):
+        raise ValueError("H, W must be in 1..4096")
+    if not (1 <= ny <= h and 1 <= nx <= w and ny * nx <= K_MAX):
+        raise ValueError("the grid needs 1 <= ny <= H, 1 <= nx <= W, ny * nx <= 4096")
     cy, cx = init_positions(h, w, ny, nx)
     cent = x[:, cy, cx].T.copy()
     cand = candidates(h, w, ny, nx)
     for t in range(n_iter):
-        lab = assign(x, cent, cy, cx, ny, nx, int(lam), cand)
+        info = None if trace is None else {}
+        lab = assign(x, cent, cy, cx, ny, nx, int(lam), cand, info)
+        if trace is not None:
+            none = np.flatnonzero(np.bincount(lab.ravel(), minlength=ny * nx) == 0)
+            trace.append(dict(info, empty=len(none), empty_ids=none.tolist()))
         if t < n_iter - 1:
             cent, cy, cx = update(x, lab, cent, cy, cx)
     lab = lab.astype(np.int32)
     if return_centres:
         return lab, np.concatenate([cent, cy[:, None], cx[:, None]], axis=1)
     return lab
+
+
+def superpixels(x, n, lam=576, n_iter=10, return_centres=False):
+    """``superpixels_on_grid`` on the grid of (H, W, n)."""
+    x = np.asarray(x)
+    _, ny, nx = grid(x.shape[1], x.shape[2], n)
+    return superpixels_on_grid(x, ny, nx, lam, n_iter, return_centres)
 
 
 def segment(img, n, lam=576, n_iter=10, w=0.0, g=0, mu=0, n_scales=4, n_orient=6, smoothing=0.0, return_centres=False, **bank_kw):

@@ -436,3 +436,50 @@ def test_quality_of_six_val_images_through_the_gpu(torch_cuda):
                 assert got[key] == want[key], (state, i, key, got[key], want[key])
             for key in ("underseg", "undersegNP", "compactness", "PRI", "VoI", "covering"):
                 assert abs(got[key] - want[key]) <= 1e-12, (state, i, key, got[key], want[key])
+
+
+# ---- the statistics kernel's 32-slot table at its threshold
+
+def _bucket(l):
+    """The slot a label's probe starts at in rt_stats_kernel's table (restated as a witness: the expected values do not use it)."""
+    return ((int(l) * 2654435761) % 2 ** 32) >> 27
+
+
+def _columns(labels):
+    """An 8 x len(labels) block: every label an 8 x 1 column."""
+    return np.broadcast_to(np.asarray(labels, np.int32), (8, len(labels))).copy()
+
+
+def _threshold_map(bucket, k=4096):
+    """16 x 64, four 8 x 32 tiles, all their labels from ONE bucket of the table's hash (so every probe walks a chain through the
+    whole table): top left exactly 32 labels (the LDS form with every slot taken), top right the same 32 and a 33rd label in one
+    pixel (the global form: both forms add into the same 32 rows of sums), bottom left another 32 labels and pixels outside
+    0 .. K-1 (-1 and K, among them a whole eight-lane group), bottom right 32 labels of which 16 are the top row's."""
+    own = [l for l in range(k) if _bucket(l) == bucket]
+    assert 127 <= len(own) <= 130
+    lab = np.empty((16, 64), np.int32)
+    lab[:8, :32] = _columns(own[:32])
+    lab[:8, 32:] = _columns(own[:32][::-1])
+    lab[5, 45] = own[32]
+    lab[8:, :32] = _columns(own[33:65])
+    lab[9, 5], lab[12, 17], lab[15, 31] = -1, k, k
+    lab[10, 8:16] = -1
+    lab[8:, 32:] = _columns(own[16:32] + own[65:81])
+    return lab
+
+
+@pytest.mark.parametrize("buckets", [(0, 31), (13,)])
+def test_stats_table_at_32_labels_and_one_more(torch_cuda, buckets):
+    """K = 4096, D = 3: tiles with exactly 32 labels, with 33, and with 32 plus out-of-range pixels (see ``_threshold_map``), one
+    image per bucket. The sums stay in the workspace; merges, costs, alive and cuts are functions of them and are compared."""
+    k = 4096
+    lab = np.stack([_threshold_map(b) for b in buckets])
+    for m, b in zip(lab, buckets):
+        seen = [np.unique(t[(t >= 0) & (t < k)]) for t in (m[:8, :32], m[:8, 32:], m[8:, :32], m[8:, 32:])]
+        assert [len(s) for s in seen] == [32, 33, 32, 32]
+        assert all(_bucket(l) == b for s in seen for l in s)
+        assert set(seen[0]) <= set(seen[1]) and len(set(seen[0]) & set(seen[3])) == 16
+        assert (m[8:, :32] == -1).sum() == 9 and (m[8:, :32] == k).sum() == 2
+    x = np.random.default_rng(32).integers(0, 46341, (len(buckets), 3, 16, 64)).astype(np.uint16)
+    refs = _check_tree(torch_cuda, x, lab, k, (1, 8, 4096))
+    assert all(a == 81 for _, _, a in refs)
