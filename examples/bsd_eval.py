@@ -42,6 +42,9 @@ OIS of each of the three (VoI: the lowest). Without `--sweep` the per-cut path a
 `--regions R[,R...] --sweep --reference-metrics`: the reference's other columns beside them - underseg, undersegNP, compactness,
 density and regions - of every listed R from the same tree and contour map (SPEC.md §17: `evaluate_gpu.under_sweep_resident`,
 `cut_shapes_device`, `sweep_reference_scores`); combines with `--agreement`.
+`--tree-nodes components` beside `--regions` (with or without `--sweep`): the tree on the connected regions of the superpixel map
+(SPEC.md §18: `Segmenter(tree_nodes="components")`): every cut at R is R connected regions, `--min-region-size` goes into the node
+map instead of running behind every cut, and the sweeps describe the delivered maps.
 """
 import os
 import sys
@@ -149,7 +152,7 @@ def superpixel_row(n, lam, n_orient, cw, g, merge):
         float(np.mean([r["regions"] for r in rows]))))
 
 
-def region_rows(n, lam, n_orient, cw, g, merge, regions):
+def region_rows(n, lam, n_orient, cw, g, merge, regions, tree_nodes="superpixels"):
     import numpy as np
     import torch
     from gabor_color_image_segmentation_amd import Segmenter, superpixel_grid
@@ -160,10 +163,15 @@ def region_rows(n, lam, n_orient, cw, g, merge, regions):
     truth = PackedTruth(os.path.join(gold, "bsd500_truth.npz"))
     ids = [str(i) for i in pack["ids"]]
     rows = {r: [] for r in regions}
+    components = tree_nodes == "components"
     seg = Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, n_superpixels=n, spatial_weight=lam)
     for shape in sorted({pack["img_" + i].shape[:2] for i in ids}):
         group = [i for i in ids if pack["img_" + i].shape[:2] == shape]
         m = superpixel_grid(shape[0], shape[1], n)[0] ** 2 // 4 if merge == "auto" else int(merge)
+        if components:                                   # m is part of the node map (SPEC.md §18): nothing runs behind a cut
+            seg = Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, n_superpixels=n, spatial_weight=lam,
+                            tree_nodes=tree_nodes, min_region_size=m)
+            m = 0
         labels, merges, _, alive = seg.region_tree_device(torch.from_numpy(np.stack([pack["img_" + i] for i in group])).cuda())
         dt = truth.to_device(group)
         for r in regions:                                # one tree, a relabel per R
@@ -181,7 +189,7 @@ def region_rows(n, lam, n_orient, cw, g, merge, regions):
             "%.4f" % float(np.mean([x[k] for x in rows[r]])) for k in keys), float(np.mean([x["regions"] for x in rows[r]]))))
 
 
-def sweep_rows(n, lam, n_orient, cw, g, regions, agreement=False, reference=False):
+def sweep_rows(n, lam, n_orient, cw, g, regions, agreement=False, reference=False, tree_nodes="superpixels"):
     import numpy as np
     import torch
     from gabor_color_image_segmentation_amd import Segmenter
@@ -194,7 +202,7 @@ def sweep_rows(n, lam, n_orient, cw, g, regions, agreement=False, reference=Fals
     pack = np.load(os.path.join(gold, "bsd_val_images.npz"))
     truth = PackedTruth(os.path.join(gold, "bsd500_truth.npz"))
     ids = [str(i) for i in pack["ids"]]
-    seg = Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, n_superpixels=n, spatial_weight=lam)
+    seg = Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, n_superpixels=n, spatial_weight=lam, tree_nodes=tree_nodes)
     rows, agree, ref = [], [], []
     for shape in sorted({pack["img_" + i].shape[:2] for i in ids}):
         group = [i for i in ids if pack["img_" + i].shape[:2] == shape]
@@ -235,12 +243,12 @@ if __name__ == '__main__':
             sweep_rows(one("--superpixels", int, 300), one("--spatial-weight", int, 576), one("--n-orient", int, 6),
                        one("--color-weight", float, 0.0), one("--chroma-gain", int, 0),
                        [int(v) for v in one("--regions", str, "8").split(",")], agreement="--agreement" in sys.argv,
-                       reference="--reference-metrics" in sys.argv)
+                       reference="--reference-metrics" in sys.argv, tree_nodes=one("--tree-nodes", str, "superpixels"))
             sys.exit(0)
         if "--regions" in sys.argv:
             region_rows(one("--superpixels", int, 300), one("--spatial-weight", int, 576), one("--n-orient", int, 6),
                         one("--color-weight", float, 0.0), one("--chroma-gain", int, 0), one("--min-region-size", str, "0"),
-                        [int(v) for v in one("--regions", str, "8").split(",")])
+                        [int(v) for v in one("--regions", str, "8").split(",")], one("--tree-nodes", str, "superpixels"))
             sys.exit(0)
         superpixel_row(one("--superpixels", int, 300), one("--spatial-weight", int, 576), one("--n-orient", int, 6),
                        one("--color-weight", float, 0.0), one("--chroma-gain", int, 0), one("--min-region-size", str, "0"))

@@ -66,6 +66,8 @@ SIGNATURES = {
     "gcs_connected_regions": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "gcs_merge_scratch_bytes": (_sz, [_i, _i, _i, _i]),
     "gcs_merge_small_regions": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "gcs_region_nodes_scratch_bytes": (_sz, [_i, _i, _i]),
+    "gcs_region_nodes": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "gcs_smooth_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "gcs_smooth_features": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "gcs_colour_opponent": (_i, [_vp, _sz, _i, _vp, _vp]),

@@ -172,7 +172,7 @@ __global__ __launch_bounds__(RT_T) void rt_merge_kernel(RtArgs A, int mean_in_ld
     extern __shared__ __attribute__((aligned(16))) unsigned char rt_lds[];
     const int tid = (int)threadIdx.x, b = (int)blockIdx.x, lane = tid & 63, wave = tid >> 6;
     const int K = A.K, D = A.D, E = D + 1, KW = A.KW;
-    int *s_cnt = reinterpret_cast<int *>(rt_lds);                          // [0] alive, [1] pairs of the round
+    int *s_cnt = reinterpret_cast<int *>(rt_lds);                          // [0] alive, [1] pairs of the round, [2] labels in use
     u64 *s_cost = reinterpret_cast<u64 *>(rt_lds + 16);                    // [K]
     uint16_t *s_t = reinterpret_cast<uint16_t *>(rt_lds + 16 + (size_t)8 * K);      // [K] the pick; of a dead node: who absorbed it
     uint16_t *s_pair = reinterpret_cast<uint16_t *>(rt_lds + 16 + (size_t)10 * K);  // [K] the smaller rep of every mutual pair
@@ -183,16 +183,25 @@ __global__ __launch_bounds__(RT_T) void rt_merge_kernel(RtArgs A, int mean_in_ld
     int *merges = A.merges + (size_t)b * (K - 1) * 2;
     u64 *costs = A.costs ? A.costs + (size_t)b * (K - 1) : nullptr;
 
-    if (tid < 2) s_cnt[tid] = 0;
+    if (tid < 3) s_cnt[tid] = 0;
     __syncthreads();
     for (int q = tid; q < K; q += RT_T) {
         const u64 n = sums[(size_t)q * E + D];
         s_flag[q] = n ? 3 : 0;
         s_t[q] = (uint16_t)RT_NONE;
         s_cost[q] = 0;
-        if (n) atomicAdd(&s_cnt[0], 1);
+        if (n) {
+            atomicAdd(&s_cnt[0], 1);
+            atomicMax(&s_cnt[2], q + 1);
+        }
     }
-    for (int idx = tid; idx < K * D; idx += RT_T) {
+    __syncthreads();
+    // Labels >= Ku own no pixel: they are never alive, never adjacent (rt_stats_kernel sets bits between labels of pixels only) and
+    // never picked, so every walk over nodes or over the words of an adjacency row may stop at Ku / KWu (the rows keep their stride
+    // KW). With K at a capacity far above the labels in use (SPEC.md §18: K = 4096 for about 1200 nodes) the rounds cost what the
+    // nodes cost; results are the same bits for every input.
+    const int Ku = s_cnt[2], KWu = (Ku + 31) >> 5;
+    for (int idx = tid; idx < Ku * D; idx += RT_T) {
         const int q = idx / D, d = idx - q * D;
         const u64 n = sums[(size_t)q * E + D];
         mean[idx] = n ? (uint16_t)((2 * sums[(size_t)q * E + d] + n) / (2 * n)) : (uint16_t)0;
@@ -209,13 +218,13 @@ __global__ __launch_bounds__(RT_T) void rt_merge_kernel(RtArgs A, int mean_in_ld
 
     while (alive > 1) {
         // pick: the adjacent node of least (cost, rep), for every node whose neighbourhood changed (all of them in round one)
-        for (int q = wave; q < K; q += RT_NW) {
+        for (int q = wave; q < Ku; q += RT_NW) {
             if (s_flag[q] != 3) continue;                                  // (uniform over the wave)
             const u64 nq = sums[(size_t)q * E + D];
             u64 best = ~0ull;
             unsigned bt = RT_NONE;
-            for (int w0 = 0; w0 < KW; w0 += 64) {                          // the row's words, 64 at a time; the wave then walks the set bits
-                const unsigned mine = w0 + lane < KW ? rt_ld(adj + (size_t)q * KW + w0 + lane) : 0u;
+            for (int w0 = 0; w0 < KWu; w0 += 64) {                         // the row's words, 64 at a time; the wave then walks the set bits
+                const unsigned mine = w0 + lane < KWu ? rt_ld(adj + (size_t)q * KW + w0 + lane) : 0u;
                 u64 nz = __ballot(mine != 0u);
                 while (nz) {
                     const int src = __ffsll((long long)nz) - 1;
@@ -241,7 +250,7 @@ __global__ __launch_bounds__(RT_T) void rt_merge_kernel(RtArgs A, int mean_in_ld
         }
         __syncthreads();
         // mutual pairs, listed by their smaller rep
-        for (int q = tid; q < K; q += RT_T) {
+        for (int q = tid; q < Ku; q += RT_T) {
             if (!(s_flag[q] & 1)) continue;
             const unsigned t = s_t[q];
             if (t != RT_NONE && (unsigned)q < t && s_t[t] == (unsigned)q) s_pair[atomicAdd(&s_cnt[1], 1)] = (uint16_t)q;
@@ -273,7 +282,7 @@ __global__ __launch_bounds__(RT_T) void rt_merge_kernel(RtArgs A, int mean_in_ld
                 mean[(size_t)a * D + e] = (uint16_t)((2 * s + n) / (2 * n));
             }
             if (lane == 0) sums[(size_t)a * E + D] = n;
-            for (int w = lane; w < KW; w += 64) {
+            for (int w = lane; w < KWu; w += 64) {
                 const unsigned v = rt_ld(adj + (size_t)bq * KW + w);
                 if (v) atomicOr(adj + (size_t)a * KW + w, v);
             }
@@ -290,7 +299,7 @@ __global__ __launch_bounds__(RT_T) void rt_merge_kernel(RtArgs A, int mean_in_ld
         // stands for the node that absorbed it. Rows of living nodes hold bits of living nodes only when the round ends.
         for (int i = wave; i < P; i += RT_NW) {
             const unsigned a = s_pair[i], bq = s_t[a];
-            for (int w = lane; w < KW; w += 64) {
+            for (int w = lane; w < KWu; w += 64) {
                 unsigned bits = rt_ld(adj + (size_t)a * KW + w);
                 while (bits) {
                     const unsigned c = (unsigned)(32 * w + __ffs((int)bits) - 1);

@@ -655,7 +655,8 @@ def region_sweep_resident(labels, merges, alive, truth: DeviceTruth, regions):
     truth: the resident ground truth of the same images; regions: 1 .. 64 distinct integers in 1 .. 4096, in any order. Returns host
     arrays ``(sums uint64 [len(regions)][T][4], terms float64 [len(regions)][T][4])`` in the caller's order of ``regions``: per cut and
     annotator map what gcs_region_agreement writes for the contingency table of ``cut_regions_device(labels, merges, alive, R)``
-    (the raw cuts: ``connectivity`` and ``min_region_size`` are not reflected). Two launches (the leaf tables with K rows; the
+    (the raw cuts: ``connectivity`` and ``min_region_size`` are not reflected; with ``tree_nodes="components"``, SPEC.md §18, the
+    delivered maps are the raw cuts). Two launches (the leaf tables with K rows; the
     sweep) and one download. Buffers of its own: ``truth``'s result block and its one-submission rule are not touched."""
     import torch
     labels, merges, alive, regs, order = _need_tree_and_cuts(labels, merges, alive, regions, truth)

@@ -190,6 +190,9 @@ def _on_device(fn):
     return wrapper
 
 
+NODES_MAX = 4096              # SPEC.md §18: K_cap, the most nodes an image's tree can have (= §14's largest K)
+
+
 class HipOps:
     """Thin pointer-passer over the C ABI for one device. Stateless apart from the bank."""
 
@@ -522,6 +525,37 @@ class HipOps:
         _lib.check(self.lib.gcs_merge_small_regions(labels_i32.data_ptr(), b, h, w, int(min_size), scratch.data_ptr(),
                                                     out.data_ptr(), self._stream()), "gcs_merge_small_regions")
 
+    def region_nodes_buffers(self, b, h, w):
+        """What SPEC.md §18 needs for one (batch, shape): ``(scratch, map (B,H,W) int32, n_nodes (B,) int32)`` (a captured graph must
+        own them). ``map`` is the second label map of the stage: the step writes the §13 map there and the node map to its output."""
+        torch = self.torch
+        need = self.lib.gcs_region_nodes_scratch_bytes(b, h, w)
+        if need == 0:
+            raise ValueError("no node map for this shape (1 <= B <= 65535, 1 <= H, W <= 4096)")
+        return (self.empty_bytes(need), torch.empty((b, h, w), dtype=torch.int32, device=self.device),
+                torch.empty((b,), dtype=torch.int32, device=self.device))
+
+    @_on_device
+    def region_nodes(self, labels_i32, min_size, out, n_nodes, scratch=None, k_cap=NODES_MAX, min_size_used=None):
+        """SPEC.md §18 on an int32 (B,H,W) device tensor into ``out`` (not the same memory): the connected regions, merged by §9 at
+        ``min_size`` or, in an image that has more than ``k_cap`` of them, at max(min_size, ceil(H W / k_cap)). ``n_nodes`` (B,)
+        int32 gets the node counts, ``min_size_used`` (None or (B,) int32) the size each image used. ``scratch``: from
+        ``region_nodes_buffers`` (None: a fresh one). Capturable."""
+        b, h, w = labels_i32.shape
+        self._need(labels_i32, self.torch.int32, (b, h, w), "labels must be a contiguous (B,H,W) int32 tensor")
+        self._need(out, self.torch.int32, (b, h, w), "out must be a contiguous (B,H,W) int32 tensor")
+        self._need(n_nodes, self.torch.int32, (b,), "n_nodes must be a contiguous (B,) int32 tensor")
+        self._need(min_size_used, self.torch.int32, (b,), "min_size_used must be a contiguous (B,) int32 tensor")
+        need = self.lib.gcs_region_nodes_scratch_bytes(b, h, w)
+        if scratch is None:
+            scratch = self.empty_bytes(need)
+        elif scratch.numel() < need or scratch.device != self.device:
+            raise ValueError("region_nodes scratch too small or on another device")
+        _lib.check(self.lib.gcs_region_nodes(labels_i32.data_ptr(), b, h, w, int(min_size), int(k_cap), scratch.data_ptr(),
+                                             out.data_ptr(), n_nodes.data_ptr(),
+                                             None if min_size_used is None else min_size_used.data_ptr(), self._stream()),
+                   "gcs_region_nodes")
+
     @_on_device
     def labels_widen(self, labels, b, h, w, out):
         _lib.check(self.lib.gcs_labels_widen(labels.data_ptr(), b, h, w, out.data_ptr(), self._stream()),
@@ -612,6 +646,16 @@ def _check_regions(n_regions, n_superpixels):
     return r
 
 
+def _check_tree_nodes(tree_nodes, n_superpixels):
+    """SPEC.md §18 parameter: "superpixels" (the tree on the raw §13 map) or "components" (on its connected regions; only on top of
+    the superpixel stage). Returns True for "components"."""
+    if tree_nodes not in ("superpixels", "components"):
+        raise ValueError(f'tree_nodes must be "superpixels" or "components", got {tree_nodes!r}')
+    if tree_nodes == "components" and n_superpixels == 0:
+        raise ValueError('tree_nodes = "components" takes the components of the superpixel map: it needs n_superpixels > 0')
+    return tree_nodes == "components"
+
+
 def lloyd(ops, feats, b, h, w, k, n_iter, mode, labels, partials, cent, sums, dist_group=None,
           rows=None, init=None, raster=None, debug=_ENV_DEBUG, fold=None):
     """SPEC.md §4 schedule on one feature slab. ``mode``: 'per_image' or 'global'.
@@ -674,7 +718,9 @@ def lloyd(ops, feats, b, h, w, k, n_iter, mode, labels, partials, cent, sums, di
 # What the per-batch step needs to know of a plan, made once in Segmenter.__init__ (``colour``, ``smooth``, ``position``: is the
 # stage on). The two pieces of the step take it, the ops, a workspace and the debug switches as arguments and never the
 # Segmenter: a graph entry holds them, and an entry that held its plan would be a reference cycle (see _segment_small).
-_StepOptions = collections.namedtuple("_StepOptions", "k n_iter colour smooth position n_superpixels spatial_weight n_regions")
+# ``components``: SPEC.md §18 is on (then ``min_size`` = the plan's min_region_size, the m of the node map).
+_StepOptions = collections.namedtuple("_StepOptions", "k n_iter colour smooth position n_superpixels spatial_weight n_regions "
+                                                      "components min_size")
 
 
 def _opponent(ops, imgs, colour):
@@ -712,23 +758,32 @@ def _step_features(ops, opt, ws, imgs, b, h, w, y0=0, chunk=None):
 
 
 def _stage_buffers(ops, opt, ws, key, b, h, w):
-    """The one place where the buffers of SPEC.md §13 (``key`` "sp": canonical tensor, workspace) and §14 ("rt": workspace,
-    merges, costs, alive) join a workspace: at a stage's first use, or up front for a graph entry. Returns them. A stage that is
-    off leaves no key."""
+    """The one place where the buffers of SPEC.md §13 (``key`` "sp": canonical tensor, workspace), §18 ("nd": scratch, second label
+    map, node counts) and §14 ("rt": workspace, merges, costs, alive; for K = ny * nx, or K_cap = 4096 on the nodes of §18: about
+    5 MB of workspace per image at D = 72, 0.32 GB for a batch of 64) join a workspace: at a stage's first use, or up front for a
+    graph entry. Returns them. A stage that is off leaves no key."""
     if key not in ws:
         _, ny, nx = superpixel_grid(h, w, opt.n_superpixels)
-        ws[key] = ops.superpixel_buffers(b, h, w, opt.n_superpixels) if key == "sp" else ops.region_tree_buffers(b, h, w, ny * nx)
+        if key == "sp":
+            ws[key] = ops.superpixel_buffers(b, h, w, opt.n_superpixels)
+        elif key == "nd":
+            ws[key] = ops.region_nodes_buffers(b, h, w)
+        else:
+            ws[key] = ops.region_tree_buffers(b, h, w, NODES_MAX if opt.components else ny * nx)
     return ws[key]
 
 
-def _step_cluster(ops, opt, ws, out, b, h, w, mode, debug, dist_group=None, rows=None, init=None, centres=None, tree=None):
+def _step_cluster(ops, opt, ws, out, b, h, w, mode, debug, dist_group=None, rows=None, init=None, centres=None, tree=None,
+                  nodes=None):
     """The second piece of the per-batch step, on the slab ``_step_features`` has filled: the labels of ``b`` images into ``out``,
     a contiguous (B,H,W) device tensor. ``n_superpixels = 0``: the Lloyd loop of SPEC.md §4 (``rows``, ``init``, ``dist_group``:
     see ``lloyd``); without a raster pass the label slab is widened into the int32 ``out``. ``n_superpixels > 0`` (SPEC.md §13
     instead of §4): features -> canonical tensor -> the one call that enqueues every pass (``centres``: see
     ``HipOps.superpixels``), then the tree of SPEC.md §14 on the raw §13 map and its cut in place. ``tree``: None = as the plan
     says (tree and cut at ``n_regions`` when that is on), True = the tree without a cut (it stays in ``ws["rt"]``), False = no
-    tree. A uint8 ``out`` is narrowed from the int32 map of the workspace (a graph entry)."""
+    tree. With ``tree_nodes = "components"`` (SPEC.md §18) the §13 map goes to the stage's own buffer, its node map to the output,
+    and tree and cut run on that, the tree at K_cap; ``nodes=False`` leaves the §13 map as it is. A uint8 ``out`` is narrowed from
+    the int32 map of the workspace (a graph entry)."""
     if opt.n_superpixels == 0:
         raster = out if rows is None and hasattr(ops, "assign_raster") else None      # the last pass writes the raster map itself
         lloyd(ops, ws["feats"], b, h, w, opt.k, opt.n_iter, mode, ws["labels"], ws["partials"], ws["cent"], ws["sums"],
@@ -739,12 +794,19 @@ def _step_cluster(ops, opt, ws, out, b, h, w, mode, debug, dist_group=None, rows
     _, ny, nx = superpixel_grid(h, w, opt.n_superpixels)
     (canon, spws), out32 = _stage_buffers(ops, opt, ws, "sp", b, h, w), ws.get("out32", out)
     _unpack(ops, ws, b, h, w, out=canon)
-    ops.superpixels(canon, b, h, w, ny, nx, opt.spatial_weight, opt.n_iter, out32, spws, centres)
+    K = ny * nx
+    if opt.components if nodes is None else nodes:
+        ndws, raw, n_nodes = _stage_buffers(ops, opt, ws, "nd", b, h, w)
+        ops.superpixels(canon, b, h, w, ny, nx, opt.spatial_weight, opt.n_iter, raw, spws, centres)
+        ops.region_nodes(raw, opt.min_size, out32, n_nodes, scratch=ndws)
+        K = NODES_MAX
+    else:
+        ops.superpixels(canon, b, h, w, ny, nx, opt.spatial_weight, opt.n_iter, out32, spws, centres)
     if opt.n_regions > 0 if tree is None else tree:
         rtws, merges, costs, alive = _stage_buffers(ops, opt, ws, "rt", b, h, w)
-        ops.region_tree(canon, out32, b, h, w, ny * nx, rtws, merges, costs, alive)
+        ops.region_tree(canon, out32, b, h, w, K, rtws, merges, costs, alive)
         if tree is None:
-            ops.region_tree_cut(out32, merges, alive, b, h, w, ny * nx, opt.n_regions, out32)
+            ops.region_tree_cut(out32, merges, alive, b, h, w, K, opt.n_regions, out32)
     if out32 is not out:
         out.copy_(out32)                           # (K, or min(K, R), <= 256 was checked: the narrowing keeps every label)
 
@@ -781,7 +843,7 @@ class Segmenter:
     def __init__(self, n_scales=4, n_orient=6, k=8, n_iter=10, ksize=13, f_max=0.4,
                  ratio=math.sqrt(2.0), bandwidth=1.0, connectivity=False, device="cuda:0", ops=None,
                  slab_candidates=1, min_region_size=0, smoothing=0.0, color_weight=0.0, chroma_gain=0,
-                 position_weight=0, n_superpixels=0, spatial_weight=576, n_regions=0):
+                 position_weight=0, n_superpixels=0, spatial_weight=576, n_regions=0, tree_nodes="superpixels"):
         """``n_superpixels = n`` (SPEC.md §13; 0 = off, 2..4096): grid-local k-means instead of the Lloyd stage - about n compact
         superpixels per image (K = ny * nx of ``superpixel_grid``) on the same features; ``k`` and ``mode`` are then unused (centres
         are per image). ``spatial_weight`` = lambda (1..65535, default 576) weighs the squared pixel distance to a centre against
@@ -790,7 +852,13 @@ class Segmenter:
 
         ``n_regions = R`` (SPEC.md §14; 0 = off, 1..4096; needs ``n_superpixels > 0``): the superpixels are merged on their adjacency
         graph, cheapest mutual pair first, until min(R, superpixels in use) regions are left; ``connectivity`` and
-        ``min_region_size`` then apply to that map. ``region_tree_device`` / ``cut_regions_device`` give the tree itself and any cut."""
+        ``min_region_size`` then apply to that map. ``region_tree_device`` / ``cut_regions_device`` give the tree itself and any cut.
+
+        ``tree_nodes = "components"`` (SPEC.md §18; needs ``n_superpixels > 0``): the tree's nodes are the 4-connected components of
+        the superpixel map (with ``min_region_size = m > 0``: merged by §9 at m first) instead of its labels, so a cut at R IS
+        min(nodes, R) connected regions, numbered in raster order of first pixel, and contour map and sweeps describe the delivered
+        maps. ``connectivity`` and ``min_region_size`` are not run again behind the cut. Without ``n_regions`` the node map itself
+        is delivered. The default, "superpixels", is the tree on the raw map."""
         if not (1 <= k <= _lib.K_MAX):
             raise ValueError(f"k must be in 1..{_lib.K_MAX}")
         if n_iter < 1:
@@ -815,6 +883,10 @@ class Segmenter:
         self.n_regions = _check_regions(n_regions, self.n_superpixels)          # SPEC.md §14 (0: the superpixel map as it is)
         if self.n_regions > 0 and not all(hasattr(self.ops, m) for m in ("region_tree_buffers", "region_tree", "region_tree_cut")):
             raise ValueError("Segmenter(n_regions=R, ops=...) needs ops that have the region tree")
+        self.tree_nodes = tree_nodes
+        self._components = _check_tree_nodes(tree_nodes, self.n_superpixels)    # SPEC.md §18
+        if self._components and not all(hasattr(self.ops, m) for m in ("region_nodes_buffers", "region_nodes")):
+            raise ValueError('Segmenter(tree_nodes="components", ops=...) needs ops that have the node map')
         if self.smoothing > 0 and getattr(self.ops, "smoothing", 0.0) != self.smoothing:
             raise ValueError("Segmenter(smoothing=K, ops=...) needs ops built with the same smoothing")
         if getattr(self.ops, "chroma_gain", 0) != self.chroma_gain:
@@ -832,7 +904,8 @@ class Segmenter:
         self.slab_candidates = int(self.debug.slab_candidates or slab_candidates)
         self.slab_placement_ms = None
         self._opt = _StepOptions(self.k, int(n_iter), self.chroma_gain > 0, self.smoothing > 0, self.position_weight > 0,
-                                 self.n_superpixels, self.spatial_weight, self.n_regions)
+                                 self.n_superpixels, self.spatial_weight, self.n_regions, self._components,
+                                 self.min_region_size)
         self._ws = {}
         self._host = {}
         self._stream = {}
@@ -855,6 +928,11 @@ class Segmenter:
         """True when the ops are HipOps (libgcs.so). The only other ops are the CPU tests' stand-in for the host logic
         (tests/fake_ops.py), which has no slabs, streams or graphs: the pipelined / captured host paths need ``native``."""
         return hasattr(self.ops, "lib")
+
+    @property
+    def _post_passes(self):
+        """Do ``connectivity`` / ``min_region_size`` run behind the step? Not in the mode of SPEC.md §18, whose maps are connected."""
+        return (self.connectivity or self.min_region_size > 0) and not self._components
 
     @property
     def n_iter(self):
@@ -884,9 +962,12 @@ class Segmenter:
             out_dtype = np.dtype(out_dtype)
             if out_dtype not in (np.dtype(np.int32), np.dtype(np.uint8)):
                 raise ValueError("out_dtype must be int32 or uint8")
-            if self.connectivity and out_dtype == np.uint8:
+            if self._components:
+                if out_dtype == np.uint8 and not 1 <= self.n_regions <= 256:
+                    raise ValueError('tree_nodes = "components": uint8 labels need n_regions in 1..256 (the node count is data)')
+            elif self.connectivity and out_dtype == np.uint8:
                 raise ValueError("connectivity=True needs int32 labels")
-            if self.min_region_size > 0 and out_dtype == np.uint8:
+            elif self.min_region_size > 0 and out_dtype == np.uint8:
                 raise ValueError("min_region_size > 0 needs int32 labels")
         h = w = None
         if imgs is not None:
@@ -906,7 +987,7 @@ class Segmenter:
         if mode == "global":
             import torch.distributed as td
             dist_on = td.is_available() and td.is_initialized()
-        return self.native and not self.connectivity and self.min_region_size == 0 and not dist_on \
+        return self.native and not self._post_passes and not dist_on \
             and not self.debug.force_collectives and (superpixels or self.n_superpixels == 0)
 
     def _host_path(self, b, h, w, mode):
@@ -942,6 +1023,8 @@ class Segmenter:
         if private is not None:
             if opt.n_superpixels > 0:
                 _stage_buffers(ops, opt, ws, "sp", n, h, w)
+                if opt.components:
+                    _stage_buffers(ops, opt, ws, "nd", n, h, w)
                 if opt.n_regions > 0:
                     _stage_buffers(ops, opt, ws, "rt", n, h, w)
                 if private == np.uint8:
@@ -1035,6 +1118,8 @@ class Segmenter:
                 ws = self._workspace(n, h, w, mode) if n == g else self._tail_workspace(n, h, w, mode)
                 _step_features(self.ops, self._opt, ws, imgs[g0:g0 + n], n, h, w)
                 _step_cluster(self.ops, self._opt, ws, out[g0:g0 + n], n, h, w, mode, self.debug, dist_group)
+            if not self._post_passes:                      # (SPEC.md §18: the step's map is connected and numbered as §7 numbers)
+                return out
             if self.min_region_size > 0:
                 regions = torch.empty_like(out)
                 self.ops.merge_small_regions(out, self.min_region_size, regions)
@@ -1061,13 +1146,18 @@ class Segmenter:
             raise ValueError(f"n_superpixels = {self.n_superpixels} on {h} x {w} pixels gives a grid of {ny} x {nx} centres, "
                              f"more than {SUPERPIXELS_MAX}")
         n_labels = min(ny * nx, self.n_regions) if self.n_regions > 0 else ny * nx      # SPEC.md §14: a cut has min(alive, R) labels
+        if self._components:
+            n_labels = self.n_regions                      # SPEC.md §18: min(nodes, R); uint8 without R was refused in _check_args
         if out_dtype is not None and np.dtype(out_dtype) == np.uint8 and n_labels > 256:
             raise ValueError(f"out_dtype uint8 cannot hold the {n_labels} labels of this superpixel grid")
         return ny, nx
 
-    def _superpixel_maps(self, imgs, tree, centres=False):
+    def _superpixel_maps(self, imgs, tree, centres=False, nodes=None):
         """The step on a (B,H,W,3) uint8 device tensor with SPEC.md §13 as its second piece and no post-passes: the fresh int32 §13
-        map, the workspace (``tree``: the uncut tree of SPEC.md §14 is in its ``"rt"``) and, if asked for, the centres."""
+        map (the node map of SPEC.md §18 in that mode, unless ``nodes=False``), the workspace (``tree``: the uncut tree of SPEC.md
+        §14 is in its ``"rt"``) and, if asked for, the centres. In the mode of §18 the tree is built here, behind one read of the
+        batch's node counts, at K = the largest of them rounded up to a multiple of 64 (the tree does not depend on K beyond
+        capacity): merge list and the sweeps' tables stay as small as the batch allows."""
         torch = _torch()
         self._check_args(imgs, kind="tensor")
         imgs = imgs.contiguous()
@@ -1078,13 +1168,21 @@ class Segmenter:
             _step_features(self.ops, self._opt, ws, imgs, b, h, w)
             out = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
             centres = torch.empty((b, ny * nx, self.bank.n_features + 2), dtype=torch.int32, device=imgs.device) if centres else None
-            _step_cluster(self.ops, self._opt, ws, out, b, h, w, "per_image", self.debug, centres=centres, tree=tree)
+            trim = tree and self._components and nodes is None
+            _step_cluster(self.ops, self._opt, ws, out, b, h, w, "per_image", self.debug, centres=centres,
+                          tree=False if trim else tree, nodes=nodes)
+            if trim:
+                K = min(NODES_MAX, -(-int(ws["nd"][2].max()) // 64) * 64)
+                ws["rt"] = self.ops.region_tree_buffers(b, h, w, K)
+                self.ops.region_tree(ws["sp"][0], out, b, h, w, K, *ws["rt"])
         return out, ws, centres
 
     def region_tree_device(self, imgs):
         """(B,H,W,3) uint8 device tensor -> (labels (B,H,W) int32: the §13 map; merges (B, K-1, 2) int32; costs (B, K-1) int64: the
         unsigned 64-bit costs, all below 2^62; alive (B,) int32) of SPEC.md §14, K = ny * nx: no cut, no post-passes. Any
-        ``n_regions`` of the plan is ignored; ``cut_regions_device`` cuts the tree at any R for the cost of a relabel."""
+        ``n_regions`` of the plan is ignored; ``cut_regions_device`` cuts the tree at any R for the cost of a relabel. With
+        ``tree_nodes = "components"`` (SPEC.md §18) ``labels`` is the node map N and K the batch's largest node count rounded up to
+        a multiple of 64 (one read of B integers from the device): the first rows of the tree at K_cap."""
         if self.n_superpixels == 0:
             raise ValueError("region_tree_device needs Segmenter(n_superpixels=n) with n > 0")
         if not hasattr(self.ops, "region_tree"):
@@ -1109,7 +1207,8 @@ class Segmenter:
         """The contour map of SPEC.md §15 of a tree ``region_tree_device`` returned (or of any label map and merge list of that
         form): a (B,H,W) int32 tensor, 0 inside the regions of the finest cut and, on a boundary pixel, the level in 1 .. alive at
         which that boundary disappears: ``contours > max(0, alive - R)`` is the thick boundary map of the cut at R. It describes
-        the raw cuts: ``connectivity`` and ``min_region_size`` are not reflected. ``out``: a tensor to fill (not ``labels``)."""
+        the raw cuts: ``connectivity`` and ``min_region_size`` are not reflected (with ``tree_nodes = "components"``, SPEC.md §18, the
+        delivered maps are the raw cuts). ``out``: a tensor to fill (not ``labels``)."""
         torch = _torch()
         if not hasattr(self.ops, "region_tree_contours"):
             raise ValueError("contour_map_device needs ops that have the contour map")
@@ -1143,7 +1242,7 @@ class Segmenter:
         last assign used) of SPEC.md §13, without the post-passes (tests / debugging)."""
         if self.n_superpixels == 0:
             raise ValueError("superpixels_device needs Segmenter(n_superpixels=n) with n > 0")
-        out, _, centres = self._superpixel_maps(imgs, tree=False, centres=True)
+        out, _, centres = self._superpixel_maps(imgs, tree=False, centres=True, nodes=False)
         return out, centres
 
     def _opponent(self, imgs, colour):

@@ -321,6 +321,23 @@ size_t gcs_merge_scratch_bytes(int B, int H, int W, int min_size);
 int gcs_merge_small_regions(const int32_t *labels_dev, int B, int H, int W, int min_size, void *scratch_dev,
                             int32_t *out_dev, gcs_stream_t stream);
 
+/* ---- node map of the region tree on connected regions (SPEC.md §18) --------------------------- */
+
+/* labels_dev int32 [B][H][W] -> nodes_out_dev int32 [B][H][W]: per image, with C = the number of connected regions of §7 and
+ * m_guard = ceil(H W / k_cap), the map of gcs_merge_small_regions at m_b = max(min_size, m_guard) if C > k_cap, else at min_size
+ * (m_b <= 1: gcs_connected_regions bit for bit). Every node is 4-connected, an image has at most k_cap of them (§9 leaves no
+ * region below m_b pixels beside another, so at most H W / m_guard <= k_cap), numbered 0,1,2,... in raster order of first pixel.
+ * n_nodes_out_dev int32 [B]: the node count; min_size_used_dev int32 [B] (may be NULL): m_b. The decision is taken per image on
+ * the device: one launch sequence for the batch, in which an image with m_b <= 1 runs no round (its blocks return at once), and
+ * with min_size <= 1 and H W <= k_cap no round is enqueued. Stream-ordered, no allocation, no host synchronisation (capturable).
+ * scratch_dev: gcs_region_nodes_scratch_bytes() bytes (about 20 per pixel; 0 for a bad shape), contents undefined before and after.
+ * GCS_EINVAL, with nothing launched: a NULL labels / scratch / nodes_out / n_nodes_out pointer, a nodes_out_dev range that overlaps
+ * the labels_dev range, B outside 1..65535, H or W outside 1..4096, min_size < 0, k_cap outside 1..4096.
+ * Added within ABI 18: new entry points change no existing call, so GCS_ABI_VERSION did not move. */
+size_t gcs_region_nodes_scratch_bytes(int B, int H, int W);
+int gcs_region_nodes(const int32_t *labels_dev, int B, int H, int W, int min_size, int k_cap, void *scratch_dev,
+                     int32_t *nodes_out_dev, int32_t *n_nodes_out_dev, int32_t *min_size_used_dev, gcs_stream_t stream);
+
 /* ---- smoothing of the feature levels (SPEC.md §10) --------------------------------------------- */
 
 /* In place on a feature slab that gcs_gabor_features has filled (either format: split or wide): every plane of every level
