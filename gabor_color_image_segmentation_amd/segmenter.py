@@ -472,6 +472,72 @@ class HipOps:
                                                      K, workspace.data_ptr(), out.data_ptr(), self._stream()),
                    "gcs_region_tree_contours")
 
+    def _need_table(self, sums, bbox, b, rows):
+        """A table of SPEC.md §19: ``sums`` (B, rows, C) int64 (the bits of the uint64 columns), ``bbox`` (B, rows, 4) int32 -> C."""
+        torch = self.torch
+        if sums is None or sums.dim() != 3 or not 6 <= sums.shape[2] <= 213:
+            raise ValueError("sums must be a contiguous (B, rows, 6 + D) int64 tensor, 0 <= D <= 207")
+        self._need(sums, torch.int64, (b, rows, sums.shape[2]), "sums must be a contiguous (B, rows, 6 + D) int64 tensor")
+        self._need(bbox, torch.int32, (b, rows, 4), "bbox must be a contiguous (B, rows, 4) int32 tensor")
+        return int(sums.shape[2])
+
+    @_on_device
+    def region_props(self, labels, imgs, canon, b, h, w, K, sums, bbox):
+        """The leaf table of SPEC.md §19 of an int32 (B,H,W) label map: ``sums`` (B, K, 6 + D) int64 (the bits of the uint64 columns
+        n, sum y, sum x, sum R, sum G, sum B, D feature sums) and ``bbox`` (B, K, 4) int32 are written whole. ``imgs``: None or the
+        (B,H,W,3) uint8 images; ``canon``: None (D = 0) or a (B,D,H,W) int16 tensor of ``features_unpack``. Two launches, capturable."""
+        torch, K = self.torch, int(K)
+        self._need(labels, torch.int32, (b, h, w), "labels must be a contiguous (B,H,W) int32 tensor")
+        self._need(imgs, torch.uint8, (b, h, w, 3), "imgs must be a contiguous (B,H,W,3) uint8 tensor")
+        d = 0 if canon is None else int(canon.shape[1]) if canon.dim() == 4 else -1
+        self._need(canon, torch.int16, (b, d, h, w), "canon must be a contiguous (B,D,H,W) int16 tensor")
+        if sums is None or bbox is None or self._need_table(sums, bbox, b, K) != 6 + d:
+            raise ValueError("sums must have 6 + D columns")
+        _lib.check(self.lib.gcs_region_props(labels.data_ptr(), None if imgs is None else imgs.data_ptr(),
+                                             None if canon is None else canon.data_ptr(), b, h, w, d, K, sums.data_ptr(),
+                                             bbox.data_ptr(), self._stream()), "gcs_region_props")
+
+    @_on_device
+    def region_props_cuts(self, sums, bbox, merges, alive, regions, b, h, w, K, group, sums_out, bbox_out):
+        """The tables of the cuts of SPEC.md §19 from the leaf table: ``regions`` (n_cuts,) int32 on the device, decreasing;
+        ``group`` (n_cuts, B, K) int32, ``sums_out`` (B, Rsum, C) int64 and ``bbox_out`` (B, Rsum, 4) int32 are written whole
+        (Rsum = the caller's sum of min(K, R)). One launch, capturable."""
+        torch, K = self.torch, int(K)
+        c = self._need_table(sums, bbox, b, K)
+        self._need(merges, torch.int32, (b, K - 1, 2), "merges must be a contiguous (B, K - 1, 2) int32 tensor")
+        self._need(alive, torch.int32, (b,), "alive must be a contiguous (B,) int32 tensor")
+        if regions is None or regions.dim() != 1 or merges is None or alive is None or group is None or sums_out is None:
+            raise ValueError("regions must be an (n_cuts,) int32 tensor; merges, alive, group and sums_out are needed")
+        n = int(regions.shape[0])
+        self._need(regions, torch.int32, (n,), "regions must be a contiguous (n_cuts,) int32 tensor")
+        self._need(group, torch.int32, (n, b, K), "group must be a contiguous (n_cuts, B, K) int32 tensor")
+        if sums_out.dim() != 3 or bbox_out is None or self._need_table(sums_out, bbox_out, b, int(sums_out.shape[1])) != c:
+            raise ValueError("sums_out must be a (B, Rsum, C) int64 tensor with the columns of sums")
+        _lib.check(self.lib.gcs_region_props_cuts(sums.data_ptr(), bbox.data_ptr(), merges.data_ptr() if K > 1 else None,
+                                                  alive.data_ptr(), regions.data_ptr(), b, h, w, K, c, n, int(sums_out.shape[1]),
+                                                  group.data_ptr(), sums_out.data_ptr(), bbox_out.data_ptr(), self._stream()),
+                   "gcs_region_props_cuts")
+
+    @_on_device
+    def region_paint(self, labels, group, sums, b, h, w, K, out):
+        """The mean-colour picture of SPEC.md §19: ``out`` (B,H,W,3) uint8 gets, per pixel of label l, the mean colour of row
+        ``group[b][l]`` (``group`` (B, K) int32) or, with ``group`` None, of row l of ``sums`` (B, G, C) int64: a contiguous table or
+        a run of rows of one (``sums_out[:, o:o + G]``, read in place). One launch, capturable."""
+        torch, K = self.torch, int(K)
+        self._need(labels, torch.int32, (b, h, w), "labels must be a contiguous (B,H,W) int32 tensor")
+        self._need(group, torch.int32, (b, K), "group must be a contiguous (B, K) int32 tensor")
+        if sums is None or sums.dim() != 3 or out is None:
+            raise ValueError("sums must be a (B, G, C) int64 tensor and out a (B,H,W,3) uint8 tensor")
+        g, c = int(sums.shape[1]), int(sums.shape[2])
+        stride = sums.stride(0) // c if b > 1 else g
+        if sums.dtype != torch.int64 or sums.shape[0] != b or (g > 1 and sums.stride(1) != c) or sums.stride(2) != 1 or stride < g \
+                or (b > 1 and sums.stride(0) != stride * c):
+            raise ValueError("sums must be a (B, G, C) int64 tensor, contiguous or a run of rows of a contiguous (B, rows, C) tensor")
+        self._need(out, torch.uint8, (b, h, w, 3), "out must be a contiguous (B,H,W,3) uint8 tensor")
+        _lib.check(self.lib.gcs_region_paint(labels.data_ptr(), None if group is None else group.data_ptr(), sums.data_ptr(), b, h, w,
+                                             K, g, c, stride, out.data_ptr(), self._stream()),
+                   "gcs_region_paint")
+
     def download(self, dst_pinned, src):
         """Device tensor -> pinned host tensor of the same bytes on the current stream, by SDMA (gcs_download)."""
         self._check_dev(src)
@@ -1237,6 +1303,83 @@ class Segmenter:
         labels, merges, _, alive = self.region_tree_device(imgs)
         return self.contour_map_device(labels, merges, alive), alive
 
+    # ---- SPEC.md §19: descriptors and mean-colour pictures of the regions of a map and of the cuts of a tree
+    def _need_props(self):
+        if not hasattr(self.ops, "region_props"):
+            raise ValueError("the region descriptors need ops that have them")
+
+    def region_props_device(self, imgs, labels, K=None, features=False):
+        """(B,H,W,3) uint8 and (B,H,W) int32 device tensors -> the leaf table of SPEC.md §19: ``(sums (B, K, 6 + D) int64, bbox
+        (B, K, 4) int32)``: per label the bits of the uint64 columns n, sum y, sum x, sum R, sum G, sum B (and, with
+        ``features=True``, the sums of the plan's D canonical features, made from ``imgs`` as ``features_device`` makes them; D = 0
+        otherwise) and the inclusive box (y0, x0, y1, x1), (H, W, -1, -1) for a label that owns no pixel. ``K=None``: one read of
+        ``labels.max()`` from the device. Any label map will do: a k-means map, its connected regions, a tree's leaves, a cut."""
+        torch = _torch()
+        self._need_props()
+        if labels.dim() != 3 or labels.dtype != torch.int32 or imgs.dim() != 4 or tuple(imgs.shape) != tuple(labels.shape) + (3,):
+            raise ValueError("labels must be a (B,H,W) int32 tensor and imgs the (B,H,W,3) uint8 tensor of the same images")
+        imgs, labels = imgs.contiguous(), labels.contiguous()
+        b, h, w = labels.shape
+        with self._device():
+            K = max(1, int(labels.max()) + 1) if K is None else int(K)
+            canon = self.features_device(imgs) if features else None
+            d = self.bank.n_features if features else 0
+            if K < 1 or b * K * (6 + d) >= 2 ** 31:
+                raise ValueError("K must be at least 1 and B * K * (6 + D) below 2^31")
+            sums = torch.empty((b, K, 6 + d), dtype=torch.int64, device=labels.device)
+            bbox = torch.empty((b, K, 4), dtype=torch.int32, device=labels.device)
+            self.ops.region_props(labels, imgs, canon, b, h, w, K, sums, bbox)
+        return sums, bbox
+
+    def cut_props_device(self, sums, bbox, merges, alive, regions, shape=None):
+        """The tables of every requested cut from the leaf table, without reading a pixel (SPEC.md §19). sums, bbox: what
+        ``region_props_device`` returned for the map and the K of ``region_tree_device``; merges, alive: that tree; regions: 1 .. 64
+        distinct integers in 1 .. 4096, in any order. Returns ``(group (n, B, K) int32, sums_out (B, Rsum, C) int64, bbox_out
+        (B, Rsum, 4) int32, offsets)``, device tensors and a list of n integers, in the caller's order of ``regions``: ``group[j][b][q]``
+        is the label ``cut_regions_device(..., regions[j])`` gives the leaf q (-1: q owns no pixel), and the rows ``offsets[j] ..
+        offsets[j] + min(K, regions[j]) - 1`` of sums_out / bbox_out are that cut's table (rows behind its groups: zeros, the empty
+        box). ``shape``: (H, W) of the images, for the empty box; default: the leaf table's own empty box, or (0, 0)."""
+        torch = _torch()
+        from .evaluate_gpu import _need_cuts
+        self._need_props()
+        regs, order = _need_cuts(regions)
+        if sums.dim() != 3 or merges.dim() != 3 or merges.shape[1] + 1 != sums.shape[1]:
+            raise ValueError("sums must be the (B, K, C) leaf table of the tree's label map: K = merges.shape[1] + 1")
+        b, K, _ = sums.shape
+        srt = [regs[j] for j in order]
+        starts = np.concatenate([[0], np.cumsum([min(K, r) for r in srt])])
+        with self._device():
+            if shape is None:
+                empty = bbox[:, :, 2] < 0
+                shape = (int(bbox[:, :, 0][empty].max()), int(bbox[:, :, 1][empty].max())) if bool(empty.any()) else \
+                    (int(bbox[:, :, 2].max()) + 1, int(bbox[:, :, 3].max()) + 1)
+            h, w = (max(1, int(v)) for v in shape)
+            regs_d = torch.tensor(srt, dtype=torch.int32).to(sums.device)
+            group = torch.empty((len(srt), b, K), dtype=torch.int32, device=sums.device)
+            sums_out = torch.empty((b, int(starts[-1]), sums.shape[2]), dtype=torch.int64, device=sums.device)
+            bbox_out = torch.empty((b, int(starts[-1]), 4), dtype=torch.int32, device=sums.device)
+            self.ops.region_props_cuts(sums.contiguous(), bbox.contiguous(), merges.contiguous(), alive.contiguous(), regs_d, b, h, w,
+                                       K, group, sums_out, bbox_out)
+            inverse = np.empty(len(order), np.int64)
+            inverse[order] = np.arange(len(order))                 # the caller's j-th R is the inverse[j]-th cut of the call
+            group = group[torch.from_numpy(inverse).to(sums.device)]
+        return group, sums_out, bbox_out, [int(starts[i]) for i in inverse]
+
+    def paint_device(self, labels, sums, group=None):
+        """The mean-colour picture of SPEC.md §19: (B,H,W) int32 labels -> a fresh (B,H,W,3) uint8 device tensor. ``sums``: a table
+        whose rows the labels name (``group`` None: the leaf table of this map) or the rows of one cut (``sums_out[:, o : o + rows]``,
+        read in place) with ``group`` (B, K) int32, that cut's slice of ``cut_props_device``. Black where a label is out of range or its row is empty."""
+        torch = _torch()
+        self._need_props()
+        if labels.dim() != 3 or labels.dtype != torch.int32 or sums.dim() != 3:
+            raise ValueError("labels must be a (B,H,W) int32 tensor and sums a (B, G, C) int64 tensor")
+        b, h, w = labels.shape
+        K = int(sums.shape[1]) if group is None else int(group.shape[-1])
+        out = torch.empty((b, h, w, 3), dtype=torch.uint8, device=labels.device)
+        with self._device():
+            self.ops.region_paint(labels.contiguous(), None if group is None else group.contiguous(), sums, b, h, w, K, out)
+        return out
+
     def superpixels_device(self, imgs):
         """(B,H,W,3) uint8 device tensor -> (labels (B,H,W) int32, centres (B, ny * nx, D + 2) int32: the D features, cy, cx the
         last assign used) of SPEC.md §13, without the post-passes (tests / debugging)."""
@@ -1815,3 +1958,40 @@ def segment_batch(imgs, mode="per_image", **kw) -> np.ndarray:
     """(B,H,W,3) uint8 -> (B,H,W) int32; equals stack([segment(i) for i in imgs]) in per_image mode."""
     out_dtype = kw.pop("out_dtype", np.int32)
     return _plan(kw).segment_batch(imgs, mode, out_dtype=out_dtype)
+
+
+def _one_image(img):
+    img = np.ascontiguousarray(img)
+    if img.ndim != 3 or img.shape[2] != 3 or img.dtype != np.uint8:
+        raise ValueError("img must be an (H,W,3) uint8 array")
+    return img
+
+
+def segment_regions(img, **kw):
+    """(H,W,3) uint8 -> ``(labels (H,W) int32, table)``: ``segment(img, **kw)`` and the descriptors of its regions (SPEC.md §19,
+    ``regions.region_table``: area, centroid, bbox, mean_rgb, mean_features, used; one entry per label 0 .. labels.max()). The table
+    is made from the delivered map, behind every post-pass of the plan, so it describes what the caller gets."""
+    from .regions import region_table
+    torch = _torch()
+    img = _one_image(img)
+    seg = _plan(kw)
+    labels = seg(img)
+    dev = seg.ops.device
+    sums, bbox = seg.region_props_device(torch.from_numpy(img[None]).to(dev),
+                                         torch.from_numpy(np.ascontiguousarray(labels[None], np.int32)).to(dev))
+    return labels, region_table(sums[0].cpu().numpy(), bbox[0].cpu().numpy())
+
+
+def render_regions(img, labels) -> np.ndarray:
+    """(H,W,3) uint8 image and an (H,W) label map of it -> (H,W,3) uint8: every region in its mean colour (SPEC.md §19), black
+    where a label is negative. Runs on the plan the module-level calls hold (the default plan if there is none yet)."""
+    torch = _torch()
+    img = _one_image(img)
+    labels = np.ascontiguousarray(labels, np.int32)
+    if labels.shape != img.shape[:2]:
+        raise ValueError("labels must be the (H,W) map of img")
+    seg = next(iter(_default.values())) if _default else _plan({})
+    dev = seg.ops.device
+    lab = torch.from_numpy(labels[None]).to(dev)
+    sums, _ = seg.region_props_device(torch.from_numpy(img[None]).to(dev), lab)
+    return seg.paint_device(lab, sums)[0].cpu().numpy()

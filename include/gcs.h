@@ -536,6 +536,49 @@ int gcs_cut_shapes(const int32_t *labels_dev, const int32_t *contours_dev, const
                    const int32_t *regions_dev, int B, int H, int W, int K, int n_cuts, void *workspace_dev, uint32_t *area_out_dev,
                    uint32_t *perim_out_dev, uint32_t *boundary_out_dev, gcs_stream_t stream);
 
+/* ---- region descriptors and mean-colour maps of label maps and tree cuts (SPEC.md §19) --------------- */
+
+/* A table row describes one region: C = 6 + D uint64 columns { n, sum y, sum x, sum R, sum G, sum B, sum x_0 .. sum x_{D-1} } and a box
+ * int32 (y0, x0, y1, x1), inclusive, (H, W, -1, -1) for a row that owns no pixel. Sums add and boxes take min / max, so the rows of
+ * every group of every cut follow from the rows of the leaves; exact integers, the same bits in any execution order.
+ *   gcs_region_props        two launches on `stream` (fill; one pass over the pixels). labels_dev int32 [B][H][W]; img_dev uint8
+ *                           [B][H][W][3] or NULL (the colour columns are then 0); feats_canonical_dev uint16 [B][D][H][W], NULL exactly
+ *                           when D = 0. sums_out_dev uint64 [B][K][C], bbox_out_dev int32 [B][K][4]: written whole, they may hold
+ *                           anything on entry. A pixel whose label is outside 0 .. K-1 is counted nowhere. K is bounded only by
+ *                           B * K * C < 2^31 (the map of gcs_connected_regions has more than 4096 labels).
+ *   gcs_region_props_cuts   one launch, a workgroup per image. sums_dev / bbox_dev: the leaf table of gcs_region_props at the K of the
+ *                           tree; merges_dev / alive_dev as gcs_region_tree wrote them, or any list gcs_region_tree_contours accepts
+ *                           (a row that is not (a < b, both reps at that step) is skipped); regions_dev int32 [n_cuts], decreasing,
+ *                           read on the device: an entry that is not below its predecessor repeats its predecessor's cut.
+ *                             group_out_dev int32 [n_cuts][B][K]  [c][b][q] = the label gcs_region_tree_cut at R_c gives the leaf label
+ *                                                                 q (groups numbered by increasing rep), -1 for a leaf with n = 0
+ *                             sums_out_dev  uint64 [B][Rsum][C], bbox_out_dev int32 [B][Rsum][4]: cut c owns the min(K, R_c) rows from
+ *                                                                 row sum_{c' < c} min(K, R_c') on; row g = the sum and the box of the
+ *                                                                 leaves with group g; the rows behind the cut's groups hold zeros
+ *                                                                 and the empty box. Rsum = sum_c min(K, R_c) is the caller's: no
+ *                                                                 row at or past Rsum is written, whatever regions_dev holds, and a
+ *                                                                 group whose number is not below min(K, R_c) (a list that leaves
+ *                                                                 more than R_c groups: no tree of `alive` leaves) has no row.
+ *                           Every output element is written. With K = 1 merges_dev is not read and may be NULL.
+ *   gcs_region_paint        one launch. rgb_out_dev uint8 [B][H][W][3]: the pixel of label l gets the mean colour of row g =
+ *                           group_dev[b][l] (group_dev int32 [B][K], one cut's slice of group_out_dev) or, with group_dev NULL, of row
+ *                           g = l (G must be K) of image b's G rows, which start at row b * row_stride of sums_dev (uint64 [..][C];
+ *                           row_stride = G for a table [B][G][C]; one cut's rows inside sums_out_dev: sums_dev = the cut's first
+ *                           row, row_stride = Rsum, no copy): floor((2 S + n) / (2 n)) per channel, at most 255. (0, 0, 0) where l
+ *                           is outside 0 .. K-1, g outside 0 .. G-1 or n = 0.
+ * No allocation, no host synchronisation (capturable). GCS_EINVAL, with nothing launched: a NULL pointer (img_dev and group_dev may
+ * be NULL; feats_canonical_dev with D = 0 and merges_dev with K = 1 must / may be), B outside 1..65535, H or W outside 1..4096, D
+ * outside 0..207 (C outside 6..213), K < 1, K > 4096 in gcs_region_props_cuts, n_cuts outside 1..64, Rsum outside 1 .. n_cuts * K,
+ * G < 1, G != K without group_dev, row_stride < G, B * K * C, B * Rsum * C, n_cuts * B * K, B * row_stride * C or B * K not below 2^31.
+ * Added within ABI 18: new entry points change no existing call, so GCS_ABI_VERSION did not move. */
+int gcs_region_props(const int32_t *labels_dev, const uint8_t *img_dev, const uint16_t *feats_canonical_dev, int B, int H, int W, int D,
+                     int K, uint64_t *sums_out_dev, int32_t *bbox_out_dev, gcs_stream_t stream);
+int gcs_region_props_cuts(const uint64_t *sums_dev, const int32_t *bbox_dev, const int32_t *merges_dev, const int32_t *alive_dev,
+                          const int32_t *regions_dev, int B, int H, int W, int K, int C, int n_cuts, int Rsum, int32_t *group_out_dev,
+                          uint64_t *sums_out_dev, int32_t *bbox_out_dev, gcs_stream_t stream);
+int gcs_region_paint(const int32_t *labels_dev, const int32_t *group_dev, const uint64_t *sums_dev, int B, int H, int W, int K, int G,
+                     int C, int row_stride, uint8_t *rgb_out_dev, gcs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
