@@ -315,6 +315,16 @@ extern "C" const char *gcs_selftest_pass_kernel(int H, int W, int n_scales, int 
     return gcs_pass_name(pk);
 }
 
+// Test hook (host only): the `nt` limit the launch of one pass over this batch would use (csrc/lloyd_pass.h: gcs_pass_nt_limit) -
+// list positions below it are loaded with the nontemporal hint -, 0 for a kernel that loads plain, -1 where lloyd_pass refuses the call.
+extern "C" int gcs_selftest_pass_nt_limit(int B, int H, int W, int n_scales, int n_orient, int k, int n_sets) {
+    GcsLayout lo;
+    if (B <= 0 || B > 65535 || !gcs_make_layout(H, W, n_scales, n_orient, &lo) || !kp_batch_fits(lo, B) || k < 1 || k > GCS_K_MAX ||
+        (n_sets != 1 && n_sets != B) || !gcs_selftest_pass_kernel(H, W, n_scales, n_orient, k))
+        return -1;
+    return gcs_pass_nt_limit(gcs_pass_kernel(lo, k), lo, B, n_sets);
+}
+
 // ------------------------------------------------------------------- self-updating passes (single rank, whole images)
 // The Lloyd loop as n_iter launches: no init kernel, no reduce launches (GcsFold in csrc/common.h, FUSED in kmeans_pass_mfma_kernel).
 // Which banks: gcs_pass_self_updating (csrc/lloyd_pass.h). Everything else keeps the init / pass / reduce launches.

@@ -959,25 +959,25 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 8 ? 2
 }
 
 template <int KT, int NST, int DSTEPS, int WAVES, bool SPLIT, int L0T, bool FUSED>
-static void launch_mfma_as(const LloydPassArgs &a, const GcsFold &fz) {
-    // which tile loads carry the nontemporal hint (see kp_nt_limit; a pass streams 3/4 of a tile's bytes): the wide-slab kernels load plain
-    const int nt_flag = SPLIT ? kp_nt_limit(a.lo, a.B, a.n_sets, a.lo.tile_bytes / 4 * 3) : 0;
+static void launch_mfma_as(const LloydPassArgs &a, const GcsFold &fz, int nt_flag) {
     hipLaunchKernelGGL((kmeans_pass_mfma_kernel<KT, NST, DSTEPS, WAVES, SPLIT, L0T, FUSED>), dim3(a.parts, a.B), dim3(64 * WAVES), 0,
                        a.stream, a.feats, a.cent, a.lo, a.k, a.n_sets == a.B ? 1 : 0, a.parts, a.reverse ? 1 : 0, a.row_lo, a.row_hi,
                        a.partials, a.lab_out, a.lab_u8, nt_flag, fz);
 }
 template <bool SELF, int KT, int NST, int DSTEPS, int WAVES, bool SPLIT, int L0T>
-static void launch_mfma(const LloydPassArgs &a, const GcsFold *fz) {
+static void launch_mfma(const LloydPassArgs &a, const GcsFold *fz, int nt_flag) {
     if constexpr (SELF)
-        if (fz) return launch_mfma_as<KT, NST, DSTEPS, WAVES, SPLIT, L0T, true>(a, *fz);
-    launch_mfma_as<KT, NST, DSTEPS, WAVES, SPLIT, L0T, false>(a, GcsFold{});
+        if (fz) return launch_mfma_as<KT, NST, DSTEPS, WAVES, SPLIT, L0T, true>(a, *fz, nt_flag);
+    launch_mfma_as<KT, NST, DSTEPS, WAVES, SPLIT, L0T, false>(a, GcsFold{}, nt_flag);
 }
 
 void lloyd_mfma_launch(GcsPassKernel pk, const LloydPassArgs &a, const GcsFold *fz) {
+    // which tile loads carry the nontemporal hint (csrc/lloyd_pass.h: gcs_pass_nt_limit; 0 for the wide-slab kernels, which load plain)
+    const int nt_flag = gcs_pass_nt_limit(pk, a.lo, a.B, a.n_sets);
     switch (pk) {
 #define GCS_PASS_LAUNCH(id, name, ...)                                                      \
     case GCS_PASS_##id:                                                                     \
-        return launch_mfma<gcs_pass_self_updating(GCS_PASS_##id), __VA_ARGS__>(a, fz);
+        return launch_mfma<gcs_pass_self_updating(GCS_PASS_##id), __VA_ARGS__>(a, fz, nt_flag);
         GCS_MFMA_PASSES(GCS_PASS_LAUNCH)
 #undef GCS_PASS_LAUNCH
     default: return;

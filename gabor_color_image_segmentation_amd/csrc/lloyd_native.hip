@@ -585,20 +585,20 @@ GcsPassKernel lloyd_native_kernel(const GcsLayout &lo) {
 }
 
 template <int NL, int MINB, int N0>
-static void launch_native(const LloydPassArgs &a) {
+static void launch_native(const LloydPassArgs &a, int nt_limit) {
     // MINB 4-wave workgroups per CU are resident: that many work, the others write zero partial rows
     const int parts_eff = native_parts_eff(a.B, a.parts, (long long)a.lo.ntiles * KP_TP, MINB);
-    const int nt_limit = kp_nt_limit(a.lo, a.B, a.n_sets, a.lo.tile_bytes);   // which tile loads carry the nontemporal hint
     hipLaunchKernelGGL((kmeans_pass_native_kernel<NL, MINB, N0>), dim3(a.B, a.parts), dim3(256), 0, a.stream, a.feats, a.cent, a.lo,
                        a.k, a.n_sets == a.B ? 1 : 0, a.parts, parts_eff, a.reverse ? 1 : 0, a.row_lo, a.row_hi, a.partials, a.lab_out,
                        a.lab_u8, nt_limit);
 }
 
 void lloyd_native_launch(GcsPassKernel pk, const LloydPassArgs &a) {
+    const int nt_limit = gcs_pass_nt_limit(pk, a.lo, a.B, a.n_sets);   // which tile loads carry the nontemporal hint (csrc/lloyd_pass.h)
     switch (pk) {
 #define GCS_PASS_LAUNCH(id, name, ...) \
     case GCS_PASS_##id:                \
-        return launch_native<__VA_ARGS__>(a);
+        return launch_native<__VA_ARGS__>(a, nt_limit);
         GCS_NATIVE_PASSES(GCS_PASS_LAUNCH)
 #undef GCS_PASS_LAUNCH
     default: return;

@@ -176,6 +176,21 @@ static inline GcsPassKernel gcs_pass_kernel(const GcsLayout &lo, int k) {
     return nst <= 10 ? GCS_PASS_WIDE_2_10 : nst <= 18 ? GCS_PASS_WIDE_2_18 : GCS_PASS_WIDE_2_26;
 }
 
+// The `nt` limit of one launch of `pk` (kp_nt_limit): the one place that decides it, for both launchers and the test hook
+// gcs_selftest_pass_nt_limit. What a tile streams per pass: the split slab 12 of its 16 bits per value (LO and MID runs; the TOP
+// run only where flagged), the deep-bank pass the whole tile. The wide-slab kernels and the generic pass load plain: 0.
+static inline int gcs_pass_nt_limit(GcsPassKernel pk, const GcsLayout &lo, int B, int n_sets) {
+    if (gcs_pass_is_native(pk)) return kp_nt_limit(lo, B, n_sets, lo.tile_bytes);
+    switch (pk) {
+#define GCS_PASS_CASE(id, name, KT, NST, DSTEPS, WAVES, SPLIT, L0T) \
+    case GCS_PASS_##id:                                             \
+        return SPLIT ? kp_nt_limit(lo, B, n_sets, lo.tile_bytes / 4 * 3) : 0;
+        GCS_MFMA_PASSES(GCS_PASS_CASE)
+#undef GCS_PASS_CASE
+    default: return 0;
+    }
+}
+
 // What one launch of a matrix-core or deep-bank pass can address (lloyd_pass and gcs_kmeans_pass_fused refuse the rest)
 static inline bool kp_batch_fits(const GcsLayout &lo, int B) {         // 4 * (tile index in the batch list) is kept in an int
     return (long long)B * lo.ntiles <= 0x1fffffffLL;
@@ -197,5 +212,6 @@ struct LloydPassArgs {
     hipStream_t stream;
 };
 // Enqueue `pk` (one of the family's ids); the caller checks the launch. fz != NULL: the self-updating form (gcs_pass_self_updating).
+// Both launchers take the `nt` limit from gcs_pass_nt_limit(pk, a.lo, a.B, a.n_sets).
 void lloyd_mfma_launch(GcsPassKernel pk, const LloydPassArgs &a, const GcsFold *fz) __attribute__((visibility("hidden")));
 void lloyd_native_launch(GcsPassKernel pk, const LloydPassArgs &a) __attribute__((visibility("hidden")));

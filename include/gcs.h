@@ -122,7 +122,9 @@ int gcs_features_gather(const uint16_t *feats_dev, int B, int H, int W, int n_sc
  * Only rows [row_lo, row_hi) of each image vote in the sums (whole image: 0, H); halo rows of
  * a row-sharded image are labelled but do not vote. `reverse` != 0 sweeps the slab back to front:
  * alternate it from pass to pass so that each pass starts on what the previous one left in the
- * Infinity Cache (results do not depend on it). labels_dev: uint8 [B][H][W] label map (every pixel of every image is
+ * Infinity Cache (results do not depend on it). Long sweeps load the part of the slab that no later pass finds in that cache
+ * with the nontemporal hint (gcs_selftest_pass_nt_limit): the hint only affects performance, results are identical bit for bit
+ * with either load form. labels_dev: uint8 [B][H][W] label map (every pixel of every image is
  * labelled, rows outside the voting window included); partials_dev:
  * gcs_kmeans_partial_bytes() bytes, fully overwritten (no zeroing needed). D <= 207 (every BASELINE bank) runs on
  * the matrix cores, wider feature vectors on a generic VALU pass; k <= GCS_K_MAX. The same n_sets must be passed
@@ -196,6 +198,12 @@ int gcs_selftest_native_parts(int B, int H, int W);
  * static string) -, or NULL for a shape, bank or k they refuse. gcs_kmeans_fused_workspace_bytes != 0 exactly for split<1,3> and
  * split<1,3,2>. Launches nothing and touches no device. */
 const char *gcs_selftest_pass_kernel(int H, int W, int n_scales, int n_orient, int k);
+/* Test hook (host only, added within ABI 18: a new entry point changes no existing call, so GCS_ABI_VERSION did not move): the
+ * `nt` limit one Lloyd pass over this batch would be launched with. The split-slab and the deep-bank kernels load the positions
+ * below it of every sweep list (the whole batch, or one image when n_sets == B) with the nontemporal hint and the last 256 MiB of
+ * the list plain; 0 for a kernel that loads every tile plain (wide slab, generic) and for a list of 256 MiB or less; -1 for a call
+ * gcs_kmeans_assign_accumulate refuses (shape, bank, B, k, n_sets). Launches nothing and touches no device. */
+int gcs_selftest_pass_nt_limit(int B, int H, int W, int n_scales, int n_orient, int k, int n_sets);
 
 /* ---- boundary scoring of one image -------------------------------------- */
 

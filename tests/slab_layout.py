@@ -30,5 +30,24 @@ def flag_bytes(seg, feats, b, h, w):
     levels = [(3 * min(2, ns - 2 * L) * no, 256 >> (2 * L)) for L in range((ns + 1) // 2)]
     s = sum(d * n for d, n in levels)
     ntiles = img_bytes // (2 * s)
-    raw = feats.cpu().numpy().view(np.uint8)[:b * img_bytes].reshape(b, img_bytes)
-    return raw[:, 2 * s * ntiles:2 * s * ntiles + 4 * ntiles].reshape(b, ntiles, 4), ntiles
+    raw = feats[:b * img_bytes].reshape(b, img_bytes)[:, 2 * s * ntiles:2 * s * ntiles + 4 * ntiles]     # (only the words travel)
+    return raw.cpu().numpy().view(np.uint8).reshape(b, ntiles, 4), ntiles
+
+
+def tile_geometry(lib, h, w, ns, no):
+    """(ntiles, tile_bytes, split) of one image's slab from the bank's shape and the byte-count entry points: a tile holds, per
+    pyramid level L, 3 * min(2, ns - 2 L) * no planes of 256 >> 2 L values of 16 bits, every level rounded up to 16 bytes
+    (csrc/common.h). The split slab (a pass streams 3/4 of it: gcs_feature_pass_bytes) carries 4 flag bytes per tile behind the
+    value runs, rounded up to 256 bytes per image; the wide slab is tiles and nothing else."""
+    tile_bytes = sum(-(-3 * min(2, ns - 2 * L) * no * (256 >> (2 * L)) * 2 // 16) * 16 for L in range((ns + 1) // 2))
+    img_bytes = lib.gcs_feature_slab_bytes(1, h, w, ns, no)
+    pass_bytes = lib.gcs_feature_pass_bytes(1, h, w, ns, no)
+    assert img_bytes > 0 and pass_bytes > 0, (h, w, ns, no)
+    split = pass_bytes != img_bytes
+    if split:
+        ntiles = pass_bytes // (tile_bytes // 4 * 3)
+        assert pass_bytes == ntiles * (tile_bytes // 4 * 3) and img_bytes == ntiles * tile_bytes + -(-4 * ntiles // 256) * 256
+    else:
+        ntiles = img_bytes // tile_bytes
+        assert img_bytes == ntiles * tile_bytes
+    return ntiles, tile_bytes, split

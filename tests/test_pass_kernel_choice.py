@@ -2,7 +2,10 @@
 gcs_selftest_pass_kernel), and what the pass entry points answer to calls they refuse - both against
 tests/golden/pass_kernel_table.json, recorded at the commit before the choice had a function of its own
 (tests/golden/make_pass_kernel_table.py: a launch recorded the stringified kernel instead of launching). No GPU: nothing here
-launches, and no pointer is dereferenced."""
+launches, and no pointer is dereferenced.
+
+The `nt` limit of a launch (csrc/lloyd_pass.h: gcs_pass_nt_limit, through the hook gcs_selftest_pass_nt_limit) against kp_nt_limit
+restated here, and the preconditions of the cases of tests/test_gpu_nt_arm.py."""
 import ctypes as C
 import json
 import os
@@ -115,3 +118,91 @@ def test_bad_arguments_keep_their_code_and_message(lib, table):
                          ("gcs_kmeans_assign_raster", 0), ("gcs_kmeans_assign_raster", 1), ("gcs_kmeans_assign_raster", 10),
                          ("gcs_kmeans_pass_fused", 0), ("gcs_kmeans_pass_fused", 11), ("gcs_kmeans_pass_fused", 12),
                          ("gcs_kmeans_pass_fused", 13)}
+
+
+# ------------------------------------------------------------------------------------------ the `nt` limit of a launch
+KEEP_BYTES = 256 << 20             # csrc/lloyd_pass.h: the end of every sweep list that is loaded plain (the Infinity Cache's size)
+NT_B = [1, 3, 16, 28, 64, 400]
+NT_SHAPES = [(41, 74), (321, 481), (2048, 2048)]
+
+
+def _nt_limit(name, ntiles, tile_bytes, b, n_sets):
+    """kp_nt_limit: list positions below the result are loaded `nt`. A sweep list is the whole batch, or one image with per-image
+    codebooks (then the budget is shared by the B lists); a split-slab pass streams 3/4 of a tile, the deep-bank pass all of it, and
+    every other kernel loads plain."""
+    if name.startswith("split<"):
+        stream = tile_bytes // 4 * 3
+    elif name.startswith("native<"):
+        stream = tile_bytes
+    else:
+        return 0
+    lists, nlist = (b, ntiles) if n_sets == b else (1, ntiles * b)
+    return max(nlist - KEEP_BYTES // stream // lists, 0)
+
+
+def test_nt_limit_equals_the_restated_one(lib):
+    """Every bank of PASS_CASES and the default 4x6 and 8x8 banks, n_sets 1 and B, B and shapes as listed; both arms and every
+    family occur."""
+    from slab_layout import tile_geometry
+    from test_gpu_value_range import PASS_CASES
+    banks = sorted({(ns, no, k) for (ns, no, _ks, _shift, k), _ in PASS_CASES} | {(4, 6, 8), (8, 8, 8)})
+    seen = {}
+    for ns, no, k in banks:
+        for h, w in NT_SHAPES:
+            name = _name(lib, h, w, ns, no, k)
+            ntiles, tile_bytes, split = tile_geometry(lib, h, w, ns, no)
+            assert split == name.startswith("split<"), (name, split)
+            for b in NT_B:
+                for n_sets in {1, b}:
+                    want = _nt_limit(name, ntiles, tile_bytes, b, n_sets)
+                    got = lib.gcs_selftest_pass_nt_limit(b, h, w, ns, no, k, n_sets)
+                    assert got == want, (name, (ns, no, k), (b, h, w), n_sets, got, want)
+                    fam = seen.setdefault(name.split("<")[0], set())
+                    fam.add("nt" if want else "plain")
+                    if n_sets == b and b > 1 and want:
+                        fam.add("nt per image")
+    assert seen["split"] == seen["native"] == {"nt", "plain", "nt per image"}, seen
+    assert set(seen) == {"split", "native", "narrow", "wide", "wide8w", "generic"}, set(seen)
+    assert lib.gcs_selftest_pass_nt_limit(64, 321, 481, 4, 6, 8, 1) == 64 * 607 - KEEP_BYTES // 17280       # the timed shape: 23 314 of 38 848
+
+
+def test_nt_limit_is_zero_for_plain_kernels_and_minus_one_where_refused(lib, recorded):
+    """Over the whole recorded domain: -1 exactly where the table says "refused", 0 for every narrow, wide and generic kernel whatever
+    the size, never negative otherwise; and -1 for the calls lloyd_pass refuses for B, n_sets or the batch size."""
+    for (ns, no, k), name in recorded.items():
+        got = {lib.gcs_selftest_pass_nt_limit(b, h, w, ns, no, k, n) for h, w in ((321, 481), (2048, 2048)) for b in (1, 64, 400)
+               for n in {1, b}}
+        if name is None:
+            assert got == {-1}, (ns, no, k, got)
+        elif name.split("<")[0] in ("split", "native"):
+            assert min(got) >= 0 and max(got) > 0, (ns, no, k, name, got)
+        else:
+            assert got == {0}, (ns, no, k, name, got)
+    for args in [(0, 321, 481, 4, 6, 8, 1), (65536, 8, 8, 4, 6, 8, 1), (3, 321, 481, 4, 6, 8, 2), (3, 321, 481, 4, 6, 8, 0),
+                 (3, 321, 481, 4, 6, 0, 1), (3, 321, 481, 4, 6, 17, 1), (3, 0, 481, 4, 6, 8, 1), (3, 321, 481, 9, 6, 8, 1),
+                 (40000, 2048, 2048, 4, 6, 8, 1), (1, 30000, 30000, 4, 6, 8, 1)]:
+        assert lib.gcs_selftest_pass_nt_limit(*args) == -1, args
+    assert lib.gcs_selftest_pass_nt_limit(3, 321, 481, 4, 6, 8, 3) == 0 and lib.gcs_selftest_pass_nt_limit(1, 8, 8, 1, 1, 1, 1) == 0
+
+
+def test_nt_arm_cases_satisfy_their_preconditions(lib):
+    """tests/test_gpu_nt_arm.py: the twelve kernels that have an `nt` arm, each id names the kernel its bank takes, the G written
+    beside a case is what the launcher computes, 0 < nt_limit < nlist with at least G + 1 positions on either side, nt_limit no
+    multiple of G, nt_limit > 0 per image list where a case runs per-image codebooks, a self-updating pass where it runs one - and
+    no batch is larger than it has to be: one image fewer breaks a condition."""
+    import test_gpu_nt_arm as nt
+    kernels = set()
+    for case in nt.NT_CASES:
+        case_id, bank, (b, h, w), g, what = case
+        limit, nlist, _ = nt.preconditions(lib, case)
+        assert limit == _nt_limit(nt.kernel_of(lib, case), *__import__("slab_layout").tile_geometry(lib, h, w, *bank[:2])[:2], b, 1)
+        kernels.add(nt.kernel_of(lib, case) + ("_self_updating" if what == "fused" else ""))
+        smaller = (case_id, bank, (b - 1, h, w), None, "pass")
+        g1 = nt.launch_workgroups(lib, smaller)
+        l1 = lib.gcs_selftest_pass_nt_limit(b - 1, h, w, bank[0], bank[1], bank[4], 1)
+        n1 = nlist // b * (b - 1)
+        assert not (l1 >= g1 + 1 and n1 - l1 >= g1 + 1 and l1 % g1), (case_id, "B - 1 would do")
+        assert 2.3e6 <= b * h * w <= 6.2e6, (case_id, b * h * w)
+    assert kernels == {"split<1,3,2>", "split<1,3>", "split<1,5>", "split<2,5>", "split<1,3,2>_self_updating", "split<1,3>_self_updating",
+                       "native<2,3,0>", "native<2,3,6>", "native<3,3,0>", "native<3,3,6>", "native<4,3,6>", "native<4,2,0>"}, kernels
+    assert sum(c[4] == "per_image" for c in nt.NT_CASES) == 2
