@@ -47,6 +47,7 @@ SIGNATURES = {
     "gcs_selftest_native_parts": (_i, [_i, _i, _i]),
     "gcs_selftest_pass_kernel": (C.c_char_p, [_i, _i, _i, _i, _i]),
     "gcs_selftest_pass_nt_limit": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "gcs_selftest_gabor_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_char_p, _sz]),
     "gcs_device_cu_count": (_i, []),
     "gcs_boundary_scratch_bytes": (_sz, [_i, _i, _i]),
     "gcs_boundary_counts": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

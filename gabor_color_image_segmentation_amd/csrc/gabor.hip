@@ -16,10 +16,12 @@
 // Nothing here allocates or frees device memory or blocks the host; every entry point is ordered on the caller's stream
 // (gcs_gabor_features forks level 1 of a large two-level batch onto a side stream and joins it back, see there).
 #include "common.h"
+#include "gabor_plan.h"
 #include <mutex>
 
 constexpr int G_TW = 64;            // output tile width  (8 lanes-in-x * 8 shifts)
 constexpr int G_TH = 32;            // output tile height (4 waves * 8 rows)
+static_assert(G_TW == GP_TW && G_TH == GP_TH, "csrc/gabor_plan.h counts tiles of this size");
 constexpr int G_HALO = 7;
 constexpr int G_LROWS = G_TH + 15;  // 47 rows: halo 14 + the zero-tap row 15
 constexpr int G_LPITCH = 96;        // bytes per LDS tile row (>= 64 + 16 + 12)
@@ -301,10 +303,6 @@ __global__ __launch_bounds__(256) void gabor_pre01_kernel(const uint8_t *__restr
 #ifndef GCS_GABOR_WAVES
 #define GCS_GABOR_WAVES 2
 #endif
-#ifndef GCS_GABOR_MTMAX_
-#define GCS_GABOR_MTMAX_ 3
-#endif
-constexpr int GCS_GABOR_MTMAX = GCS_GABOR_MTMAX_;   // row tiles (of four filters) per launch; two for the 15-row frame
 
 // One pyramid level of a launch. Consecutive levels with the same filter count share ONE launch (tiles of level L, then
 // L+1, ... in one list): a level boundary then costs one reload of the A operand per workgroup instead of a kernel
@@ -909,8 +907,6 @@ __global__ __launch_bounds__(256) void gabor_strip_kernel(StripArgs A, GcsLayout
 }
 
 // ------------------------------------------------------------------------------ workspace
-static inline int gabor_hp(int H) { return (H + G_TH - 1) / G_TH * G_TH + 15; }
-static inline int gabor_wp(int W) { return (W + G_TW - 1) / G_TW * G_TW + 32; }
 
 struct GaborWs {
     size_t plane_off[GCS_LEVELS_MAX];   // padded planes [B][3][Hp][Wp] int8 of level L
@@ -921,8 +917,8 @@ struct GaborWs {
 static GaborWs gabor_ws(int B, int H, int W, int n_levels) {
     GaborWs ws{};
     size_t off = 0;
-    int h = H, w = W;
     for (int L = 0; L < n_levels; ++L) {
+        const int h = gabor_level_extent(H, L), w = gabor_level_extent(W, L);   // (csrc/gabor_plan.h: the one pyramid arithmetic)
         ws.HL[L] = h;
         ws.WL[L] = w;
         ws.Hp[L] = gabor_hp(h);
@@ -933,8 +929,6 @@ static GaborWs gabor_ws(int B, int H, int W, int n_levels) {
             ws.img_off[L] = off;
             off += ((size_t)B * 3 * h * w + 255) / 256 * 256;
         }
-        h = (h + 1) / 2;
-        w = (w + 1) / 2;
     }
     ws.total = off + 256;   // the second LDS copy of the last tile row reads two bytes past its plane row
     return ws;
@@ -947,7 +941,6 @@ struct GaborSide {
     bool tried = false;
 };
 constexpr int GCS_MAX_DEVICES = 64;
-constexpr long long GCS_GABOR_FORK_MIN_PIXELS = 1 << 21;
 static std::mutex g_side_mu;
 static GaborSide g_side[GCS_MAX_DEVICES];
 static GaborSide *gabor_side() {                     // call with g_side_mu held; NULL: run on the caller's stream only
@@ -982,39 +975,39 @@ extern "C" size_t gcs_gabor_workspace_bytes(int B, int H, int W, int n_scales) {
     return gabor_ws(B, H, W, (n_scales + 1) / 2).total;
 }
 
+// The rules every call of gcs_gabor_features must meet beside its pointers, for the entry point and for the test hook
+// gcs_selftest_gabor_plan alike: the message the call is refused with, or NULL with the layout in *lo.
+static const char *gabor_call_refused(int B, int H, int W, int n_scales, int n_orient, int ksize, int shift, GcsLayout *lo) {
+    if (B <= 0) return "gcs_gabor_features: B must be > 0";
+    if (H < 8 || W < 8) return "gcs_gabor_features: H and W must be >= 8";
+    if (shift < 0 || shift > 23) return "gcs_gabor_features: shift out of range";
+    if (ksize < 1 || ksize > GCS_KSIZE_MAX || (ksize & 1) == 0) return "gcs_gabor_features: ksize must be odd and <= 15";
+    if (B > 65535) return "gcs_gabor_features: B too large for one launch";
+    if (!gcs_make_layout(H, W, n_scales, n_orient, lo)) return "gcs_gabor_features: need 1 <= n_scales <= 8, n_orient >= 1";
+    if ((long long)B * lo->img_bytes > 0x7fffffffffffLL) return "gcs_gabor_features: slab too large";
+    if ((long long)lo->ntiles * lo->tile_bytes > 0xffffffffLL)   // the kernel addresses one image's slab with 32-bit lane offsets
+        return "gcs_gabor_features: one image's feature slab must stay below 4 GiB";
+    if (gabor_hp(H) / 4 + 1 > 65535) return "gcs_gabor_features: H too large for one launch";      // (gabor_hp(H): level 0's padded rows)
+    if ((size_t)W * 6 + 16 > 60 * 1024) return "gcs_gabor_features: W too large for the pyramid row buffer";
+    return nullptr;
+}
+
 extern "C" int gcs_gabor_features(const uint8_t *img, int B, int H, int W, const int8_t *packed,
                                   const int32_t *bias, int n_scales, int n_orient, int ksize, int shift, void *workspace,
                                   uint16_t *feats, gcs_stream_t stream) {
     if (!img || !packed || !bias || !feats || !workspace)
         return gcs_fail(GCS_EINVAL, "gcs_gabor_features: NULL pointer");
-    if (B <= 0) return gcs_fail(GCS_EINVAL, "gcs_gabor_features: B must be > 0");
-    if (H < 8 || W < 8) return gcs_fail(GCS_EINVAL, "gcs_gabor_features: H and W must be >= 8");
-    if (shift < 0 || shift > 23) return gcs_fail(GCS_EINVAL, "gcs_gabor_features: shift out of range");
-    if (ksize < 1 || ksize > GCS_KSIZE_MAX || (ksize & 1) == 0)
-        return gcs_fail(GCS_EINVAL, "gcs_gabor_features: ksize must be odd and <= 15");
-    if (B > 65535) return gcs_fail(GCS_EINVAL, "gcs_gabor_features: B too large for one launch");
     GcsLayout lo;
-    if (!gcs_make_layout(H, W, n_scales, n_orient, &lo))
-        return gcs_fail(GCS_EINVAL, "gcs_gabor_features: need 1 <= n_scales <= 8, n_orient >= 1");
-    if ((long long)B * lo.img_bytes > 0x7fffffffffffLL) return gcs_fail(GCS_EINVAL, "gcs_gabor_features: slab too large");
-    if ((long long)lo.ntiles * lo.tile_bytes > 0xffffffffLL)   // the kernel addresses one image's slab with 32-bit lane offsets
-        return gcs_fail(GCS_EINVAL, "gcs_gabor_features: one image's feature slab must stay below 4 GiB");
+    if (const char *why = gabor_call_refused(B, H, W, n_scales, n_orient, ksize, shift, &lo)) return gcs_fail(GCS_EINVAL, why);
     const GaborWs ws = gabor_ws(B, H, W, lo.n_levels);
-    if (ws.Hp[0] / 4 + 1 > 65535) return gcs_fail(GCS_EINVAL, "gcs_gabor_features: H too large for one launch");
-    if ((size_t)W * 6 + 16 > 60 * 1024) return gcs_fail(GCS_EINVAL, "gcs_gabor_features: W too large for the pyramid row buffer");
     unsigned char *wsb = static_cast<unsigned char *>(workspace);
     const dim3 block(256);
-    // Main region of level L (what gabor_mfma_kernel's tile list covers) and whether gabor_strip_kernel has work
-    const bool pack_r = lo.Wm != GCS_NO_STRIP, pack_b = lo.Hm != GCS_NO_STRIP, strips = pack_r || pack_b;
-    auto region_h = [&](int L) { return pack_b ? lo.Hm >> L : ws.HL[L]; };
-    auto region_w = [&](int L) { return pack_r ? lo.Wm >> L : ws.WL[L]; };
-    auto half_tiles = [&](int L) { return (long long)((region_w(L) + G_TW / 2 - 1) / (G_TW / 2)) * ((region_h(L) + G_TH - 1) / G_TH); };
     // Two-level bank (the default): level 1 only needs the input images, so its pre-pass and its MFMA launch run on a side
     // stream forked from the caller's stream here and joined back before this call returns to it: beside the level-0
     // pre-pass and in the tail of the level-0 MFMA launch (same-box A/B, three runs: stage 0.552 -> 0.530, 0.565 -> 0.542,
     // 0.547 -> 0.532 ms per 64 images). Deeper banks share one MFMA launch that needs every level's planes first; forking
     // only their pre-passes costs more in cross-queue waits than it hides (8x8 bank 0.80 -> 0.87 ms): one stream. Small
-    // batches stay on one stream too.
+    // batches stay on one stream too (gabor_fork_wanted, csrc/gabor_plan.h).
     GaborSide *sd = nullptr;
     std::unique_lock<std::mutex> side_lock;
     // Not while the caller's stream is being captured into a graph: the process-wide side stream would join that capture and
@@ -1022,7 +1015,7 @@ extern "C" int gcs_gabor_features(const uint8_t *img, int B, int H, int W, const
     // thread would then enqueue into a foreign capture). A captured step runs its levels on the one stream.
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(stream, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
-    if (lo.n_levels == 2 && (long long)B * H * W >= GCS_GABOR_FORK_MIN_PIXELS && cap == hipStreamCaptureStatusNone) {
+    if (gabor_fork_wanted(lo, B) && cap == hipStreamCaptureStatusNone) {
         side_lock = std::unique_lock<std::mutex>(g_side_mu);     // the fork / join events are reused: one enqueue at a time
         sd = gabor_side();
         if (!sd) side_lock.unlock();
@@ -1040,7 +1033,6 @@ extern "C" int gcs_gabor_features(const uint8_t *img, int B, int H, int W, const
         side_lock.unlock();
         return e == hipSuccess ? GCS_OK : gcs_hip_fail(e, "gcs_gabor_features(join)");
     };
-#define GCS_STREAM_OF(L) ((forked && (L) >= 1) ? sd->s : stream)
 #define GCS_GABOR_CHECK(what)                                    \
     do {                                                         \
         hipError_t e_ = hipGetLastError();                       \
@@ -1049,15 +1041,13 @@ extern "C" int gcs_gabor_features(const uint8_t *img, int B, int H, int W, const
             return gcs_hip_fail(e_, what);                       \
         }                                                        \
     } while (0)
-    // A call so small that the tiles of ALL its levels fit the resident slots at once (one to four BSD images) also takes
-    // the fused list: level 1's tiles then run beside level 0's instead of in a launch of their own behind them (one image:
-    // the two launches take 19 us each, one after the other; the slot is called once per image, script.py:22-30).
-    long long tiles_all = 0;
-    for (int L = 0; L < lo.n_levels; ++L) tiles_all += (long long)B * ((half_tiles(L) + 1) / 2);
-    // (not for a split-slab bank whose level is three row tiles that cannot run as groups - 9 to 11 filters per level -: the fused
-    //  three-tile kernel with both split store paths live spills 50 VGPRs; such a call takes the two single-level launches)
-    const bool fuse_small = lo.n_levels == 2 && tiles_all <= 2LL * gcs_cu_count() &&
-                            !(lo.split && mtiles(lo.FL[0]) == 3 && lo.FL[0] % 4 != 0);
+    // WHAT is launched, where and in which order: csrc/gabor_plan.h. From here on the plan is executed launch by launch.
+    const GaborPlan plan = gabor_plan(lo, B, ksize, shift, gcs_cu_count(), forked);
+    if (plan.error) {
+        (void)join();
+        return gcs_fail(GCS_EINVAL, plan.error);
+    }
+    const GaborRegions R(lo);
     // split slab: which flag bytes the pre-pass of level L clears (csrc/common.h; level 0 also those of absent levels)
     auto flag_zero = [&](int zmask) {
         GaborFlagZero z{};
@@ -1065,197 +1055,154 @@ extern "C" int gcs_gabor_features(const uint8_t *img, int B, int H, int W, const
         return z;
     };
     const int zmask0 = 1 | (0xf & ~((1 << lo.n_levels) - 1));
-    // ---- pre-passes: the padded planes of every level (level L >= 2 reads level L-1's compact image)
-    for (int L = 0; L < lo.n_levels; ++L) {
-        if (fuse_small && !forked) {                           // a small call: both pre-passes of the two-level bank in one launch
-            if (L == 1) continue;
-            const int n0 = (ws.Hp[0] * (ws.Wp[0] / 16) + 511) / 512;
-            const size_t lds = 2 * (size_t)((W * 3 + 6) & ~3);
-            hipLaunchKernelGGL(gabor_pre01_kernel, dim3(n0 + ws.Hp[1], B), block, lds, stream, img, (size_t)B * H * W * 3, H, W, n0,
-                               ws.HL[0], ws.WL[0], ws.Hp[0], ws.Wp[0], reinterpret_cast<int8_t *>(wsb + ws.plane_off[0]),
-                               ws.HL[1], ws.WL[1], ws.Hp[1], ws.Wp[1], reinterpret_cast<int8_t *>(wsb + ws.plane_off[1]),
-                               flag_zero(zmask0 | 2));
-            GCS_GABOR_CHECK("gcs_gabor_features(pad)");
-            continue;
-        }
-        int8_t *planes = reinterpret_cast<int8_t *>(wsb + ws.plane_off[L]);
-        const int HL = ws.HL[L], WL = ws.WL[L], Hp = ws.Hp[L], Wp = ws.Wp[L];
-        // level-0 pre-pass: about two interior items (16 bytes x 3 channels) per thread and loop round
-        const int pitems = Hp * (Wp / 16);
-        const dim3 pgrid((pitems + 511) / 512, B);
-        uint8_t *img_out = (L >= 1 && L + 1 < lo.n_levels) ? wsb + ws.img_off[L] : nullptr;
-        if (L == 0)
-            hipLaunchKernelGGL((gabor_plane_kernel<0>), pgrid, block, 0, GCS_STREAM_OF(L), img, H, W, HL, WL, Hp, Wp, planes,
-                               (uint8_t *)nullptr, flag_zero(zmask0));
-        else if (L == 1) {
-            const size_t lds = 2 * (size_t)((W * 3 + 6) & ~3);
-            hipLaunchKernelGGL((gabor_down_kernel<true>), dim3(Hp, B), block, lds, GCS_STREAM_OF(L), img, (size_t)B * H * W * 3, H, W,
-                               HL, WL, Hp, Wp, planes, img_out, flag_zero(2));
-        } else {
-            const int Hs = ws.HL[L - 1], Ws = ws.WL[L - 1];
-            const size_t lds = 6 * (size_t)((Ws + 6) & ~3);
-            hipLaunchKernelGGL((gabor_down_kernel<false>), dim3(Hp, B), block, lds, GCS_STREAM_OF(L),
-                               (const uint8_t *)(wsb + ws.img_off[L - 1]), (size_t)B * 3 * Hs * Ws, Hs, Ws, HL, WL, Hp, Wp,
-                               planes, img_out, flag_zero(0));
-        }
-        GCS_GABOR_CHECK("gcs_gabor_features(pad)");
-    }
-    // ---- the bank: one launch per run of levels with the same filter count (every level of an even-scale bank)
     int mt_base[GCS_LEVELS_MAX];
     for (int L = 0, m = 0; L < lo.n_levels; ++L) {
         mt_base[L] = m;
         m += mtiles(lo.FL[L]);
     }
-    const int mtmax = ksize <= 13 ? GCS_GABOR_MTMAX : 2;     // A operand: MT x KS x 4 VGPRs (84 for 3 x 7, 64 for 2 x 8)
-    auto launch_group = [&](int L0, int &L1) -> int {
-        L1 = L0 + 1;
-        // fused lists pay ~2 % for level fields that are no longer launch constants and win the small levels' ramp and
-        // tail back: a gain from three levels on (8x8 bank: 0.90 -> 0.80 ms), a small loss for two (0.552 -> 0.557 ms)
-        if (lo.n_levels > 2 || fuse_small)
-            while (L1 < lo.n_levels && lo.FL[L1] == lo.FL[L0]) ++L1;
-        const int FLg = lo.FL[L0], MT = mtiles(FLg);
-        if (L0 == 0 && L1 > 1)                       // this launch reads planes the side stream is still writing
+    for (int i = 0; i < plan.n; ++i) {
+        const GaborPlanLaunch &l = plan.at(i);
+        if (l.join)                                  // this launch reads planes the side stream is still writing
             if (int rc = join()) return rc;
-        // three row tiles only for single launches of level 0 / 1 (compile-time level): with the level a run-time value the
-        // store path of every level is live and a third tile's 28 A registers spill
-        // (a fused list of exactly levels 0 and 1 - LVL = -2: two store paths - keeps the third tile too)
-        const bool two_fused = lo.n_levels == 2 && L0 == 0 && L1 == 2;
-        const int mtmax_here = ((L1 - L0 == 1 && L0 <= 1) || two_fused) ? mtmax : 2;
-        // a small call (fuse_small) whose filters fill whole row tiles: ONE launch of MT groups of one-tile workgroups (blockIdx.y)
-        const bool grouped = fuse_small && FLg % 4 == 0 && MT > 1;
-        const int passes = grouped ? 1 : (MT + mtmax_here - 1) / mtmax_here;
-        const int per_pass = grouped ? MT : (MT + passes - 1) / passes;   // 4 tiles -> 2 + 2, not 3 + 1
-        for (int mt0 = 0; mt0 < MT; mt0 += per_pass) {
-            const int n = grouped ? 1 : MT - mt0 >= per_pass ? per_pass : MT - mt0;
-            // filters of this launch: [4*mt0, min(FL, 4*(mt0+n))) of each level (planes c*FL + f)
-            const int fl_here = FLg - 4 * mt0 < 4 * n ? FLg - 4 * mt0 : 4 * n;
-            const int gq = (fl_here - 4 * (n - 1) + 1) / 2;
+        hipStream_t st = l.side ? sd->s : stream;
+        const dim3 grid(l.grid_x, l.grid_y);
+        const int L = l.L0;
+        int8_t *planes = reinterpret_cast<int8_t *>(wsb + ws.plane_off[L]);
+        const int HL = ws.HL[L], WL = ws.WL[L], Hp = ws.Hp[L], Wp = ws.Wp[L];
+        uint8_t *img_out = (L >= 1 && L + 1 < lo.n_levels) ? wsb + ws.img_off[L] : nullptr;
+        switch (l.kernel) {
+        case GP_PRE01: {                             // a small call: both pre-passes of the two-level bank in one launch
+            const int n0 = (int)l.grid_x - ws.Hp[1];
+            const size_t lds = 2 * (size_t)((W * 3 + 6) & ~3);
+            hipLaunchKernelGGL(gabor_pre01_kernel, grid, block, lds, st, img, (size_t)B * H * W * 3, H, W, n0,
+                               ws.HL[0], ws.WL[0], ws.Hp[0], ws.Wp[0], reinterpret_cast<int8_t *>(wsb + ws.plane_off[0]),
+                               ws.HL[1], ws.WL[1], ws.Hp[1], ws.Wp[1], reinterpret_cast<int8_t *>(wsb + ws.plane_off[1]),
+                               flag_zero(zmask0 | 2));
+            GCS_GABOR_CHECK("gcs_gabor_features(pad)");
+            break;
+        }
+        case GP_PLANE0:
+            hipLaunchKernelGGL((gabor_plane_kernel<0>), grid, block, 0, st, img, H, W, HL, WL, Hp, Wp, planes,
+                               (uint8_t *)nullptr, flag_zero(zmask0));
+            GCS_GABOR_CHECK("gcs_gabor_features(pad)");
+            break;
+        case GP_DOWN_RGB: {
+            const size_t lds = 2 * (size_t)((W * 3 + 6) & ~3);
+            hipLaunchKernelGGL((gabor_down_kernel<true>), grid, block, lds, st, img, (size_t)B * H * W * 3, H, W,
+                               HL, WL, Hp, Wp, planes, img_out, flag_zero(2));
+            GCS_GABOR_CHECK("gcs_gabor_features(pad)");
+            break;
+        }
+        case GP_DOWN: {
+            const int Hs = ws.HL[L - 1], Ws = ws.WL[L - 1];
+            const size_t lds = 6 * (size_t)((Ws + 6) & ~3);
+            hipLaunchKernelGGL((gabor_down_kernel<false>), grid, block, lds, st,
+                               (const uint8_t *)(wsb + ws.img_off[L - 1]), (size_t)B * 3 * Hs * Ws, Hs, Ws, HL, WL, Hp, Wp,
+                               planes, img_out, flag_zero(0));
+            GCS_GABOR_CHECK("gcs_gabor_features(pad)");
+            break;
+        }
+        case GP_STRIP: {
+            StripArgs A{};
+            A.n_levels = l.L1 - l.L0;
+            int tasks = 0;
+            for (int Ls = l.L0; Ls < l.L1; ++Ls) {
+                StripLevel &v = A.lv[Ls - l.L0];
+                v.planes = reinterpret_cast<const int8_t *>(wsb + ws.plane_off[Ls]);
+                v.apack = packed + (size_t)mt_base[Ls] * 8 * 64 * 16;
+                v.bias = bias + (size_t)mt_base[Ls] * 4;
+                v.Hp = ws.Hp[Ls]; v.Wp = ws.Wp[Ls]; v.HL = ws.HL[Ls]; v.WL = ws.WL[Ls];
+                v.col_x = R.pack_r ? lo.Wm >> Ls : 0;
+                v.nseg_col = R.pack_r ? (ws.HL[Ls] + 31) / 32 : 0;
+                v.row_y = R.pack_b ? lo.Hm >> Ls : 0;
+                v.row_n = R.pack_b ? ws.HL[Ls] - (lo.Hm >> Ls) : 0;
+                v.row_w = R.pack_r ? lo.Wm >> Ls : ws.WL[Ls];
+                v.nseg_row = (v.row_w + 63) / 64;
+                tasks += 3 * (v.nseg_col + v.row_n * v.nseg_row);
+                v.task_end = tasks;
+                v.FL = lo.FL[Ls]; v.MT = mtiles(lo.FL[Ls]); v.row0 = lo.row0[Ls]; v.L = Ls;
+            }
+            if (A.n_levels == 1) A.lv[1] = A.lv[0];
+            A.tasks_per_image = tasks;
+            if ((long long)tasks * B != l.total_tiles) { (void)join(); return gcs_fail(GCS_EINVAL, "gcs_gabor_features: plan and strip tasks disagree"); }
+            if (l.KS == 7)
+                hipLaunchKernelGGL((gabor_strip_kernel<7>), grid, block, 0, st, A, lo, shift, reinterpret_cast<unsigned char *>(feats), l.total_tiles);
+            else
+                hipLaunchKernelGGL((gabor_strip_kernel<8>), grid, block, 0, st, A, lo, shift, reinterpret_cast<unsigned char *>(feats), l.total_tiles);
+            GCS_GABOR_CHECK("gcs_gabor_features(strips)");
+            break;
+        }
+        case GP_MFMA: {
             GaborLevels G{};
             long long total_ll = 0;
-            for (int L = L0; L < L1; ++L) {
-                GaborLevel &v = G.lv[L - L0];
-                v.planes = reinterpret_cast<const int8_t *>(wsb + ws.plane_off[L]);
-                v.apack = packed + (size_t)(mt_base[L] + mt0) * 8 * 64 * 16;
-                v.bias = bias + (size_t)(mt_base[L] + mt0) * 4;
-                v.HLm = region_h(L);
-                v.Hp = ws.Hp[L];
-                v.Wp = ws.Wp[L];
-                v.pitchLm = pack_r ? region_w(L) : round_up(ws.WL[L], 8);
-                v.htx = (region_w(L) + G_TW / 2 - 1) / (G_TW / 2);
-                v.hcount = (int)half_tiles(L);
+            for (int Lg = l.L0; Lg < l.L1; ++Lg) {
+                GaborLevel &v = G.lv[Lg - l.L0];
+                v.planes = reinterpret_cast<const int8_t *>(wsb + ws.plane_off[Lg]);
+                v.apack = packed + (size_t)(mt_base[Lg] + l.mt0) * 8 * 64 * 16;
+                v.bias = bias + (size_t)(mt_base[Lg] + l.mt0) * 4;
+                v.HLm = R.region_h(Lg);
+                v.Hp = ws.Hp[Lg];
+                v.Wp = ws.Wp[Lg];
+                v.pitchLm = R.pack_r ? R.region_w(Lg) : round_up(ws.WL[Lg], 8);
+                v.htx = R.htx(Lg);
+                v.hcount = (int)R.half_tiles(Lg);
                 v.tiles_per_image = (v.hcount + 1) / 2;
                 total_ll += (long long)v.tiles_per_image * B;
-                if (total_ll > 0x3fffffffLL) return gcs_fail(GCS_EINVAL, "gcs_gabor_features: too many tiles");
                 v.tile_end = (int)total_ll;
-                v.L = L;
-                v.offL = lo.split ? lo.sl0[L] : lo.off[L];
+                v.L = Lg;
+                v.offL = lo.split ? lo.sl0[Lg] : lo.off[Lg];
             }
-            for (int i = L1 - L0; i < GCS_LEVELS_MAX; ++i) {      // unused entries: never selected (tile < total_tiles)
-                G.lv[i] = G.lv[L1 - L0 - 1];
+            for (int i = l.L1 - l.L0; i < GCS_LEVELS_MAX; ++i) {      // unused entries: never selected (tile < total_tiles)
+                G.lv[i] = G.lv[l.L1 - l.L0 - 1];
                 G.lv[i].tile_end = 0x7fffffff;
             }
-            const int total_tiles = (int)total_ll;
             const GaborSlab slab{lo.bx_n, lo.ntiles, lo.tile_bytes, lo.img_bytes, lo.S, lo.mid_off, lo.top_off, lo.flag_off};
-            // persistent grid: one workgroup per resident slot (two 54 KB workgroups per CU)
-            const int slots = gcs_cu_count() * 2;
-            const dim3 grid(total_tiles < slots ? total_tiles : slots, grouped ? MT : 1);
-#define GCS_GABOR_LAUNCH4(MT_, GQ_, KS_, LV_, FA_)                                                                     \
-    gabor_launch<MT_, GQ_, KS_, LV_, FA_>(lo.split != 0, grid, block, GCS_STREAM_OF(L0), G, FLg, 4 * mt0, shift,          \
-                                          reinterpret_cast<unsigned char *>(feats), total_tiles, slab)
-            // single launches of level 0 / level 1 (every bank of at most two levels) compile that level's store path alone
-#define GCS_GABOR_LAUNCH3(MT_, GQ_, KS_, FA_)                                       \
-    do {                                                                            \
-        if (L1 - L0 == 1 && L0 == 0) GCS_GABOR_LAUNCH4(MT_, GQ_, KS_, 0, FA_);      \
-        else if (L1 - L0 == 1 && L0 == 1) GCS_GABOR_LAUNCH4(MT_, GQ_, KS_, 1, FA_); \
-        else GCS_GABOR_LAUNCH4(MT_, GQ_, KS_, -1, FA_);                             \
-    } while (0)
-            // the short epilogue needs shift == 8 (bytes 1-2 of the low accumulator) and no unused accumulator quad
-#define GCS_GABOR_LAUNCH2(MT_, KS_)                                       \
-    do {                                                                  \
-        if (gq == 1) GCS_GABOR_LAUNCH3(MT_, 1, KS_, false);               \
-        else if (shift == 8) GCS_GABOR_LAUNCH3(MT_, 2, KS_, true);        \
-        else GCS_GABOR_LAUNCH3(MT_, 2, KS_, false);                       \
-    } while (0)
-            // 7 K-steps need the kernel inside rows 1..13 of the 15-row frame (ksize <= 13)
-            if (ksize <= 13) {
-                if (n == 3) {                    // single launch of level 0 or 1, or the fused list of both (mtmax_here)
-#define GCS_GABOR_LAUNCH3T(GQ_, FA_)                                        \
-    do {                                                                    \
-        if (two_fused) GCS_GABOR_LAUNCH4(3, GQ_, 7, -2, FA_);               \
-        else if (L0 == 0) GCS_GABOR_LAUNCH4(3, GQ_, 7, 0, FA_);             \
-        else GCS_GABOR_LAUNCH4(3, GQ_, 7, 1, FA_);                          \
-    } while (0)
-                    if (gq == 1) GCS_GABOR_LAUNCH3T(1, false);
-                    else if (shift == 8) GCS_GABOR_LAUNCH3T(2, true);
-                    else GCS_GABOR_LAUNCH3T(2, false);
-#undef GCS_GABOR_LAUNCH3T
-                }
-                else if (n == 2) GCS_GABOR_LAUNCH2(2, 7);
-                else GCS_GABOR_LAUNCH2(1, 7);
-            } else {
-                if (n == 2) GCS_GABOR_LAUNCH2(2, 8);
-                else GCS_GABOR_LAUNCH2(1, 8);
+            if (total_ll != l.total_tiles) {               // checked before anything of this entry is launched, like the strips' tasks
+                (void)join();
+                return gcs_fail(GCS_EINVAL, "gcs_gabor_features: plan and bank tiles disagree");
             }
-#undef GCS_GABOR_LAUNCH4
-#undef GCS_GABOR_LAUNCH3
-#undef GCS_GABOR_LAUNCH2
+            bool found = false;
+#define GCS_GABOR_ARM(MT_, GQ_, KS_, LV_, FA_)                                                                           \
+    if (l.MT == MT_ && l.GQ == GQ_ && l.KS == KS_ && l.LVL == LV_ && l.FAST == FA_) {                                    \
+        gabor_launch<MT_, GQ_, KS_, LV_, FA_>(l.SPLIT, grid, block, st, G, lo.FL[l.L0], 4 * l.mt0, shift,                \
+                                              reinterpret_cast<unsigned char *>(feats), l.total_tiles, slab);            \
+        found = true;                                                                                                    \
+    }
+            GCS_GABOR_ARMS(GCS_GABOR_ARM)
+#undef GCS_GABOR_ARM
+            if (!found) {                                  // a plan entry without a compiled kernel is an error, never another kernel (nothing was launched)
+                (void)join();
+                return gcs_fail(GCS_EINVAL, "gcs_gabor_features: no bank kernel for a launch of the plan");
+            }
             GCS_GABOR_CHECK("gcs_gabor_features");
+            break;
         }
-        return GCS_OK;
-    };
-    // The packed edge strips (57 + 30 tasks of a few microseconds per BSD image), one small launch per level on the level's
-    // stream IN FRONT of its MFMA launch: level 0's right behind the plane pre-pass, while the chip is still empty (a launch
-    // behind the MFMA kernels cost 27 us at the end of the stage; reserving four CUs for it beside level 0 held level 1 back:
-    // profiles/r4_notes.md), level 1's on the side stream in the tail of level 0 like level 1 itself.
-    auto launch_strips = [&](int L0s, int L1s) -> int {
-        StripArgs A{};
-        A.n_levels = L1s - L0s;
-        int tasks = 0;
-        for (int L = L0s; L < L1s; ++L) {
-            StripLevel &v = A.lv[L - L0s];
-            v.planes = reinterpret_cast<const int8_t *>(wsb + ws.plane_off[L]);
-            v.apack = packed + (size_t)mt_base[L] * 8 * 64 * 16;
-            v.bias = bias + (size_t)mt_base[L] * 4;
-            v.Hp = ws.Hp[L]; v.Wp = ws.Wp[L]; v.HL = ws.HL[L]; v.WL = ws.WL[L];
-            v.col_x = pack_r ? lo.Wm >> L : 0;
-            v.nseg_col = pack_r ? (ws.HL[L] + 31) / 32 : 0;
-            v.row_y = pack_b ? lo.Hm >> L : 0;
-            v.row_n = pack_b ? ws.HL[L] - (lo.Hm >> L) : 0;
-            v.row_w = pack_r ? lo.Wm >> L : ws.WL[L];
-            v.nseg_row = (v.row_w + 63) / 64;
-            tasks += 3 * (v.nseg_col + v.row_n * v.nseg_row);
-            v.task_end = tasks;
-            v.FL = lo.FL[L]; v.MT = mtiles(lo.FL[L]); v.row0 = lo.row0[L]; v.L = L;
         }
-        if (A.n_levels == 1) A.lv[1] = A.lv[0];
-        A.tasks_per_image = tasks;
-        const long long total = (long long)tasks * B;
-        if (total > 0x3fffffffLL) { (void)join(); return gcs_fail(GCS_EINVAL, "gcs_gabor_features: too many strip tasks"); }
-        hipStream_t ss = GCS_STREAM_OF(L0s);
-        const dim3 sgrid((unsigned)((total + 3) / 4));
-        if (ksize <= 13)
-            hipLaunchKernelGGL((gabor_strip_kernel<7>), sgrid, block, 0, ss, A, lo, shift, reinterpret_cast<unsigned char *>(feats), (int)total);
-        else
-            hipLaunchKernelGGL((gabor_strip_kernel<8>), sgrid, block, 0, ss, A, lo, shift, reinterpret_cast<unsigned char *>(feats), (int)total);
-        GCS_GABOR_CHECK("gcs_gabor_features(strips)");
-        return GCS_OK;
-    };
-    for (int L0 = 0, L1 = 0; L0 < lo.n_levels; L0 = L1) {
-        // (a fused list - L1 > L0 + 1 - joins the side stream first: every level's planes are then ready on `stream`)
-        int Lend = L0 + 1;
-        if (lo.n_levels > 2 || fuse_small)
-            while (Lend < lo.n_levels && lo.FL[Lend] == lo.FL[L0]) ++Lend;
-        if (strips) {
-            if (L0 == 0 && Lend > 1)
-                if (int rc = join()) return rc;
-            if (int rc = launch_strips(L0, Lend < 2 ? Lend : 2)) return rc;
-        }
-        if (int rc = launch_group(L0, L1)) return rc;
     }
     if (int rc = join()) return rc;
 #undef GCS_GABOR_CHECK
-#undef GCS_STREAM_OF
     return GCS_OK;
+}
+
+// Test hook (include/gcs.h): the plan as text, one line per launch. Host arithmetic only unless cu_count == 0.
+extern "C" int gcs_selftest_gabor_plan(int B, int H, int W, int n_scales, int n_orient, int ksize, int shift, int cu_count,
+                                       int forked, char *buf, size_t buf_bytes) {
+    if (buf && buf_bytes) buf[0] = 0;
+    GcsLayout lo;
+    if (cu_count < 0 || gabor_call_refused(B, H, W, n_scales, n_orient, ksize, shift, &lo)) return -1;
+    const GaborPlan plan = gabor_plan(lo, B, ksize, shift, cu_count ? cu_count : gcs_cu_count(), forked != 0);
+    if (plan.error) return -1;
+    size_t at = 0;
+    for (int i = 0; i < plan.n; ++i) {
+        const GaborPlanLaunch &l = plan.at(i);
+        char line[192];
+        const int n = gabor_plan_line(l, line, sizeof line);
+        if (buf && at + (size_t)n < buf_bytes) {
+            memcpy(buf + at, line, (size_t)n + 1);
+            at += (size_t)n;
+        }
+    }
+    return plan.n;
 }
 
 // ------------------------------------------------------------------------------- unpack

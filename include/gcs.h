@@ -204,6 +204,19 @@ const char *gcs_selftest_pass_kernel(int H, int W, int n_scales, int n_orient, i
  * the list plain; 0 for a kernel that loads every tile plain (wide slab, generic) and for a list of 256 MiB or less; -1 for a call
  * gcs_kmeans_assign_accumulate refuses (shape, bank, B, k, n_sets). Launches nothing and touches no device. */
 int gcs_selftest_pass_nt_limit(int B, int H, int W, int n_scales, int n_orient, int k, int n_sets);
+/* Test hook (host only, added within ABI 18: a new entry point changes no existing call, so GCS_ABI_VERSION did not move): the
+ * launch plan of gcs_gabor_features for this call - the very list it executes (csrc/gabor_plan.h) - as text in buf (NUL-terminated;
+ * lines that do not fit buf_bytes are left out, buf may be NULL), one line per launch in launch order:
+ *     <kernel> levels=<L0>:<L1> f0=<first filter> grid=<x>x<y> tiles=<n> stream=<main|side> join=<0|1>
+ * <kernel>: gabor_plane_kernel<0>, gabor_down_kernel<true|false>, gabor_pre01_kernel (the padded planes of levels [L0, L1)),
+ * gabor_strip_kernel<7|8> (the packed edge strips of those levels; tiles = its tasks) or gabor_mfma_kernel<MT,GQ,KS,LVL,FAST,SPLIT>
+ * (filters f0 .. of those levels; tiles = the launch's tile list, grid.y = its row-tile groups). join=1: the caller's stream waits
+ * for the side stream in front of the launch (it always does behind the last one). cu_count: the compute units the persistent grids
+ * and the small-call rule are sized for, 0 = those of the current device (gcs_device_cu_count; the only case that touches a
+ * device). forked != 0: the caller has a side stream to give (no graph capture): the plan uses it where the bank and the batch
+ * size ask for one. Returns the number of launches, -1 for a call gcs_gabor_features refuses. Launches nothing. */
+int gcs_selftest_gabor_plan(int B, int H, int W, int n_scales, int n_orient, int ksize, int shift, int cu_count, int forked,
+                            char *buf, size_t buf_bytes);
 
 /* ---- boundary scoring of one image -------------------------------------- */
 

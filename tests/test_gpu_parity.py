@@ -424,8 +424,12 @@ def test_global_codebook_bit_exact(torch_cuda):
 def test_small_call_launch_forms_of_two_level_banks(torch_cuda, no, ks, b, h, w):
     """Round 5: a small call (every tile of both levels fits the resident slots) runs both pre-passes in one launch
     (gabor_pre01_kernel) and the bank's row tiles side by side as blockIdx.y groups of one launch when the 2 * n_orient filters of a
-    level fill whole row tiles (n_orient 4 / 6 / 8: two / three / four groups; 8-K-step frames for ksize 15); otherwise the fused
-    two-level list of three row tiles (LVL = -2: n_orient 5) or two launches of two (n_orient 7); n_orient 2: one tile, no groups.
+    level fill whole row tiles (n_orient 4 / 6 / 8: two / three / four groups of <1,2,KS,-1,true,SPLIT>; 8-K-step frames for ksize
+    15); n_orient 7 (wide slab): the fused list in two launches, <2,2,7,-1,true,false> and <2,1,7,-1,false,false>; n_orient 2: one
+    tile, no groups (<1,2,7,-1,true,true>). n_orient 5 is NOT a small call: a split-slab level of three ragged row tiles is excluded
+    (csrc/gabor_plan.h), it takes gabor_plane_kernel<0>, gabor_down_kernel<true> and the single-level launches <3,1,7,0,false,true>
+    and <3,1,7,1,false,true>. No bank here takes the fused two-level list of three row tiles (LVL = -2: wide banks with 18, 22, ...
+    filters per level - tests/test_gpu_gabor_instantiations.py). What gcs_selftest_gabor_plan answers for these calls.
     Features and labels == the oracle, packed edge strips (81 = 8 k + 1, 121 = 8 k + 1) included."""
     from gabor_color_image_segmentation_amd import Segmenter
     torch = torch_cuda
