@@ -538,6 +538,64 @@ class HipOps:
                                              K, g, c, stride, out.data_ptr(), self._stream()),
                    "gcs_region_paint")
 
+    def adjacency_buffers(self, tables, capacity):
+        """The workspace of ``gcs_region_adjacency`` for ``tables`` images (``gcs_region_adjacency_cuts``: n_cuts * B) at ``capacity``
+        edges each (SPEC.md §20): the open-addressing tables the edges are counted in (a captured graph must own it)."""
+        need = self.lib.gcs_region_adjacency_workspace_bytes(int(tables), int(capacity))
+        if need == 0:
+            raise ValueError("no adjacency workspace for this batch / capacity (B >= 1, 1 <= capacity <= 16384)")
+        return self.empty_bytes(need)
+
+    def _need_graph(self, edges, vals, count, lead, what):
+        """An edge table of SPEC.md §20 over the leading axes ``lead``: edges (.., cap, 2) int32, vals (.., cap, 3) int64 (the bits of
+        the uint64 columns), count ``lead`` int32 -> cap."""
+        torch = self.torch
+        if edges is None or vals is None or count is None or edges.dim() != len(lead) + 2:
+            raise ValueError(f"{what}: edges (.., capacity, 2) int32, vals (.., capacity, 3) int64 and count int32 are needed")
+        cap = int(edges.shape[-2])
+        self._need(edges, torch.int32, lead + (cap, 2), f"{what}: edges must be a contiguous (.., capacity, 2) int32 tensor")
+        self._need(vals, torch.int64, lead + (cap, 3), f"{what}: vals must be a contiguous (.., capacity, 3) int64 tensor")
+        self._need(count, torch.int32, lead, f"{what}: count must be a contiguous int32 tensor over the leading axes")
+        return cap
+
+    @_on_device
+    def region_adjacency(self, labels, imgs, strength, b, h, w, K, workspace, edges, vals, count):
+        """The edge table of SPEC.md §20 of an int32 (B,H,W) label map: ``edges`` (B, capacity, 2) int32, ``vals`` (B, capacity, 3)
+        int64 (the bits of the uint64 columns length, contrast, strength) and ``count`` (B,) int32 are written whole. ``imgs``: None
+        or the (B,H,W,3) uint8 images; ``strength``: None or a (B,H,W) int32 plane; ``workspace``: from ``adjacency_buffers(B,
+        capacity)``. Three launches, capturable."""
+        torch, K = self.torch, int(K)
+        self._need(labels, torch.int32, (b, h, w), "labels must be a contiguous (B,H,W) int32 tensor")
+        self._need(imgs, torch.uint8, (b, h, w, 3), "imgs must be a contiguous (B,H,W,3) uint8 tensor")
+        self._need(strength, torch.int32, (b, h, w), "strength must be a contiguous (B,H,W) int32 tensor")
+        cap = self._need_graph(edges, vals, count, (b,), "region_adjacency")
+        if labels is None or workspace is None or workspace.numel() * workspace.element_size() < \
+                self.lib.gcs_region_adjacency_workspace_bytes(b, cap):
+            raise ValueError("labels and a workspace of adjacency_buffers(B, capacity) are needed")
+        _lib.check(self.lib.gcs_region_adjacency(labels.data_ptr(), None if imgs is None else imgs.data_ptr(),
+                                                 None if strength is None else strength.data_ptr(), b, h, w, K, cap,
+                                                 workspace.data_ptr(), edges.data_ptr(), vals.data_ptr(), count.data_ptr(),
+                                                 self._stream()), "gcs_region_adjacency")
+
+    @_on_device
+    def region_adjacency_cuts(self, edges, vals, count, group, b, K, G, workspace, edges_out, vals_out, count_out):
+        """The edge tables of the cuts of SPEC.md §20 from a leaf table: ``group`` (n_cuts, B, K) int32 (``region_props_cuts``' own, or
+        any relabelling), ``G`` the number of groups; ``edges_out`` (n_cuts, B, capacity, 2) int32, ``vals_out`` (n_cuts, B, capacity,
+        3) int64 and ``count_out`` (n_cuts, B) int32 are written whole; ``workspace``: from ``adjacency_buffers(n_cuts * B,
+        capacity)``. Three launches, capturable."""
+        torch, K = self.torch, int(K)
+        cap = self._need_graph(edges, vals, count, (b,), "region_adjacency_cuts")
+        if group is None or group.dim() != 3:
+            raise ValueError("group must be a contiguous (n_cuts, B, K) int32 tensor")
+        n = int(group.shape[0])
+        self._need(group, torch.int32, (n, b, K), "group must be a contiguous (n_cuts, B, K) int32 tensor")
+        cap_out = self._need_graph(edges_out, vals_out, count_out, (n, b), "region_adjacency_cuts (outputs)")
+        if workspace is None or workspace.numel() * workspace.element_size() < self.lib.gcs_region_adjacency_workspace_bytes(n * b, cap_out):
+            raise ValueError("a workspace of adjacency_buffers(n_cuts * B, capacity) is needed")
+        _lib.check(self.lib.gcs_region_adjacency_cuts(edges.data_ptr(), vals.data_ptr(), count.data_ptr(), group.data_ptr(), b, K, int(G),
+                                                      cap, n, cap_out, workspace.data_ptr(), edges_out.data_ptr(), vals_out.data_ptr(),
+                                                      count_out.data_ptr(), self._stream()), "gcs_region_adjacency_cuts")
+
     def download(self, dst_pinned, src):
         """Device tensor -> pinned host tensor of the same bytes on the current stream, by SDMA (gcs_download)."""
         self._check_dev(src)
@@ -1380,6 +1438,64 @@ class Segmenter:
             self.ops.region_paint(labels.contiguous(), None if group is None else group.contiguous(), sums, b, h, w, K, out)
         return out
 
+    # ---- SPEC.md §20: which regions touch, and along how much boundary
+    def _need_adjacency(self):
+        if not hasattr(self.ops, "region_adjacency"):
+            raise ValueError("the region adjacency graph needs ops that have it")
+
+    def region_adjacency_device(self, labels, K=None, imgs=None, strength=None, capacity=None):
+        """(B,H,W) int32 device tensor -> the edge table of SPEC.md §20, ``(edges (B, capacity, 2) int32, vals (B, capacity, 3) int64,
+        count (B,) int32)``: per image ``count`` rows (a, b), a < b, sorted, with the bits of the uint64 columns length (pixel pairs
+        across the boundary), contrast (their summed squared colour difference; 0 without ``imgs``, the (B,H,W,3) uint8 images) and
+        strength (the summed values, negatives as 0, of ``strength``, a (B,H,W) int32 plane, on both sides; 0 without); rows behind
+        them hold (-1, -1) and zeros, and an image with more than ``capacity`` edges has count -1. ``K=None``: one read of
+        ``labels.max()`` from the device. ``capacity=None``: min(16384, max(64, 4 K), K (K - 1) / 2 or 1, 2HW - H - W or 1)."""
+        torch = _torch()
+        self._need_adjacency()
+        if labels.dim() != 3 or labels.dtype != torch.int32:
+            raise ValueError("labels must be a (B,H,W) int32 tensor")
+        labels = labels.contiguous()
+        b, h, w = labels.shape
+        with self._device():
+            K = max(1, int(labels.max()) + 1) if K is None else int(K)
+            if K < 1:
+                raise ValueError("K must be at least 1")
+            if capacity is None:
+                capacity = min(16384, max(64, 4 * K), K * (K - 1) // 2 or 1, 2 * h * w - h - w or 1)
+            cap = int(capacity)
+            if not 1 <= cap <= 16384:
+                raise ValueError("capacity must be in 1 .. 16384")
+            edges = torch.empty((b, cap, 2), dtype=torch.int32, device=labels.device)
+            vals = torch.empty((b, cap, 3), dtype=torch.int64, device=labels.device)
+            count = torch.empty((b,), dtype=torch.int32, device=labels.device)
+            self.ops.region_adjacency(labels, None if imgs is None else imgs.contiguous(),
+                                      None if strength is None else strength.contiguous(), b, h, w, K,
+                                      self.ops.adjacency_buffers(b, cap), edges, vals, count)
+        return edges, vals, count
+
+    def cut_adjacency_device(self, edges, vals, count, group, G=None, capacity=None):
+        """The edge tables of cuts from the leaf table, without reading a pixel (SPEC.md §20). edges, vals, count: what
+        ``region_adjacency_device`` returned for the leaf map; ``group`` (n_cuts, B, K) int32 as ``cut_props_device`` returns it (or
+        any relabelling of the K leaves; entries outside 0 .. G-1 drop their leaf). ``G``: the number of groups, default K.
+        ``capacity``: default min(the leaf table's, G (G - 1) / 2 or 1). Returns ``(edges (n_cuts, B, capacity, 2), vals (n_cuts, B, capacity, 3), count
+        (n_cuts, B))`` in the same format: the graph of the map ``cut_regions_device`` writes at that cut."""
+        torch = _torch()
+        self._need_adjacency()
+        if group.dim() != 3 or edges.dim() != 3 or group.shape[1] != edges.shape[0]:
+            raise ValueError("group must be an (n_cuts, B, K) int32 tensor and edges the (B, capacity, 2) leaf table of the same images")
+        n, b, K = group.shape
+        G = K if G is None else int(G)
+        cap = min(int(edges.shape[1]), G * (G - 1) // 2 or 1) if capacity is None else int(capacity)
+        if G < 1 or not 1 <= cap <= 16384:
+            raise ValueError("G must be at least 1 and capacity in 1 .. 16384")
+        with self._device():
+            edges_out = torch.empty((n, b, cap, 2), dtype=torch.int32, device=edges.device)
+            vals_out = torch.empty((n, b, cap, 3), dtype=torch.int64, device=edges.device)
+            count_out = torch.empty((n, b), dtype=torch.int32, device=edges.device)
+            self.ops.region_adjacency_cuts(edges.contiguous(), vals.contiguous(), count.contiguous(), group.contiguous(), b, K, G,
+                                           self.ops.adjacency_buffers(n * b, cap), edges_out, vals_out, count_out)
+        return edges_out, vals_out, count_out
+
     def superpixels_device(self, imgs):
         """(B,H,W,3) uint8 device tensor -> (labels (B,H,W) int32, centres (B, ny * nx, D + 2) int32: the D features, cy, cx the
         last assign used) of SPEC.md §13, without the post-passes (tests / debugging)."""
@@ -1967,19 +2083,30 @@ def _one_image(img):
     return img
 
 
-def segment_regions(img, **kw):
+def segment_regions(img, adjacency=False, **kw):
     """(H,W,3) uint8 -> ``(labels (H,W) int32, table)``: ``segment(img, **kw)`` and the descriptors of its regions (SPEC.md §19,
     ``regions.region_table``: area, centroid, bbox, mean_rgb, mean_features, used; one entry per label 0 .. labels.max()). The table
-    is made from the delivered map, behind every post-pass of the plan, so it describes what the caller gets."""
-    from .regions import region_table
+    is made from the delivered map, behind every post-pass of the plan, so it describes what the caller gets. ``adjacency=True``: the
+    table gains the key ``"adjacency"``, the region adjacency graph of the delivered map (SPEC.md §20, ``regions.adjacency_table``
+    with ``n_regions`` = the number of labels: pairs, length, mean_contrast from ``img``, mean_strength 0, degree, neighbours).
+    A delivered map with more than 16 384 edges (no map of connected regions of fewer than 5 463 labels has) raises ``ValueError``."""
+    from .regions import region_table, adjacency_table
     torch = _torch()
     img = _one_image(img)
     seg = _plan(kw)
     labels = seg(img)
     dev = seg.ops.device
-    sums, bbox = seg.region_props_device(torch.from_numpy(img[None]).to(dev),
-                                         torch.from_numpy(np.ascontiguousarray(labels[None], np.int32)).to(dev))
-    return labels, region_table(sums[0].cpu().numpy(), bbox[0].cpu().numpy())
+    imgs_d = torch.from_numpy(img[None]).to(dev)
+    lab_d = torch.from_numpy(np.ascontiguousarray(labels[None], np.int32)).to(dev)
+    sums, bbox = seg.region_props_device(imgs_d, lab_d)
+    table = region_table(sums[0].cpu().numpy(), bbox[0].cpu().numpy())
+    if adjacency:
+        k = int(sums.shape[1])
+        edges, vals, count = seg.region_adjacency_device(lab_d, K=k, imgs=imgs_d)
+        if int(count[0]) < 0:                                      # more edges than the default capacity: once more at the largest
+            edges, vals, count = seg.region_adjacency_device(lab_d, K=k, imgs=imgs_d, capacity=16384)
+        table["adjacency"] = adjacency_table(edges[0].cpu().numpy(), vals[0].cpu().numpy(), int(count[0]), n_regions=k)
+    return labels, table
 
 
 def render_regions(img, labels) -> np.ndarray:

@@ -600,6 +600,40 @@ int gcs_region_props_cuts(const uint64_t *sums_dev, const int32_t *bbox_dev, con
 int gcs_region_paint(const int32_t *labels_dev, const int32_t *group_dev, const uint64_t *sums_dev, int B, int H, int W, int K, int G,
                      int C, int row_stride, uint8_t *rgb_out_dev, gcs_stream_t stream);
 
+/* ---- region adjacency graph of label maps and tree cuts (SPEC.md §20) -------------------------------- */
+
+/* The edges of a label map are the label pairs (a, b), a < b, both in 0 .. K-1, that meet across at least one horizontal or vertical
+ * pixel pair (a crossing). An edge carries three uint64 columns { length, contrast, strength }: the number of crossings, the sum over
+ * crossings of the squared colour difference (all three channels), and the sum over crossings of max(E(p), 0) + max(E(q), 0) for a
+ * plane E. A table of an image is E_cap rows: count rows (a, b) / columns sorted by (a, b) ascending, then rows (-1, -1) / zeros;
+ * an image with more than E_cap edges gets count = -1 and sentinel rows only (the other images are unaffected).
+ *   gcs_region_adjacency       three launches on `stream` (fill; one pass over the pixels; sort and write). labels_dev int32 [B][H][W];
+ *                              img_dev uint8 [B][H][W][3] or NULL (contrast = 0); strength_dev int32 [B][H][W] or NULL (strength = 0),
+ *                              any int32, negatives count as 0. A pair with a label outside 0 .. K-1 is a crossing of nothing.
+ *                              workspace_dev: gcs_region_adjacency_workspace_bytes(B, E_cap) bytes, 8-byte aligned.
+ *                                edges_out_dev int32 [B][E_cap][2], vals_out_dev uint64 [B][E_cap][3], count_out_dev int32 [B]
+ *   gcs_region_adjacency_cuts  three launches. edges_dev / vals_dev / count_dev: a leaf table at E_cap; group_dev int32 [n_cuts][B][K],
+ *                              any values (a slice per cut of gcs_region_props_cuts' group_out_dev). Under cut c a leaf edge (a, b)
+ *                              of image b' with g_a = group[c][b'][a], g_b = group[c][b'][b], both in 0 .. G-1 and different, adds
+ *                              its columns into edge (min(g_a, g_b), max(g_a, g_b)); every other leaf edge (and a row whose labels
+ *                              are outside 0 .. K-1) is dropped. count = -1 in gives count = -1 out, in every cut.
+ *                              workspace_dev: gcs_region_adjacency_workspace_bytes(n_cuts * B, E_out_cap) bytes.
+ *                                edges_out_dev int32 [n_cuts][B][E_out_cap][2], vals_out_dev uint64 [n_cuts][B][E_out_cap][3],
+ *                                count_out_dev int32 [n_cuts][B], each table in the format above at E_out_cap
+ * Every output element is written; outputs and workspace may hold anything on entry; inputs are read only. Exact integers and a final
+ * sort: the same bits in any execution order. No allocation, no host synchronisation (capturable). GCS_EINVAL, with nothing launched:
+ * a NULL pointer (img_dev and strength_dev may be NULL), B outside 1..65535, H or W outside 1..4096, K < 1, G < 1, E_cap or E_out_cap
+ * outside 1..16384, n_cuts outside 1..64, B * H * W, n_cuts * B * K, B * E_cap * 3 or the 8-byte words of the workspace not below
+ * 2^31. gcs_region_adjacency_workspace_bytes returns 0 for B < 1 or E_cap outside 1..16384.
+ * Added within ABI 18: new entry points change no existing call, so GCS_ABI_VERSION did not move. */
+size_t gcs_region_adjacency_workspace_bytes(int B, int E_cap);
+int gcs_region_adjacency(const int32_t *labels_dev, const uint8_t *img_dev, const int32_t *strength_dev, int B, int H, int W, int K,
+                         int E_cap, void *workspace_dev, int32_t *edges_out_dev, uint64_t *vals_out_dev, int32_t *count_out_dev,
+                         gcs_stream_t stream);
+int gcs_region_adjacency_cuts(const int32_t *edges_dev, const uint64_t *vals_dev, const int32_t *count_dev, const int32_t *group_dev,
+                              int B, int K, int G, int E_cap, int n_cuts, int E_out_cap, void *workspace_dev, int32_t *edges_out_dev,
+                              uint64_t *vals_out_dev, int32_t *count_out_dev, gcs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
