@@ -12,9 +12,9 @@
 //           and stays 0). A workgroup owns a run of whole rows of one image; its counters sit in LDS when the K (n_cuts + 2) +
 //           n_cuts + 1 of them fit SW_LDS_COUNTERS (the budget of the other sweep's pixel pass) and leave with one vector atomic per
 //           non-zero counter, otherwise every count is a global atomic (slow, exact). No neighbour is read: U already holds them.
-//   groups  a workgroup per image: rs_absorbers and, per distinct tau, rs_group_reps (tree_cuts.h: the walk of gcs_region_sweep);
+//   groups  a workgroup per image: rs_absorbers and, per distinct tau, rs_group_reps (tree_cuts.h: the walk every cut kernel shares);
 //           every leaf adds its area and the suffix sum of its bins above c into its rep's LDS row, the rows leave densely.
-// Integer sums only: any order gives the same bits.
+// Both kernels take their tau list from rs_taus (tree_cuts.h). Integer sums only: any order gives the same bits.
 #include "common.h"
 #include "tree_cuts.h"
 
@@ -23,16 +23,6 @@ constexpr int CS_PIXELS_MIN = 4096;                            // pixels a workg
 
 __global__ __launch_bounds__(256) void cut_shapes_zero_kernel(unsigned *p, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = 0u;
-}
-
-// s_tau[c] = tau of cut c, made non-decreasing (an entry of regions that is not below its predecessor repeats its predecessor's cut,
-// as in gcs_region_sweep). Called by the whole workgroup, ends behind a __syncthreads().
-__device__ __forceinline__ void cs_taus(const int32_t *__restrict__ regions, int n_cuts, int alive, int n_rows, int *s_tau) {
-    if ((int)threadIdx.x < n_cuts) s_tau[threadIdx.x] = rs_tau(alive, regions[threadIdx.x], n_rows);
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int c = 1; c < n_cuts; ++c) s_tau[c] = max(s_tau[c], s_tau[c - 1]);
-    __syncthreads();
 }
 
 __global__ __launch_bounds__(CS_THREADS) void cut_shapes_pixel_kernel(const int32_t *__restrict__ labels,
@@ -47,7 +37,7 @@ __global__ __launch_bounds__(CS_THREADS) void cut_shapes_pixel_kernel(const int3
     const int y0 = blockIdx.x * rows_per, y1 = min(H, y0 + rows_per);
     if (use_lds)
         for (int i = tid; i < n_tab; i += CS_THREADS) cs_tab[i] = 0u;
-    cs_taus(regions, n_cuts, alive_p[b], K - 1, s_tau);        // (and the barrier behind the zeroing)
+    rs_taus(regions, n_cuts, alive_p[b], K - 1, s_tau);        // (and the barrier behind the zeroing)
     unsigned *tab = use_lds ? cs_tab : ws + (size_t)b * n_tab;
     unsigned *t_area = tab + (size_t)K * E, *t_bd = t_area + K;
     const int tau0 = s_tau[0];
@@ -105,7 +95,7 @@ __global__ __launch_bounds__(AG_THREADS) void cut_shapes_group_kernel(const int3
     const int n_tab = K * (E + 1) + E;
     const unsigned *bins = ws + (size_t)b * n_tab, *leaf_area = bins + (size_t)K * E, *bd = leaf_area + K;
     rs_absorbers(merges + (size_t)b * (K - 1) * 2, K - 1, K, s_dk, &s_changed);   // (merges is not read with K = 1)
-    cs_taus(regions, n_cuts, alive_p[b], K - 1, s_tau);
+    rs_taus(regions, n_cuts, alive_p[b], K - 1, s_tau);
     if (tid == 0) {                                            // boundary[c] = the pixels with m' > c
         unsigned above = 0;
         for (int c = n_cuts - 1; c >= 0; --c) {

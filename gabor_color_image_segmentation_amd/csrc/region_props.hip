@@ -7,27 +7,25 @@
 // group of a cut are made from the rows of its leaves: the pixels are read once, for every cut.
 //   gcs_region_props       rp_fill_kernel   sums := 0, boxes := empty.
 //                          rp_stats_kernel  one workgroup per 8 x 32 pixel tile, one thread per pixel, ONE read of labels, image and
-//                                           canonical features: the shape of rt_stats_kernel (region_tree.hip). The
-//                                           labels a tile sees get a row of uint32 accumulators and a box in LDS through a 32-slot
-//                                           hash table (256 pixels * 65 535 < 2^32, 256 * 4095 < 2^32), eight lanes that agree on the
-//                                           label add one sum, touched rows leave with 64-bit vector atomics and atomicMin / atomicMax;
-//                                           a tile that sees more than 32 labels adds straight into the global rows (slow, exact).
-//                                           No table indexed by K exists on chip: K is bounded by the output's size alone.
-//   gcs_region_props_cuts  rp_cuts_kernel   a workgroup per image: rs_absorbers once, then per distinct tau rs_group_reps
-//                                           (tree_cuts.h: the walk of gcs_region_sweep) and the numbering of gcs_region_tree_cut
-//                                           (groups by increasing rep); a wave per leaf adds its row into its group's dense row.
+//                                           canonical features. Sums: the tile accumulator of label_tile.h, shared with
+//                                           rt_stats_kernel (region_tree.hip), rows [n, y, x, R, G, B, D sums] (256 * 4095 < 2^32).
+//                                           Boxes, this kernel's own: a box per slot in LDS, eight lanes that agree add one box,
+//                                           atomicMin / atomicMax into the global boxes; a tile of more than 32 labels writes both
+//                                           straight to memory. No table indexed by K exists on chip: K is bounded by the output.
+//   gcs_region_props_cuts  rp_cuts_kernel   a workgroup per image, all of its walk from tree_cuts.h: rs_absorbers and rs_taus once,
+//                                           then per distinct tau rs_group_reps and rs_number_groups (the cut and the numbering
+//                                           of gcs_region_tree_cut); a wave per leaf adds its row into its group's dense row.
 //   gcs_region_paint       rp_paint_kernel  4096 pixels of an image per workgroup; the packed mean colours of the G rows sit in LDS
 //                                           where they fit (RP_PAINT_LDS rows), else every pixel reads its row in L2 and divides.
 //                                           A thread paints four consecutive pixels of the batch: 12 bytes, three whole words.
 #include <algorithm>
 
 #include "common.h"
+#include "label_tile.h"
 #include "tree_cuts.h"
 
 namespace {
 
-constexpr int RP_TH = 8, RP_TW = 32;         // statistics tile: 8 rows of 32 pixels, 256 threads
-constexpr int RP_SLOTS = 32;                 // labels a tile accumulates in LDS
 constexpr int RP_D_MAX = 207, RP_HW_MAX = 4096, RP_FIXED = 6;
 constexpr int RP_PP = 4096;                  // pixels per workgroup of the paint kernel
 constexpr int RP_PAINT_LDS = 2048;           // rows whose mean colours a paint workgroup keeps in LDS (8 KiB: two per pixel it serves)
@@ -51,24 +49,19 @@ __global__ __launch_bounds__(256) void rp_fill_kernel(u64 *sums, size_t n_sums, 
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < 4 * n_rows; i += step) bbox[i] = rp_empty_box(i, H, W);
 }
 
-__global__ __launch_bounds__(256) void rp_stats_kernel(RpArgs A) {
+__global__ __launch_bounds__(LT_THREADS) void rp_stats_kernel(RpArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned rp_smem[];
     const int tid = (int)threadIdx.x, b = (int)blockIdx.z, D = A.D, C = RP_FIXED + D, K = A.K;
-    unsigned *s_acc = rp_smem;                                             // [RP_SLOTS][C]
-    int *s_box = reinterpret_cast<int *>(s_acc + RP_SLOTS * C);            // [RP_SLOTS][4]
-    int *s_keys = s_box + RP_SLOTS * 4;                                    // [RP_SLOTS] label of the slot, -1: free
-    int *s_over = s_keys + RP_SLOTS;                                       // more labels than slots
-    for (int idx = tid; idx < RP_SLOTS * C; idx += 256) s_acc[idx] = 0u;
-    if (tid < RP_SLOTS) {
-        s_keys[tid] = -1;
-        s_box[4 * tid] = A.H, s_box[4 * tid + 1] = A.W, s_box[4 * tid + 2] = -1, s_box[4 * tid + 3] = -1;
-    }
-    if (tid == 0) *s_over = 0;
+    unsigned *s_acc = rp_smem;                                             // [LT_SLOTS][C]
+    int *s_box = reinterpret_cast<int *>(s_acc + LT_SLOTS * C);            // [LT_SLOTS][4]
+    int *s_keys = s_box + LT_SLOTS * 4;                                    // [LT_SLOTS] label of the slot, -1: free
+    int *s_over = s_keys + LT_SLOTS;                                       // more labels than slots
+    lt_clear(s_acc, C, s_keys, s_over);
+    if (tid < LT_SLOTS) s_box[4 * tid] = A.H, s_box[4 * tid + 1] = A.W, s_box[4 * tid + 2] = -1, s_box[4 * tid + 3] = -1;
     __syncthreads();
     const size_t hw = (size_t)A.H * A.W;
-    const int yy = (int)blockIdx.y * RP_TH + tid / RP_TW, xx = (int)blockIdx.x * RP_TW + tid % RP_TW;
-    const bool valid = yy < A.H && xx < A.W;
-    const int y = yy < A.H ? yy : A.H - 1, x = xx < A.W ? xx : A.W - 1;    // clamped: reads stay inside
+    int y, x;
+    const bool valid = lt_pixel(A.H, A.W, &y, &x);
     const size_t p = (size_t)y * A.W + x;
     const int l = A.labels[(size_t)b * hw + p];
     const bool in = valid && (unsigned)l < (unsigned)K;                    // a label outside 0 .. K-1 is counted nowhere
@@ -77,19 +70,7 @@ __global__ __launch_bounds__(256) void rp_stats_kernel(RpArgs A) {
         const uint8_t *c = A.img + ((size_t)b * hw + p) * 3;
         fixed[3] = c[0], fixed[4] = c[1], fixed[5] = c[2];
     }
-    int slot = -1;
-    if (in) {
-        const unsigned h = ((unsigned)l * 2654435761u) >> 27;
-        for (int q = 0; q < RP_SLOTS; ++q) {
-            const int s = (int)((h + q) & (RP_SLOTS - 1));
-            const int old = atomicCAS(&s_keys[s], -1, l);
-            if (old == -1 || old == l) {
-                slot = s;
-                break;
-            }
-        }
-        if (slot < 0) *s_over = 1;
-    }
+    const int slot = lt_claim(s_keys, s_over, l, in);
     __syncthreads();
     const uint16_t *px = D ? A.feats + (size_t)b * D * hw + p : nullptr;
     u64 *g_sums = A.sums + (size_t)b * K * C;
@@ -106,50 +87,20 @@ __global__ __launch_bounds__(256) void rp_stats_kernel(RpArgs A) {
         }
         return;
     }
-    // eight neighbouring lanes (one run of a tile row) that are all counted and agree on the label add ONE sum and one box
-    int same = in ? 1 : 0;
-#pragma unroll
-    for (int m = 1; m < 8; m <<= 1) {
-        const int os = __shfl_xor(slot, m), osame = __shfl_xor(same, m);
-        same = same && osame && os == slot;
-    }
+    const int same = lt_agree(slot, in);                                   // eight lanes that agree add one sum and one box
     unsigned *row = s_acc + (in ? slot : 0) * C;
     int *box = s_box + (in ? slot : 0) * 4;
-    const bool lead = (tid & 7) == 0;
     if (same) {
-        if (lead) atomicMin(box, y), atomicMin(box + 1, x), atomicMax(box + 2, y), atomicMax(box + 3, x + 7);
+        if ((tid & 7) == 0) atomicMin(box, y), atomicMin(box + 1, x), atomicMax(box + 2, y), atomicMax(box + 3, x + 7);
     } else if (in) {
         atomicMin(box, y), atomicMin(box + 1, x), atomicMax(box + 2, y), atomicMax(box + 3, x);
     }
 #pragma unroll
-    for (int e = 0; e < RP_FIXED; ++e) {
-        unsigned t = fixed[e];
-#pragma unroll
-        for (int m = 1; m < 8; m <<= 1) t += (unsigned)__shfl_xor((int)t, m);
-        if (same) {
-            if (lead) atomicAdd(row + e, t);
-        } else if (in) {
-            atomicAdd(row + e, fixed[e]);
-        }
-    }
-    for (int d = 0; d < D; ++d) {
-        const unsigned v = px[(size_t)d * hw];
-        unsigned t = v;
-#pragma unroll
-        for (int m = 1; m < 8; m <<= 1) t += (unsigned)__shfl_xor((int)t, m);
-        if (same) {
-            if (lead) atomicAdd(row + RP_FIXED + d, t);
-        } else if (in) {
-            atomicAdd(row + RP_FIXED + d, v);
-        }
-    }
+    for (int e = 0; e < RP_FIXED; ++e) lt_add(row + e, fixed[e], same, in);
+    for (int d = 0; d < D; ++d) lt_add(row + RP_FIXED + d, px[(size_t)d * hw], same, in);
     __syncthreads();
-    for (int idx = tid; idx < RP_SLOTS * C; idx += 256) {
-        const int s = idx / C, e = idx - s * C;
-        const unsigned v = s_acc[idx];
-        if (v) atomicAdd(g_sums + (size_t)s_keys[s] * C + e, (u64)v);     // (v != 0: the slot has a label)
-    }
-    if (tid < RP_SLOTS * 4) {
+    lt_flush(s_acc, s_keys, C, g_sums);
+    if (tid < LT_SLOTS * 4) {
         const int s = tid >> 2, e = tid & 3, key = s_keys[s];
         if (key >= 0) {
             if (e < 2) atomicMin(g_box + (size_t)key * 4 + e, s_box[tid]);
@@ -170,20 +121,17 @@ __global__ __launch_bounds__(AG_THREADS) void rp_cuts_kernel(const u64 *__restri
     __shared__ unsigned s_used[RS_K_MAX / 32], s_rep[RS_K_MAX / 32], s_pref[RS_K_MAX / 32];
     __shared__ int s_tau[RS_CUTS_MAX], s_off[RS_CUTS_MAX + 1];
     __shared__ int s_changed;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, KW = (K + 31) >> 5;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const u64 *leaf = sums + (size_t)b * K * C;
     const int *leaf_box = bbox + (size_t)b * K * 4;
     u64 *out = sums_out + (size_t)b * Rsum * C;
     int *out_box = bbox_out + (size_t)b * Rsum * 4;
     rs_absorbers(merges + (size_t)b * (K - 1) * 2, K - 1, K, s_dk, &s_changed);   // (merges is not read with K = 1)
-    if (tid < n_cuts) s_tau[tid] = rs_tau(alive_p[b], regions[tid], K - 1);
     if (tid < RS_K_MAX / 32) s_used[tid] = 0u;
-    __syncthreads();
-    if (tid == 0) {
-        // an entry that is not below its predecessor repeats its predecessor's cut; cut c owns min(K, R_c) rows behind the cuts before it
+    rs_taus(regions, n_cuts, alive_p[b], K - 1, s_tau);                    // (and the barrier behind the zeroing)
+    if (tid == 0) {                                                        // cut c owns min(K, R_c) rows behind the cuts before it
         int acc = 0;
         for (int c = 0; c < n_cuts; ++c) {
-            if (c > 0) s_tau[c] = max(s_tau[c], s_tau[c - 1]);
             s_off[c] = acc;
             acc += min(K, max(regions[c], 0));
         }
@@ -198,28 +146,7 @@ __global__ __launch_bounds__(AG_THREADS) void rp_cuts_kernel(const u64 *__restri
     for (int c = 0; c < n_cuts; ++c) {
         if (c == 0 || s_tau[c] != s_tau[c - 1]) {
             rs_group_reps(s_dk, s_root, K, s_tau[c]);
-            if (tid < RS_K_MAX / 32) s_rep[tid] = 0u;
-            __syncthreads();
-            for (int q = tid; q < K; q += AG_THREADS)
-                if ((s_used[q >> 5] >> (q & 31)) & 1u) {
-                    const unsigned r = s_root[q];
-                    atomicOr(&s_rep[r >> 5], 1u << (r & 31));
-                }
-            __syncthreads();
-            if (tid == 0) {
-                unsigned acc = 0;
-                for (int w = 0; w < KW; ++w) {
-                    s_pref[w] = acc;
-                    acc += (unsigned)__popc(s_rep[w]);
-                }
-            }
-            __syncthreads();
-            for (int q = tid; q < K; q += AG_THREADS) {                    // groups numbered in increasing order of their rep
-                const unsigned r = s_root[q];
-                const bool used = (s_used[q >> 5] >> (q & 31)) & 1u;
-                s_group[q] = used ? (short)(s_pref[r >> 5] + (unsigned)__popc(s_rep[r >> 5] & ((1u << (r & 31)) - 1u))) : (short)-1;
-            }
-            __syncthreads();
+            rs_number_groups(s_used, s_root, K, s_rep, s_pref, s_group);
         }
         int32_t *g_out = group_out + ((size_t)c * B + b) * K;
         for (int q = tid; q < K; q += AG_THREADS) g_out[q] = (int32_t)s_group[q];
@@ -331,8 +258,8 @@ extern "C" int gcs_region_props(const int32_t *labels, const uint8_t *img, const
     const int fgrid = (int)std::min<size_t>((n_sums + 255) / 256, (size_t)gcs_cu_count() * 8);
     hipLaunchKernelGGL(rp_fill_kernel, dim3(fgrid), dim3(256), 0, stream, A.sums, n_sums, bbox_out, n_rows, H, W);
     GCS_CHECK_LAUNCH("gcs_region_props (fill)");
-    const dim3 tiles((W + RP_TW - 1) / RP_TW, (H + RP_TH - 1) / RP_TH, B);
-    hipLaunchKernelGGL(rp_stats_kernel, tiles, dim3(256), (size_t)RP_SLOTS * (C + 5) * 4 + 16, stream, A);
+    const dim3 tiles((W + LT_TW - 1) / LT_TW, (H + LT_TH - 1) / LT_TH, B);
+    hipLaunchKernelGGL(rp_stats_kernel, tiles, dim3(LT_THREADS), (size_t)LT_SLOTS * (C + 5) * 4 + 16, stream, A);
     GCS_CHECK_LAUNCH("gcs_region_props (statistics)");
     return GCS_OK;
 }

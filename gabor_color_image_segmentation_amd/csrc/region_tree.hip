@@ -5,9 +5,8 @@
 // node of least (cost, rep), mutual picks merge, the round's merges are listed in (cost, rep) order. One call enqueues
 //   rt_zero_kernel      the [K][D + 1] uint64 sums and the K x K adjacency bit matrix of every image := 0.
 //   rt_stats_kernel     one workgroup per 8 x 32 pixel tile, one thread per pixel: ONE read of the canonical tensor and of the label
-//                       map. Sums: the labels a tile sees get a row of uint32 accumulators in LDS through a 32-slot hash table (256
-//                       pixels * 65 535 < 2^32), eight lanes that agree on the label add one sum, touched rows are flushed with 64-bit
-//                       vector atomics; a tile that sees more than 32 labels adds straight into the global rows (slow, exact).
+//                       map. Sums: the tile accumulator of label_tile.h, shared with rp_stats_kernel (region_props.hip), rows
+//                       [D sums, n]; a tile that sees more than 32 labels adds straight into the global rows (slow, exact).
 //                       Adjacency: a pixel whose right / lower neighbour carries another in-range label sets bits (a, b) and (b, a)
 //                       (an atomic OR only when the bit is not seen set: every later pixel of the same border reads and skips).
 //   rt_merge_kernel     ONE workgroup of 1024 threads per image runs every round (the trip count is data, so the loop lives here):
@@ -16,19 +15,20 @@
 //                       remap (the merged node's neighbours drop the dead label's bit, gain the rep's, and pick again next round).
 //                       Picks, costs, pair list and flags sit in LDS, the means too where they fit beside them; sums and adjacency
 //                       stay in the workspace (L2). Only workgroup barriers: images are independent.
-// and gcs_region_tree_cut one launch: a workgroup per image builds the parent table of the first alive - R merges in LDS (parent <
-// child, so pointer jumping needs no union by rank), marks the labels in use, numbers the roots in increasing order and relabels.
+// and gcs_region_tree_cut one launch: a workgroup per image walks the list as every cut kernel does (tree_cuts.h: rs_absorbers, then
+// rs_group_reps at tau = alive - R: a row counts when 0 <= a < b < K and both are still reps), marks the labels in use, numbers
+// their groups in increasing order of rep (rs_number_groups) and relabels.
 // No allocation, no host synchronisation: every launch sits on the caller's stream (and inside a captured graph).
 #include <algorithm>
 
 #include "common.h"
+#include "label_tile.h"
+#include "tree_cuts.h"
 
 namespace {
 
-constexpr int RT_TH = 8, RT_TW = 32;         // statistics tile: 8 rows of 32 pixels, 256 threads
-constexpr int RT_SLOTS = 32;                 // labels a tile accumulates in LDS
-constexpr int RT_D_MAX = 207, RT_K_MAX = 4096, RT_HW_MAX = 4096;
-constexpr int RT_T = 1024, RT_NW = RT_T / 64;   // merge / cut workgroup
+constexpr int RT_D_MAX = 207, RT_K_MAX = RS_K_MAX, RT_HW_MAX = 4096;
+constexpr int RT_T = 1024, RT_NW = RT_T / 64;   // merge / contour-prepare workgroup
 constexpr unsigned RT_NONE = 0xffffu;        // "no adjacent node" (a label is below 4096)
 constexpr size_t RT_LDS_MAX = 65536;
 
@@ -63,20 +63,17 @@ __device__ __forceinline__ void rt_edge(unsigned *adj, int KW, int a, int b) {
     if (!(rt_ld(wb) & bb)) atomicOr(wb, bb);
 }
 
-__global__ __launch_bounds__(256) void rt_stats_kernel(RtArgs A) {
+__global__ __launch_bounds__(LT_THREADS) void rt_stats_kernel(RtArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned rt_smem[];
-    const int tid = (int)threadIdx.x, b = (int)blockIdx.z, D = A.D, E = D + 1, K = A.K;
-    unsigned *s_acc = rt_smem;                                             // [RT_SLOTS][E]
-    int *s_keys = reinterpret_cast<int *>(s_acc + RT_SLOTS * E);          // [RT_SLOTS] label of the slot, -1: free
-    int *s_over = s_keys + RT_SLOTS;                                       // more labels than slots
-    for (int idx = tid; idx < RT_SLOTS * E; idx += 256) s_acc[idx] = 0u;
-    if (tid < RT_SLOTS) s_keys[tid] = -1;
-    if (tid == 0) *s_over = 0;
+    const int b = (int)blockIdx.z, D = A.D, E = D + 1, K = A.K;
+    unsigned *s_acc = rt_smem;                                             // [LT_SLOTS][E]
+    int *s_keys = reinterpret_cast<int *>(s_acc + LT_SLOTS * E);          // [LT_SLOTS] label of the slot, -1: free
+    int *s_over = s_keys + LT_SLOTS;                                       // more labels than slots
+    lt_clear(s_acc, E, s_keys, s_over);
     __syncthreads();
     const size_t hw = (size_t)A.H * A.W;
-    const int yy = (int)blockIdx.y * RT_TH + tid / RT_TW, xx = (int)blockIdx.x * RT_TW + tid % RT_TW;
-    const bool valid = yy < A.H && xx < A.W;
-    const int y = yy < A.H ? yy : A.H - 1, x = xx < A.W ? xx : A.W - 1;    // clamped: reads stay inside
+    int y, x;
+    const bool valid = lt_pixel(A.H, A.W, &y, &x);
     const int *lab = A.labels + (size_t)b * hw + (size_t)y * A.W + x;
     const int l = *lab;
     const bool in = valid && (unsigned)l < (unsigned)K;                    // a label outside 0 .. K-1 is counted nowhere
@@ -91,19 +88,7 @@ __global__ __launch_bounds__(256) void rt_stats_kernel(RtArgs A) {
             if (r != l && (unsigned)r < (unsigned)K) rt_edge(adj, A.KW, l, r);
         }
     }
-    int slot = -1;
-    if (in) {
-        const unsigned h = ((unsigned)l * 2654435761u) >> 27;
-        for (int p = 0; p < RT_SLOTS; ++p) {
-            const int s = (int)((h + p) & (RT_SLOTS - 1));
-            const int old = atomicCAS(&s_keys[s], -1, l);
-            if (old == -1 || old == l) {
-                slot = s;
-                break;
-            }
-        }
-        if (slot < 0) *s_over = 1;
-    }
+    const int slot = lt_claim(s_keys, s_over, l, in);
     __syncthreads();
     const uint16_t *px = A.feats + (size_t)b * D * hw + (size_t)y * A.W + x;
     u64 *g_sums = A.sums + (size_t)b * K * E;
@@ -115,32 +100,11 @@ __global__ __launch_bounds__(256) void rt_stats_kernel(RtArgs A) {
         }
         return;
     }
-    // eight neighbouring lanes that are all counted and agree on the label add ONE sum (fewer same-address LDS atomics)
-    int same = in ? 1 : 0;
-#pragma unroll
-    for (int m = 1; m < 8; m <<= 1) {
-        const int os = __shfl_xor(slot, m), osame = __shfl_xor(same, m);
-        same = same && osame && os == slot;
-    }
+    const int same = lt_agree(slot, in);
     unsigned *row = s_acc + (in ? slot : 0) * E;
-    const bool lead = (tid & 7) == 0;
-    for (int d = 0; d < E; ++d) {
-        const unsigned v = d < D ? px[(size_t)d * hw] : 1u;
-        unsigned t = v;
-#pragma unroll
-        for (int m = 1; m < 8; m <<= 1) t += (unsigned)__shfl_xor((int)t, m);
-        if (same) {
-            if (lead) atomicAdd(row + d, t);
-        } else if (in) {
-            atomicAdd(row + d, v);
-        }
-    }
+    for (int d = 0; d < E; ++d) lt_add(row + d, d < D ? px[(size_t)d * hw] : 1u, same, in);
     __syncthreads();
-    for (int idx = tid; idx < RT_SLOTS * E; idx += 256) {
-        const int s = idx / E, e = idx - s * E;
-        const unsigned v = s_acc[idx];
-        if (v) atomicAdd(g_sums + (size_t)s_keys[s] * E + e, (u64)v);
-    }
+    lt_flush(s_acc, s_keys, E, g_sums);
 }
 
 // LDS of the merge kernel: 16 bytes of counters, then per node the pick's cost (8 bytes) and target (2), a slot of the pair list (2)
@@ -329,66 +293,28 @@ __global__ __launch_bounds__(RT_T) void rt_merge_kernel(RtArgs A, int mean_in_ld
     }
 }
 
-__global__ __launch_bounds__(RT_T) void rt_cut_kernel(const int *labels, const int *merges, const int *alive_p, int H, int W, int K,
-                                                      int R, int *out) {
-    __shared__ unsigned short s_parent[RT_K_MAX];
-    __shared__ short s_new[RT_K_MAX];
-    __shared__ unsigned s_used[RT_K_MAX / 32], s_root[RT_K_MAX / 32], s_pref[RT_K_MAX / 32];
-    const int tid = (int)threadIdx.x, b = (int)blockIdx.x, KW = (K + 31) >> 5;
+// LDS: the absorber table and the reps of tree_cuts.h, the new number of every label, three bit rows.
+__global__ __launch_bounds__(AG_THREADS) void rt_cut_kernel(const int *labels, const int *merges, const int *alive_p, int H, int W,
+                                                            int K, int R, int *out) {
+    __shared__ unsigned s_dk[RS_K_MAX];
+    __shared__ unsigned short s_root[RS_K_MAX];
+    __shared__ short s_new[RS_K_MAX];
+    __shared__ unsigned s_used[RS_K_MAX / 32], s_rep[RS_K_MAX / 32], s_pref[RS_K_MAX / 32];
+    __shared__ int s_changed;
+    const int tid = (int)threadIdx.x, b = (int)blockIdx.x;
     const size_t hw = (size_t)H * W;
     labels += (size_t)b * hw;
     out += (size_t)b * hw;
-    merges += (size_t)b * (K - 1) * 2;
-    const int m = min(max(alive_p[b] - R, 0), K - 1);                      // rows to apply
-    for (int q = tid; q < K; q += RT_T) s_parent[q] = (unsigned short)q;
-    if (tid < RT_K_MAX / 32) s_used[tid] = s_root[tid] = 0u;
-    __syncthreads();
-    for (int t = tid; t < m; t += RT_T) {
-        const int a = merges[2 * t], c = merges[2 * t + 1];
-        if (a >= 0 && a < c && c < K) s_parent[c] = (unsigned short)a;    // every c dies once; (-1, -1) rows are skipped
-    }
-    __syncthreads();
-    for (int it = 0; it < 12; ++it) {                                      // parent < child: chains of at most 4096 = 2^12 links
-        unsigned short pp[RT_K_MAX / RT_T];
-#pragma unroll
-        for (int j = 0; j < RT_K_MAX / RT_T; ++j) {
-            const int q = tid + j * RT_T;
-            pp[j] = q < K ? s_parent[s_parent[q]] : 0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < RT_K_MAX / RT_T; ++j) {
-            const int q = tid + j * RT_T;
-            if (q < K) s_parent[q] = pp[j];
-        }
-        __syncthreads();
-    }
-    for (size_t p = tid; p < hw; p += RT_T) {
+    if (tid < RS_K_MAX / 32) s_used[tid] = 0u;                             // (the barriers of the walk lie before the pixel pass)
+    rs_absorbers(merges + (size_t)b * (K - 1) * 2, K - 1, K, s_dk, &s_changed);   // (merges is not read with K = 1)
+    rs_group_reps(s_dk, s_root, K, rs_tau(alive_p[b], R, K - 1));
+    for (size_t p = tid; p < hw; p += AG_THREADS) {
         const int l = labels[p];
         if ((unsigned)l < (unsigned)K && !(s_used[l >> 5] & (1u << (l & 31)))) atomicOr(&s_used[l >> 5], 1u << (l & 31));
     }
     __syncthreads();
-    for (int q = tid; q < K; q += RT_T)
-        if (s_used[q >> 5] & (1u << (q & 31))) {
-            const int r = s_parent[q];
-            atomicOr(&s_root[r >> 5], 1u << (r & 31));
-        }
-    __syncthreads();
-    if (tid == 0) {
-        unsigned acc = 0;
-        for (int w = 0; w < KW; ++w) {
-            s_pref[w] = acc;
-            acc += (unsigned)__popc(s_root[w]);
-        }
-    }
-    __syncthreads();
-    for (int q = tid; q < K; q += RT_T) {                                  // groups numbered in increasing order of their rep
-        const int r = s_parent[q];
-        const bool used = s_used[q >> 5] & (1u << (q & 31));
-        s_new[q] = used ? (short)(s_pref[r >> 5] + (unsigned)__popc(s_root[r >> 5] & ((1u << (r & 31)) - 1u))) : (short)-1;
-    }
-    __syncthreads();
-    for (size_t p = tid; p < hw; p += RT_T) {                              // (out may be labels: a pixel is read, then written, by one thread)
+    rs_number_groups(s_used, s_root, K, s_rep, s_pref, s_new);
+    for (size_t p = tid; p < hw; p += AG_THREADS) {                        // (out may be labels: a pixel is read, then written, by one thread)
         const int l = labels[p];
         out[p] = (unsigned)l < (unsigned)K ? (int)s_new[l] : -1;
     }
@@ -598,8 +524,8 @@ extern "C" int gcs_region_tree(const uint16_t *feats, const int32_t *labels, int
     const int zgrid = (int)std::min<size_t>((n16 + 255) / 256, (size_t)gcs_cu_count() * 8);
     hipLaunchKernelGGL(rt_zero_kernel, dim3(zgrid), dim3(256), 0, stream, reinterpret_cast<uint4 *>(ws), n16);
     GCS_CHECK_LAUNCH("gcs_region_tree (zero)");
-    const dim3 tiles((W + RT_TW - 1) / RT_TW, (H + RT_TH - 1) / RT_TH, B);
-    hipLaunchKernelGGL(rt_stats_kernel, tiles, dim3(256), (size_t)RT_SLOTS * (D + 1) * 4 + RT_SLOTS * 4 + 16, stream, A);
+    const dim3 tiles((W + LT_TW - 1) / LT_TW, (H + LT_TH - 1) / LT_TH, B);
+    hipLaunchKernelGGL(rt_stats_kernel, tiles, dim3(LT_THREADS), (size_t)LT_SLOTS * (D + 1) * 4 + LT_SLOTS * 4 + 16, stream, A);
     GCS_CHECK_LAUNCH("gcs_region_tree (statistics)");
     const size_t state = rt_state_bytes(K), with_mean = state + k * D * 2;
     const int mean_in_lds = with_mean <= RT_LDS_MAX ? 1 : 0;
@@ -613,7 +539,7 @@ extern "C" int gcs_region_tree_cut(const int32_t *labels, const int32_t *merges,
     if (!labels || !alive || !labels_out || (K > 1 && !merges)) return gcs_fail(GCS_EINVAL, "gcs_region_tree_cut: NULL pointer");
     if (!rt_shape_ok(B, H, W, K)) return gcs_fail(GCS_EINVAL, "gcs_region_tree_cut: bad shape (1 <= B <= 65535, 1 <= H, W <= 4096, 1 <= K <= 4096)");
     if (R < 1) return gcs_fail(GCS_EINVAL, "gcs_region_tree_cut: R must be >= 1");
-    hipLaunchKernelGGL(rt_cut_kernel, dim3(B), dim3(RT_T), 0, stream, labels, merges, alive, H, W, K, R, labels_out);
+    hipLaunchKernelGGL(rt_cut_kernel, dim3(B), dim3(AG_THREADS), 0, stream, labels, merges, alive, H, W, K, R, labels_out);
     GCS_CHECK_LAUNCH("gcs_region_tree_cut");
     return GCS_OK;
 }

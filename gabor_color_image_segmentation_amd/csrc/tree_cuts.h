@@ -1,7 +1,10 @@
-// tree_cuts.h — what the kernels that walk the cuts of a region tree share (SPEC.md §16, §17): which rows of a merge list count and
-// what absorbs every label (step 1), and the group rep of every label at one cut (pointer jumping). Used by region_sweep_kernel
-// (scoring.hip: gcs_region_sweep, gcs_region_sweep_under) and cut_shapes_group_kernel (cut_shapes.hip: gcs_cut_shapes). Every
-// function is called by ALL AG_THREADS threads of a workgroup; the LDS arrays belong to the caller.
+// tree_cuts.h — what the kernels that walk the cuts of a region tree share (SPEC.md §14, §16, §17, §19): which rows of a merge list
+// count and what absorbs every label (step 1), the non-decreasing tau of a list of cuts, the group rep of every label at one cut
+// (pointer jumping), and the dense numbering of the groups of the labels in use. Used by rt_cut_kernel (region_tree.hip:
+// gcs_region_tree_cut), region_sweep_kernel (scoring.hip: gcs_region_sweep, gcs_region_sweep_under), cut_shapes_pixel_kernel (the tau
+// list alone) and cut_shapes_group_kernel (cut_shapes.hip: gcs_cut_shapes) and rp_cuts_kernel (region_props.hip:
+// gcs_region_props_cuts). Except rs_taus, which takes any workgroup, every function is called by ALL AG_THREADS threads of a
+// workgroup; the LDS arrays belong to the caller.
 #pragma once
 #include "common.h"
 
@@ -59,6 +62,17 @@ __device__ __forceinline__ int rs_tau(int alive, int R, int n_rows) {
     return (int)(want < 0 ? 0 : want > n_rows ? n_rows : want);
 }
 
+// s_tau[c] = tau of cut c, made non-decreasing (an entry of regions that is not below its predecessor repeats its predecessor's cut,
+// as in gcs_region_sweep, which keeps a running tau instead). Called by a whole workgroup of at least n_cuts threads, ends behind
+// a __syncthreads().
+__device__ __forceinline__ void rs_taus(const int32_t *__restrict__ regions, int n_cuts, int alive, int n_rows, int *s_tau) {
+    if ((int)threadIdx.x < n_cuts) s_tau[threadIdx.x] = rs_tau(alive, regions[threadIdx.x], n_rows);
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int c = 1; c < n_cuts; ++c) s_tau[c] = max(s_tau[c], s_tau[c - 1]);
+    __syncthreads();
+}
+
 // The group rep of every label with the rows below tau applied: s_root[q] = s_dk[q] names a row < tau ? its absorber : q, then
 // pointer jumping, ceil(log2 K) rounds (a chain has at most K - 1 links). Ends behind a __syncthreads().
 __device__ __forceinline__ void rs_group_reps(const unsigned *s_dk, unsigned short *s_root, int K, int tau) {
@@ -84,4 +98,35 @@ __device__ __forceinline__ void rs_group_reps(const unsigned *s_dk, unsigned sho
         }
         __syncthreads();
     }
+}
+
+// The groups of the labels in use (bit row s_used), numbered densely in increasing order of their rep: s_group[q] = the number of
+// label q's group, -1 for a label not in use. s_rep (the reps' bit row) and s_pref (reps below each word) are scratch of
+// ceil(K / 32) words each, no more than the workgroup has threads (a thread zeroes a word: K <= RS_K_MAX gives 128 <= AG_THREADS).
+// Ends behind a __syncthreads().
+__device__ __forceinline__ void rs_number_groups(const unsigned *s_used, const unsigned short *s_root, int K, unsigned *s_rep,
+                                                 unsigned *s_pref, short *s_group) {
+    const int tid = threadIdx.x, KW = (K + 31) >> 5;
+    if (tid < KW) s_rep[tid] = 0u;
+    __syncthreads();
+    for (int q = tid; q < K; q += AG_THREADS)
+        if ((s_used[q >> 5] >> (q & 31)) & 1u) {
+            const unsigned r = s_root[q];
+            atomicOr(&s_rep[r >> 5], 1u << (r & 31));
+        }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned acc = 0;
+        for (int w = 0; w < KW; ++w) {
+            s_pref[w] = acc;
+            acc += (unsigned)__popc(s_rep[w]);
+        }
+    }
+    __syncthreads();
+    for (int q = tid; q < K; q += AG_THREADS) {
+        const unsigned r = s_root[q];
+        const bool used = (s_used[q >> 5] >> (q & 31)) & 1u;
+        s_group[q] = used ? (short)(s_pref[r >> 5] + (unsigned)__popc(s_rep[r >> 5] & ((1u << (r & 31)) - 1u))) : (short)-1;
+    }
+    __syncthreads();
 }

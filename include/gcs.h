@@ -443,7 +443,8 @@ int gcs_superpixel_segment(const uint16_t *feats_canonical_dev, int B, int H, in
  *                                    (rows >= alive - 1) are (-1, -1) with cost 0. The tree does not depend on any R.
  *   gcs_region_tree_cut              one launch: the first max(0, alive - R) rows applied, the groups numbered 0, 1, ... in increasing order
  *                                    of their rep: labels_out_dev int32 [B][H][W] has min(alive, R) labels per image. labels_out_dev may
- *                                    BE labels_dev (in place); it must not overlap it otherwise.
+ *                                    BE labels_dev (in place); it must not overlap it otherwise. Any list is taken: a row that is not
+ *                                    0 <= a < b < K with both still reps at that step is skipped, as in gcs_region_sweep.
  * A pixel whose label is outside 0 .. K-1 is counted nowhere, is adjacent to nothing and leaves the cut as -1. feats_canonical_dev is
  * the [B][D][H][W] uint16 tensor of gcs_features_unpack. With K = 1 there are no rows: merges / costs pointers are not read.
  * GCS_EINVAL, with nothing launched: a NULL feats / labels / workspace / alive / labels_out pointer, a NULL merges pointer with K > 1,

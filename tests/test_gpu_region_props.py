@@ -136,6 +136,37 @@ def test_accumulator_width(torch_cuda, d):
     assert (sums[0, 1] == 0).all() and bbox[0].tolist() == [[0, 0, 63, 63], [64, 64, -1, -1]]
 
 
+# ---- the tile accumulator (csrc/label_tile.h) at its slot boundary, inside one launch
+
+def _stripes(h, w, extra=None):
+    """Column stripes x % 32 (32 labels in every full tile row: every slot taken, none missing), ``extra``: one pixel of label 32."""
+    lab = np.broadcast_to(np.arange(w, dtype=np.int32) % 32, (h, w)).copy()
+    if extra is not None:
+        lab[extra] = 32
+    return lab
+
+
+@pytest.mark.parametrize("d", [0, 2])
+@pytest.mark.parametrize("h,w", [(8, 32), (9, 33)])
+def test_tile_with_32_labels_beside_one_with_33(torch_cuda, h, w, d):
+    """B = 2: image 0's first tile holds exactly 32 labels (the LDS rows and boxes), image 1's the same and a 33rd label in one pixel
+    (the global rows), both in one launch; at 9 x 33 the second tiles are ragged in both directions."""
+    lab = np.stack([_stripes(h, w), _stripes(h, w, (5, 13))])
+    img, feats = _rand(h * w + d, 2, h, w, d)
+    sums, bbox, _ = _check_leaf(torch_cuda, lab, img, feats if d else None, 33)
+    assert sums[0, 32, 0] == 0 and sums[1, 32, 0] == 1 and bbox[1, 32].tolist() == [5, 13, 5, 13]
+
+
+def test_tile_of_one_label_at_full_range(torch_cuda):
+    """One 8 x 32 tile of one label, both features at 46339: every eight-lane sum is 8 * 46339, both LDS cells reach 256 * 46339."""
+    lab = np.zeros((1, 8, 32), np.int32)
+    img = np.full((1, 8, 32, 3), 255, np.uint8)
+    feats = np.full((1, 2, 8, 32), 46339, np.uint16)
+    sums, bbox, _ = _check_leaf(torch_cuda, lab, img, feats, 1)
+    assert sums[0, 0].tolist() == [256, 28 * 32, 496 * 8, 255 * 256, 255 * 256, 255 * 256, 46339 * 256, 46339 * 256]
+    assert bbox[0, 0].tolist() == [0, 0, 7, 31]
+
+
 # ---- the cuts
 
 def _cuts(torch, sums, bbox, merges, alive, regions, shape, rsum=None):
@@ -240,8 +271,8 @@ def test_cuts_of_the_librarys_own_trees_with_a_different_alive_per_image(torch_c
 
 
 def test_cuts_of_a_list_with_rows_that_do_not_count(torch_cuda):
-    """Rows with a = b, b >= K, an absorbed b, a dead a and (-1, -1) in the middle are skipped by rs_absorbers; gcs_region_tree_cut
-    takes the list with those rows cleared (it does not ask whether both are still reps), so ``group`` is held against that."""
+    """Rows with a = b, b >= K, an absorbed b, a dead a and (-1, -1) in the middle are skipped by rs_absorbers, the walk of every cut
+    kernel: ``group`` is held against gcs_region_tree_cut on the list with those rows cleared and on the raw list itself."""
     k = 24
     lab = _noise(21, 1, 15, 18, k)
     img, feats = _rand(22, 1, 15, 18, 1)
@@ -254,6 +285,7 @@ def test_cuts_of_a_list_with_rows_that_do_not_count(torch_cuda):
     for c, r in enumerate(regions):
         cut = _tree_cut(torch_cuda, lab, clean[None], [k], k, r)
         assert np.array_equal(group[c, 0][lab[0]], cut[0])
+        assert np.array_equal(group[c, 0][lab[0]], _tree_cut(torch_cuda, lab, bad[None], [k], k, r)[0])
     assert group[-1, 0].max() + 1 > 1                              # a forest: more than R = 1 groups, the others have no row
     assert so.shape[1] == sum(regions) and so[0, -1, 0] < lab.size
 

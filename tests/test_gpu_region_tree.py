@@ -483,3 +483,72 @@ def test_stats_table_at_32_labels_and_one_more(torch_cuda, buckets):
     x = np.random.default_rng(32).integers(0, 46341, (len(buckets), 3, 16, 64)).astype(np.uint16)
     refs = _check_tree(torch_cuda, x, lab, k, (1, 8, 4096))
     assert all(a == 81 for _, _, a in refs)
+
+
+# ---- the tile accumulator (csrc/label_tile.h) at its slot boundary, inside one launch
+
+def _stripes(h, w, extra=None):
+    """Column stripes x % 32 (32 labels in every full tile row: every slot taken, none missing), ``extra``: one pixel of label 32."""
+    lab = np.broadcast_to(np.arange(w, dtype=np.int32) % 32, (h, w)).copy()
+    if extra is not None:
+        lab[extra] = 32
+    return lab
+
+
+@pytest.mark.parametrize("h,w", [(8, 32), (9, 33)])
+def test_stats_tile_with_32_labels_beside_one_with_33(torch_cuda, h, w):
+    """B = 2, D = 2: image 0's first tile holds exactly 32 labels (the LDS rows), image 1's the same and a 33rd label in one pixel (the
+    global rows), both in one launch; at 9 x 33 the second tiles are ragged in both directions."""
+    lab = np.stack([_stripes(h, w), _stripes(h, w, (5, 13))])
+    x = np.random.default_rng(h * w).integers(0, 46340, (2, 2, h, w)).astype(np.uint16)
+    refs = _check_tree(torch_cuda, x, lab, 33, (1, 33))
+    assert [a for _, _, a in refs] == [32, 33]
+
+
+def test_stats_tile_of_one_label_at_full_range(torch_cuda):
+    """8 x 64, D = 2: the left tile is label 0 with every feature at 46339, so every eight-lane sum is 8 * 46339 and both LDS cells reach
+    256 * 46339; the right tile is label 1 at 0. The one merge costs 2 * 46339^2 * 256 exactly when label 0's mean is 46339."""
+    lab = np.zeros((1, 8, 64), np.int32)
+    lab[0, :, 32:] = 1
+    x = np.where(lab == 0, 46339, 0).astype(np.uint16)[:, None].repeat(2, axis=1)
+    (m, c, a), = _check_tree(torch_cuda, x, lab, 2, (1, 2))
+    assert a == 2 and m.tolist() == [[0, 1]] and int(c[0]) == 2 * 46339 ** 2 * 256
+
+
+# ---- the cut on lists outside the form gcs_region_tree writes: SPEC.md §16's row rule
+
+def test_cut_of_a_list_with_rows_that_do_not_count(torch_cuda):
+    """B = 2, 15 x 18, K = 24, alive 24 and 21: the balanced list with a = b, b >= K, an absorbed b, a dead a, (-1, -1) in the middle and
+    a label (6) that is the b of two well-formed rows with different a. The cut of the raw list == the restatement's cut of the list
+    with those rows cleared, every pixel, out-of-range labels (-1) included, out of place and in place."""
+    import contour_map_ref as cm
+    import region_props_ref as rp
+    torch, k = torch_cuda, 24
+    bad = cm.balanced(k).copy()
+    bad[1], bad[3], bad[5], bad[7], bad[9] = (4, 4), (2, k), bad[0], (bad[0][1], 23), (-1, -1)
+    assert bad[13].tolist() == [4, 6]
+    bad[14] = (0, 6)
+    clean = rp.counted(bad, k)
+    assert (clean[[1, 3, 5, 7, 9, 14]] == -1).all() and (clean >= 0).all(1).sum() == k - 1 - 6
+    lab = np.random.default_rng(24).integers(0, k, (2, 15, 18)).astype(np.int32)
+    for q in (3, 11, 19):
+        lab[1][lab[1] == q] = q + 1
+    lab[0, 0, 0], lab[0, 7, 9], lab[1, 14, 17], lab[1, 3, 3] = -1, k, 2 ** 30, -2 ** 31
+    alive = [24, 21]
+    assert [len(np.unique(l[(l >= 0) & (l < k)])) for l in lab] == alive
+    dev = (torch.from_numpy(lab).cuda(), torch.from_numpy(np.stack([bad, bad])).cuda(), torch.tensor(alive, dtype=torch.int32, device="cuda"))
+    for r in (24, 12, 6, 3, 1):
+        for in_place in (False, True):
+            got = _gpu_cut(torch, dev, k, r, in_place=in_place)
+            for i in range(2):
+                want = rt.cut(lab[i], clean, alive[i], r)
+                assert (want[(lab[i] < 0) | (lab[i] >= k)] == -1).all()
+                assert np.array_equal(got[i], want), (r, in_place, i, int((got[i] != want).sum()))
+    # K = 1: no list (a NULL pointer); label 0 stays 0, everything else is -1
+    lab1 = np.zeros((2, 5, 7), np.int32)
+    lab1[1, 0, 0], lab1[1, 4, 6] = 3, -1
+    dev1 = (torch.from_numpy(lab1).cuda(), None, torch.tensor([1, 1], dtype=torch.int32, device="cuda"))
+    for r, in_place in ((1, False), (5, True)):
+        got = _gpu_cut(torch, dev1, 1, r, in_place=in_place)
+        for i in range(2):
+            assert np.array_equal(got[i], rt.cut(lab1[i], np.zeros((0, 2), np.int32), 1, r))

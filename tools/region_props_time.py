@@ -6,6 +6,7 @@ the tree on connected regions (SPEC.md §18; K = the batch's largest node count 
     region_props_time.py time  [out.json] [--parent path/to/parent/libgcs.so]
     region_props_time.py trace [--parent path/to/parent/libgcs.so]   (under rocprofv3 --kernel-trace -f csv -d <dir> -o run --)
     region_props_time.py split <run_kernel_trace.csv> <out.json>
+    region_props_time.py same  <out.json> --parent path/to/parent/libgcs.so
 
 ``time``: every ``*_ms`` figure is the median of ``reps`` calls after ``warm`` warm-up calls, each call between two events on the
 stream, on device-resident inputs and outputs; per case ``<tree>_d<D>_``:
@@ -24,6 +25,11 @@ PARENT commit's library and through a second plan on the parent's library, the t
 leaf pass: its rt_stats_kernel does the same accumulation), then the three calls at D = 72, first on the superpixel tree, then on
 the component tree; ``split`` adds the median time of each kernel in each of the two phases to the JSON, and ``leaf_ratio`` =
 rp_stats_kernel / rt_stats_kernel per phase.
+``same``: gcs_region_props, gcs_region_props_cuts (both per case) and gcs_region_tree_cut at R = 8 (per tree) through this build and
+twice through the PARENT's library on the SAME device buffers in one process, the three taking turns call by call, SAME_REPS calls
+after ``warm``: separate ``time`` runs place their buffers independently, which moves a latency-bound kernel by a few per cent
+whichever library runs it. Adds ``same_buffers`` to the JSON: per figure parent, parent2, this, the parent's min and max, the
+spread max(|parent - parent2|, parent max - min) and ``inside``.
 """
 import csv
 import json
@@ -38,6 +44,7 @@ from contour_map_time import REGIONS  # noqa: E402
 
 KERNELS = ("rt_stats_kernel", "rp_fill_kernel", "rp_stats_kernel", "rp_cuts_kernel", "rp_paint_kernel")
 PHASES = ("superpixels", "components")
+SAME_REPS = 60
 PERCUT_REPS = 7                                          # the caller's route of today: hundreds of launches per call
 
 
@@ -211,6 +218,49 @@ def trace_main(parent=None):
                 torch.cuda.current_stream().synchronize()
 
 
+def same_main(out_path, parent):
+    sys.path.insert(0, ROOT)
+    import torch
+    p1, p2 = _parent_plans(parent, dict(n_superpixels=N, spatial_weight=LAM, **BANK))
+    imgs = _batch(torch)
+    cases = _cases(torch, imgs)
+    same = {}
+
+    def turns(key, call):
+        """``call(ops)`` -> a closure; the three plans' closures take turns."""
+        fns = {"parent": call(p1.ops), "this": call(c["seg"].ops), "parent2": call(p2.ops)}
+        times = {who: [] for who in fns}
+        for rnd in range(WARM + SAME_REPS):
+            for who, fn in fns.items():
+                t = _timed(torch, fn)
+                if rnd >= WARM:
+                    times[who].append(t)
+        m = {who: statistics.median(ts) for who, ts in times.items()}
+        lo, hi = min(times["parent"]), max(times["parent"])
+        spread = max(abs(m["parent"] - m["parent2"]), hi - lo)
+        same[key] = dict(m, parent_min=lo, parent_max=hi, spread=spread, inside=abs(m["this"] - m["parent"]) <= spread)
+        print(key, json.dumps(same[key]), flush=True)
+
+    for name, c in cases.items():
+        k = c["k"]
+        for d in (0, 72):
+            buf = _buffers(torch, c, d)
+            canon = c["canon"] if d else None
+            turns("%s_d%d_props_ms" % (name, d),
+                  lambda ops: lambda: ops.region_props(c["lab"], imgs, canon, BATCH, H, W, k, buf["sums"], buf["bbox"]))
+            turns("%s_d%d_cuts_ms" % (name, d),
+                  lambda ops: lambda: ops.region_props_cuts(buf["sums"], buf["bbox"], c["merges"], c["alive"], buf["regs"], BATCH, H, W, k,
+                                                            buf["group"], buf["sums_out"], buf["bbox_out"]))
+            del buf
+            torch.cuda.empty_cache()
+        out = torch.empty_like(c["lab"])
+        turns("%s_cut_ms" % name, lambda ops: lambda: ops.region_tree_cut(c["lab"], c["merges"], c["alive"], BATCH, H, W, k, 8, out))
+    res = json.load(open(out_path)) if os.path.exists(out_path) else {}
+    res["same_buffers"] = dict(same, reps=SAME_REPS, warm=WARM)
+    with open(out_path, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def split_main(trace, out_path):
     with open(trace) as f:
         ks = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for r in csv.DictReader(f))
@@ -237,5 +287,7 @@ if __name__ == "__main__":
         trace_main(parent)
     elif mode == "split":
         split_main(paths[0], paths[1])
+    elif mode == "same":
+        same_main(paths[0], parent)
     else:
         time_main(paths[0] if paths else None, parent)
