@@ -45,6 +45,10 @@ density and regions - of every listed R from the same tree and contour map (SPEC
 `--tree-nodes components` beside `--regions` (with or without `--sweep`): the tree on the connected regions of the superpixel map
 (SPEC.md §18: `Segmenter(tree_nodes="components")`): every cut at R is R connected regions, `--min-region-size` goes into the node
 map instead of running behind every cut, and the sweeps describe the delivered maps.
+`--tree-nodes clusters [--k K]` beside `--regions` (with or without `--sweep`; no `--superpixels`): the tree on the connected regions
+of the k-means map of K clusters (SPEC.md §21: `Segmenter(tree_nodes="clusters", k=K)`, default K = 16), the rest as for `components`
+(the n and lambda columns print 0): `--tree-nodes clusters --k 16 --regions 4,6,8,12,16,32 --sweep --agreement --reference-metrics
+--n-orient 5 --color-weight 0.125 --chroma-gain 4` prints the mode's table of `DESIGN.md` §7 from one tree per batch.
 """
 import os
 import sys
@@ -152,7 +156,16 @@ def superpixel_row(n, lam, n_orient, cw, g, merge):
         float(np.mean([r["regions"] for r in rows]))))
 
 
-def region_rows(n, lam, n_orient, cw, g, merge, regions, tree_nodes="superpixels"):
+def region_plan(n, lam, n_orient, cw, g, tree_nodes, k, m=0):
+    """The plan of `--regions`: on superpixels (SPEC.md §14, §18) or, with `--tree-nodes clusters`, on the k-means map (§21)."""
+    from gabor_color_image_segmentation_amd import Segmenter
+    if tree_nodes == "clusters":
+        return Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, k=k, tree_nodes=tree_nodes, min_region_size=m)
+    return Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, n_superpixels=n, spatial_weight=lam, tree_nodes=tree_nodes,
+                     min_region_size=m)
+
+
+def region_rows(n, lam, n_orient, cw, g, merge, regions, tree_nodes="superpixels", k=16):
     import numpy as np
     import torch
     from gabor_color_image_segmentation_amd import Segmenter, superpixel_grid
@@ -163,14 +176,13 @@ def region_rows(n, lam, n_orient, cw, g, merge, regions, tree_nodes="superpixels
     truth = PackedTruth(os.path.join(gold, "bsd500_truth.npz"))
     ids = [str(i) for i in pack["ids"]]
     rows = {r: [] for r in regions}
-    components = tree_nodes == "components"
-    seg = Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, n_superpixels=n, spatial_weight=lam)
+    components = tree_nodes in ("components", "clusters")
+    seg = None if components else region_plan(n, lam, n_orient, cw, g, "superpixels", k)
     for shape in sorted({pack["img_" + i].shape[:2] for i in ids}):
         group = [i for i in ids if pack["img_" + i].shape[:2] == shape]
-        m = superpixel_grid(shape[0], shape[1], n)[0] ** 2 // 4 if merge == "auto" else int(merge)
-        if components:                                   # m is part of the node map (SPEC.md §18): nothing runs behind a cut
-            seg = Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, n_superpixels=n, spatial_weight=lam,
-                            tree_nodes=tree_nodes, min_region_size=m)
+        m = superpixel_grid(shape[0], shape[1], n or 300)[0] ** 2 // 4 if merge == "auto" else int(merge)
+        if components:                                   # m is part of the node map (SPEC.md §18, §21): nothing runs behind a cut
+            seg = region_plan(n, lam, n_orient, cw, g, tree_nodes, k, m)
             m = 0
         labels, merges, _, alive = seg.region_tree_device(torch.from_numpy(np.stack([pack["img_" + i] for i in group])).cuda())
         dt = truth.to_device(group)
@@ -189,7 +201,7 @@ def region_rows(n, lam, n_orient, cw, g, merge, regions, tree_nodes="superpixels
             "%.4f" % float(np.mean([x[k] for x in rows[r]])) for k in keys), float(np.mean([x["regions"] for x in rows[r]]))))
 
 
-def sweep_rows(n, lam, n_orient, cw, g, regions, agreement=False, reference=False, tree_nodes="superpixels"):
+def sweep_rows(n, lam, n_orient, cw, g, regions, agreement=False, reference=False, tree_nodes="superpixels", k=16):
     import numpy as np
     import torch
     from gabor_color_image_segmentation_amd import Segmenter
@@ -202,7 +214,7 @@ def sweep_rows(n, lam, n_orient, cw, g, regions, agreement=False, reference=Fals
     pack = np.load(os.path.join(gold, "bsd_val_images.npz"))
     truth = PackedTruth(os.path.join(gold, "bsd500_truth.npz"))
     ids = [str(i) for i in pack["ids"]]
-    seg = Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, n_superpixels=n, spatial_weight=lam, tree_nodes=tree_nodes)
+    seg = region_plan(n, lam, n_orient, cw, g, tree_nodes, k)
     rows, agree, ref = [], [], []
     for shape in sorted({pack["img_" + i].shape[:2] for i in ids}):
         group = [i for i in ids if pack["img_" + i].shape[:2] == shape]
@@ -236,19 +248,26 @@ def sweep_rows(n, lam, n_orient, cw, g, regions, agreement=False, reference=Fals
 
 
 if __name__ == '__main__':
-    if "--superpixels" in sys.argv:
+    clusters = "--tree-nodes" in sys.argv and sys.argv[sys.argv.index("--tree-nodes") + 1] == "clusters"
+    if "--superpixels" in sys.argv or (clusters and "--regions" in sys.argv):
         def one(name, conv, default):
             return conv(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
+        if clusters and "--superpixels" in sys.argv:
+            sys.exit("--tree-nodes clusters takes the k-means map: leave --superpixels out")
+        if clusters:                                     # (no superpixel stage: its two columns print 0)
+            sys.argv += ["--superpixels", "0", "--spatial-weight", "0"]
         if "--regions" in sys.argv and "--sweep" in sys.argv:
             sweep_rows(one("--superpixels", int, 300), one("--spatial-weight", int, 576), one("--n-orient", int, 6),
                        one("--color-weight", float, 0.0), one("--chroma-gain", int, 0),
                        [int(v) for v in one("--regions", str, "8").split(",")], agreement="--agreement" in sys.argv,
-                       reference="--reference-metrics" in sys.argv, tree_nodes=one("--tree-nodes", str, "superpixels"))
+                       reference="--reference-metrics" in sys.argv, tree_nodes=one("--tree-nodes", str, "superpixels"),
+                       k=one("--k", int, 16))
             sys.exit(0)
         if "--regions" in sys.argv:
             region_rows(one("--superpixels", int, 300), one("--spatial-weight", int, 576), one("--n-orient", int, 6),
                         one("--color-weight", float, 0.0), one("--chroma-gain", int, 0), one("--min-region-size", str, "0"),
-                        [int(v) for v in one("--regions", str, "8").split(",")], one("--tree-nodes", str, "superpixels"))
+                        [int(v) for v in one("--regions", str, "8").split(",")], one("--tree-nodes", str, "superpixels"),
+                        one("--k", int, 16))
             sys.exit(0)
         superpixel_row(one("--superpixels", int, 300), one("--spatial-weight", int, 576), one("--n-orient", int, 6),
                        one("--color-weight", float, 0.0), one("--chroma-gain", int, 0), one("--min-region-size", str, "0"))

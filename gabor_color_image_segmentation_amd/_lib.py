@@ -79,6 +79,7 @@ SIGNATURES = {
     "gcs_superpixel_segment": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "gcs_region_tree_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "gcs_region_tree": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "gcs_region_tree_slab": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "gcs_region_tree_cut": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "gcs_region_tree_contours_workspace_bytes": (_sz, [_i, _i]),
     "gcs_region_tree_contours": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),

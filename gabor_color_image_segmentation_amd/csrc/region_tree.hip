@@ -9,6 +9,10 @@
 //                       [D sums, n]; a tile that sees more than 32 labels adds straight into the global rows (slow, exact).
 //                       Adjacency: a pixel whose right / lower neighbour carries another in-range label sets bits (a, b) and (b, a)
 //                       (an atomic OR only when the bit is not seen set: every later pixel of the same border reads and skips).
+//   rt_stats_slab_kernel  the same tile, labels, adjacency and accumulator with the values read from the FEATURE SLAB (SPEC.md §21,
+//                       gcs_region_tree_slab): a pixel locates its block and slot once (gcs_locate), then steps plane by plane through
+//                       its tile, every level at its own resolution (the 2^L x 2^L pixels of a level-L slot read the same bytes and
+//                       each adds the value to its own label); sums and bits equal rt_stats_kernel's on gcs_features_unpack of the slab.
 //   rt_merge_kernel     ONE workgroup of 1024 threads per image runs every round (the trip count is data, so the loop lives here):
 //                       pick (a wave per node whose neighbourhood changed: it walks the node's adjacency row, lanes over the planes of a cost), mutual pairs,
 //                       rank of every pair in (cost, rep) order = its row of the merge list, merge (sums, mean, adjacency row OR),
@@ -23,6 +27,7 @@
 
 #include "common.h"
 #include "label_tile.h"
+#include "slab_slots.h"
 #include "tree_cuts.h"
 
 namespace {
@@ -63,12 +68,15 @@ __device__ __forceinline__ void rt_edge(unsigned *adj, int KW, int a, int b) {
     if (!(rt_ld(wb) & bb)) atomicOr(wb, bb);
 }
 
-__global__ __launch_bounds__(LT_THREADS) void rt_stats_kernel(RtArgs A) {
-    extern __shared__ __attribute__((aligned(16))) unsigned rt_smem[];
-    const int b = (int)blockIdx.z, D = A.D, E = D + 1, K = A.K;
-    unsigned *s_acc = rt_smem;                                             // [LT_SLOTS][E]
-    int *s_keys = reinterpret_cast<int *>(s_acc + LT_SLOTS * E);          // [LT_SLOTS] label of the slot, -1: free
-    int *s_over = s_keys + LT_SLOTS;                                       // more labels than slots
+// What the two statistics kernels do before they read a value: the tile accumulator of label_tile.h cleared, this thread's pixel
+// (clamped past the edge) and label, the adjacency bits of its right and lower pair, its label's slot. Returns the slot; the slots
+// and *s_over are settled for the workgroup (a __syncthreads() has passed).
+struct RtPixel {
+    int y, x, l;
+    bool in;                                 // inside the image with a label in 0 .. K-1: a label outside is counted nowhere
+};
+__device__ __forceinline__ int rt_tile_begin(const RtArgs &A, int b, unsigned *s_acc, int *s_keys, int *s_over, RtPixel *px) {
+    const int E = A.D + 1, K = A.K;
     lt_clear(s_acc, E, s_keys, s_over);
     __syncthreads();
     const size_t hw = (size_t)A.H * A.W;
@@ -76,7 +84,7 @@ __global__ __launch_bounds__(LT_THREADS) void rt_stats_kernel(RtArgs A) {
     const bool valid = lt_pixel(A.H, A.W, &y, &x);
     const int *lab = A.labels + (size_t)b * hw + (size_t)y * A.W + x;
     const int l = *lab;
-    const bool in = valid && (unsigned)l < (unsigned)K;                    // a label outside 0 .. K-1 is counted nowhere
+    const bool in = valid && (unsigned)l < (unsigned)K;
     unsigned *adj = A.adj + (size_t)b * K * A.KW;
     if (in) {
         if (x + 1 < A.W) {
@@ -90,6 +98,21 @@ __global__ __launch_bounds__(LT_THREADS) void rt_stats_kernel(RtArgs A) {
     }
     const int slot = lt_claim(s_keys, s_over, l, in);
     __syncthreads();
+    px->y = y, px->x = x, px->l = l, px->in = in;
+    return slot;
+}
+
+__global__ __launch_bounds__(LT_THREADS) void rt_stats_kernel(RtArgs A) {
+    extern __shared__ __attribute__((aligned(16))) unsigned rt_smem[];
+    const int b = (int)blockIdx.z, D = A.D, E = D + 1, K = A.K;
+    unsigned *s_acc = rt_smem;                                             // [LT_SLOTS][E]
+    int *s_keys = reinterpret_cast<int *>(s_acc + LT_SLOTS * E);          // [LT_SLOTS] label of the slot, -1: free
+    int *s_over = s_keys + LT_SLOTS;                                       // more labels than slots
+    RtPixel p;
+    const int slot = rt_tile_begin(A, b, s_acc, s_keys, s_over, &p);
+    const int y = p.y, x = p.x, l = p.l;
+    const bool in = p.in;
+    const size_t hw = (size_t)A.H * A.W;
     const uint16_t *px = A.feats + (size_t)b * D * hw + (size_t)y * A.W + x;
     u64 *g_sums = A.sums + (size_t)b * K * E;
     if (*s_over) {                                                         // (uniform over the workgroup)
@@ -103,6 +126,67 @@ __global__ __launch_bounds__(LT_THREADS) void rt_stats_kernel(RtArgs A) {
     const int same = lt_agree(slot, in);
     unsigned *row = s_acc + (in ? slot : 0) * E;
     for (int d = 0; d < E; ++d) lt_add(row + d, d < D ? px[(size_t)d * hw] : 1u, same, in);
+    __syncthreads();
+    lt_flush(s_acc, s_keys, E, g_sums);
+}
+
+// The D values of one pixel in the slab of its image, handed to f(column of the sums row = logical feature, value): physical plane
+// order (level, channel, filter in level), a plane step inside the tile is a constant per level. Split slab: low byte, MID nibble
+// and, in a tile whose level flag is set, TOP nibble (a plane is a multiple of the nibble group: byte += half a plane, same shift).
+template <class F>
+__device__ __forceinline__ void rt_slab_walk(const GcsLayout &lo, const unsigned char *img, int y, int x, F f) {
+    int blk, iy, ix;
+    gcs_locate(lo, y, x, blk, iy, ix);
+    const unsigned tile = (unsigned)(blk >> 2), q = (unsigned)(blk & 3);
+    for (int L = 0; L < lo.n_levels; ++L) {
+        const unsigned side = 8u >> L, npl = (unsigned)KP_TP >> (2 * L);
+        const int FL = lo.FL[L], col0 = 2 * L * lo.n_orient;
+        if (lo.split) {
+            unsigned slot = tile * (unsigned)lo.S + (unsigned)lo.sl0[L] + ((unsigned)iy >> L) * 4u * side + q * side + ((unsigned)ix >> L);
+            unsigned nb;
+            int sh;
+            sm_nibble(L, slot, nb, sh);
+            const bool top = img[lo.flag_off + 4u * tile + (unsigned)L] != 0;
+            for (int c = 0; c < 3; ++c)
+                for (int fl = 0; fl < FL; ++fl, slot += npl, nb += npl >> 1) {
+                    unsigned v = (img[slot] ^ 0x80u) | (((unsigned)img[lo.mid_off + nb] >> sh & 15u) << 8);
+                    if (top) v |= ((unsigned)img[lo.top_off + nb] >> sh & 15u) << 12;
+                    f(c * lo.F + col0 + fl, v);
+                }
+        } else {
+            const unsigned char *p = img + (size_t)tile * lo.tile_bytes + lo.off[L] +
+                                     (size_t)(q * side * side + ((unsigned)iy >> L) * side + ((unsigned)ix >> L)) * 2;
+            for (int c = 0; c < 3; ++c)
+                for (int fl = 0; fl < FL; ++fl, p += 2 * npl)
+                    f(c * lo.F + col0 + fl, (unsigned)*reinterpret_cast<const uint16_t *>(p) ^ 0x8080u);
+        }
+    }
+}
+
+__global__ __launch_bounds__(LT_THREADS) void rt_stats_slab_kernel(RtArgs A, GcsLayout lo, const unsigned char *slab) {
+    extern __shared__ __attribute__((aligned(16))) unsigned rt_smem[];
+    const int b = (int)blockIdx.z, D = A.D, E = D + 1, K = A.K;
+    unsigned *s_acc = rt_smem;                                             // [LT_SLOTS][E]
+    int *s_keys = reinterpret_cast<int *>(s_acc + LT_SLOTS * E);          // [LT_SLOTS] label of the slot, -1: free
+    int *s_over = s_keys + LT_SLOTS;                                       // more labels than slots
+    RtPixel p;
+    const int slot = rt_tile_begin(A, b, s_acc, s_keys, s_over, &p);
+    const int y = p.y, x = p.x, l = p.l;
+    const bool in = p.in;
+    const unsigned char *img = slab + (size_t)b * (size_t)lo.img_bytes;    // (a clamped pixel past the edge reads inside the image)
+    u64 *g_sums = A.sums + (size_t)b * K * E;
+    if (*s_over) {                                                         // (uniform over the workgroup)
+        if (in) {
+            u64 *row = g_sums + (size_t)l * E;
+            rt_slab_walk(lo, img, y, x, [&](int d, unsigned v) { atomicAdd(row + d, (u64)v); });
+            atomicAdd(row + D, 1ull);
+        }
+        return;
+    }
+    const int same = lt_agree(slot, in);
+    unsigned *row = s_acc + (in ? slot : 0) * E;
+    rt_slab_walk(lo, img, y, x, [&](int d, unsigned v) { lt_add(row + d, v, same, in); });
+    lt_add(row + D, 1u, same, in);
     __syncthreads();
     lt_flush(s_acc, s_keys, E, g_sums);
 }
@@ -504,6 +588,34 @@ extern "C" size_t gcs_region_tree_workspace_bytes(int B, int H, int W, int D, in
     return (size_t)B * (rt_align(k * (D + 1) * 8) + rt_align(k * kw * 4) + rt_align(k * D * 2));
 }
 
+// The three launches of SPEC.md §14. `lo`: NULL = statistics from the canonical tensor A.feats, else from the slab `slab` of that layout.
+static int rt_enqueue(RtArgs A, const GcsLayout *lo, const unsigned char *slab, void *workspace, gcs_stream_t stream) {
+    const int B = A.B, H = A.H, W = A.W, D = A.D, K = A.K;
+    A.KW = (K + 31) / 32;
+    const size_t k = (size_t)K;
+    const size_t sums_b = rt_align(k * (D + 1) * 8), adj_b = rt_align(k * A.KW * 4);
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    A.sums = reinterpret_cast<u64 *>(ws);                                  // image b's rows: [b][K][D + 1] (dense; the padding sits behind all)
+    A.adj = reinterpret_cast<unsigned *>(ws + (size_t)B * sums_b);
+    A.mean = reinterpret_cast<uint16_t *>(ws + (size_t)B * (sums_b + adj_b));
+    const size_t n16 = (size_t)B * (sums_b + adj_b) / 16;
+    const int zgrid = (int)std::min<size_t>((n16 + 255) / 256, (size_t)gcs_cu_count() * 8);
+    hipLaunchKernelGGL(rt_zero_kernel, dim3(zgrid), dim3(256), 0, stream, reinterpret_cast<uint4 *>(ws), n16);
+    GCS_CHECK_LAUNCH("gcs_region_tree (zero)");
+    const dim3 tiles((W + LT_TW - 1) / LT_TW, (H + LT_TH - 1) / LT_TH, B);
+    const size_t tile_lds = (size_t)LT_SLOTS * (D + 1) * 4 + LT_SLOTS * 4 + 16;
+    if (lo)
+        hipLaunchKernelGGL(rt_stats_slab_kernel, tiles, dim3(LT_THREADS), tile_lds, stream, A, *lo, slab);
+    else
+        hipLaunchKernelGGL(rt_stats_kernel, tiles, dim3(LT_THREADS), tile_lds, stream, A);
+    GCS_CHECK_LAUNCH("gcs_region_tree (statistics)");
+    const size_t state = rt_state_bytes(K), with_mean = state + k * D * 2;
+    const int mean_in_lds = with_mean <= RT_LDS_MAX ? 1 : 0;
+    hipLaunchKernelGGL(rt_merge_kernel, dim3(B), dim3(RT_T), mean_in_lds ? with_mean : state, stream, A, mean_in_lds);
+    GCS_CHECK_LAUNCH("gcs_region_tree (merge)");
+    return GCS_OK;
+}
+
 extern "C" int gcs_region_tree(const uint16_t *feats, const int32_t *labels, int B, int H, int W, int D, int K, void *workspace,
                                int32_t *merges_out, uint64_t *costs_out, int32_t *alive_out, gcs_stream_t stream) {
     if (!feats || !labels || !workspace || !alive_out || (K > 1 && !merges_out))
@@ -512,26 +624,25 @@ extern "C" int gcs_region_tree(const uint16_t *feats, const int32_t *labels, int
         return gcs_fail(GCS_EINVAL, "gcs_region_tree: bad shape (1 <= B <= 65535, 1 <= H, W <= 4096, 1 <= D <= 207, 1 <= K <= 4096)");
     RtArgs A{};
     A.feats = feats, A.labels = labels;
-    A.B = B, A.H = H, A.W = W, A.D = D, A.K = K, A.KW = (K + 31) / 32;
-    const size_t k = (size_t)K;
-    const size_t sums_b = rt_align(k * (D + 1) * 8), adj_b = rt_align(k * A.KW * 4);
-    unsigned char *ws = static_cast<unsigned char *>(workspace);
-    A.sums = reinterpret_cast<u64 *>(ws);                                  // image b's rows: [b][K][D + 1] (dense; the padding sits behind all)
-    A.adj = reinterpret_cast<unsigned *>(ws + (size_t)B * sums_b);
-    A.mean = reinterpret_cast<uint16_t *>(ws + (size_t)B * (sums_b + adj_b));
+    A.B = B, A.H = H, A.W = W, A.D = D, A.K = K;
     A.merges = merges_out, A.costs = reinterpret_cast<u64 *>(costs_out), A.alive = alive_out;
-    const size_t n16 = (size_t)B * (sums_b + adj_b) / 16;
-    const int zgrid = (int)std::min<size_t>((n16 + 255) / 256, (size_t)gcs_cu_count() * 8);
-    hipLaunchKernelGGL(rt_zero_kernel, dim3(zgrid), dim3(256), 0, stream, reinterpret_cast<uint4 *>(ws), n16);
-    GCS_CHECK_LAUNCH("gcs_region_tree (zero)");
-    const dim3 tiles((W + LT_TW - 1) / LT_TW, (H + LT_TH - 1) / LT_TH, B);
-    hipLaunchKernelGGL(rt_stats_kernel, tiles, dim3(LT_THREADS), (size_t)LT_SLOTS * (D + 1) * 4 + LT_SLOTS * 4 + 16, stream, A);
-    GCS_CHECK_LAUNCH("gcs_region_tree (statistics)");
-    const size_t state = rt_state_bytes(K), with_mean = state + k * D * 2;
-    const int mean_in_lds = with_mean <= RT_LDS_MAX ? 1 : 0;
-    hipLaunchKernelGGL(rt_merge_kernel, dim3(B), dim3(RT_T), mean_in_lds ? with_mean : state, stream, A, mean_in_lds);
-    GCS_CHECK_LAUNCH("gcs_region_tree (merge)");
-    return GCS_OK;
+    return rt_enqueue(A, nullptr, nullptr, workspace, stream);
+}
+
+extern "C" int gcs_region_tree_slab(const uint16_t *feats_slab, const int32_t *labels, int B, int H, int W, int n_scales, int n_orient,
+                                    int K, void *workspace, int32_t *merges_out, uint64_t *costs_out, int32_t *alive_out,
+                                    gcs_stream_t stream) {
+    if (!feats_slab || !labels || !workspace || !alive_out || (K > 1 && !merges_out))
+        return gcs_fail(GCS_EINVAL, "gcs_region_tree_slab: NULL pointer");
+    GcsLayout lo;
+    if (!rt_shape_ok(B, H, W, K) || !gcs_make_layout(H, W, n_scales, n_orient, &lo) || lo.D > RT_D_MAX)
+        return gcs_fail(GCS_EINVAL, "gcs_region_tree_slab: bad shape (1 <= B <= 65535, 1 <= H, W <= 4096, a bank of at most 207 "
+                                    "features, 1 <= K <= 4096)");
+    RtArgs A{};
+    A.labels = labels;
+    A.B = B, A.H = H, A.W = W, A.D = lo.D, A.K = K;
+    A.merges = merges_out, A.costs = reinterpret_cast<u64 *>(costs_out), A.alive = alive_out;
+    return rt_enqueue(A, &lo, reinterpret_cast<const unsigned char *>(feats_slab), workspace, stream);
 }
 
 extern "C" int gcs_region_tree_cut(const int32_t *labels, const int32_t *merges, const int32_t *alive, int B, int H, int W, int K,

@@ -444,6 +444,20 @@ class HipOps:
                    "gcs_region_tree")
 
     @_on_device
+    def region_tree_slab(self, feats, labels, b, h, w, K, workspace, merges, costs, alive):
+        """``region_tree`` with the node statistics taken from the feature slab ``feats`` itself (SPEC.md §21): no canonical tensor.
+        Same buffers, same results bit for bit. Three launches, capturable."""
+        torch, K = self.torch, int(K)
+        self._need_tree(b, h, w, K, merges, alive, labels=labels)
+        self._need(costs, torch.int64, (b, K - 1), "costs must be a contiguous (B, K - 1) int64 tensor")
+        if feats is None or feats.numel() * feats.element_size() < self.lib.gcs_feature_slab_bytes(b, h, w, *self._bk):
+            raise ValueError("feats must be the feature slab of this batch, shape and bank")
+        _lib.check(self.lib.gcs_region_tree_slab(feats.data_ptr(), labels.data_ptr(), b, h, w, *self._bk, K, workspace.data_ptr(),
+                                                 merges.data_ptr() if K > 1 else None,
+                                                 None if costs is None or K == 1 else costs.data_ptr(), alive.data_ptr(),
+                                                 self._stream()), "gcs_region_tree_slab")
+
+    @_on_device
     def region_tree_cut(self, labels, merges, alive, b, h, w, K, R, out):
         """The cut of SPEC.md §14 at ``R``: ``out`` (B,H,W) int32 (it may be ``labels``) gets min(alive, R) labels per image. One
         launch, capturable."""
@@ -766,17 +780,20 @@ def _check_regions(n_regions, n_superpixels):
     if r is None or not (0 <= r <= REGIONS_MAX):
         raise ValueError(f"n_regions must be the integer 0 (off) or 1..{REGIONS_MAX}, got {n_regions!r}")
     if r > 0 and n_superpixels == 0:
-        raise ValueError("n_regions > 0 merges superpixels: it needs n_superpixels > 0")
+        raise ValueError('n_regions > 0 merges superpixels: it needs n_superpixels > 0 (or tree_nodes = "clusters", SPEC.md §21)')
     return r
 
 
 def _check_tree_nodes(tree_nodes, n_superpixels):
-    """SPEC.md §18 parameter: "superpixels" (the tree on the raw §13 map) or "components" (on its connected regions; only on top of
-    the superpixel stage). Returns True for "components"."""
-    if tree_nodes not in ("superpixels", "components"):
-        raise ValueError(f'tree_nodes must be "superpixels" or "components", got {tree_nodes!r}')
+    """SPEC.md §18 / §21 parameter: "superpixels" (the tree on the raw §13 map), "components" (on its connected regions; only on top
+    of the superpixel stage) or "clusters" (on the connected regions of the k-means map; only without the superpixel stage).
+    Returns True for "components"."""
+    if not isinstance(tree_nodes, str) or tree_nodes not in ("superpixels", "components", "clusters"):
+        raise ValueError(f'tree_nodes must be "superpixels", "components" or "clusters", got {tree_nodes!r}')
     if tree_nodes == "components" and n_superpixels == 0:
         raise ValueError('tree_nodes = "components" takes the components of the superpixel map: it needs n_superpixels > 0')
+    if tree_nodes == "clusters" and n_superpixels > 0:
+        raise ValueError('tree_nodes = "clusters" takes the components of the k-means map: it needs n_superpixels = 0')
     return tree_nodes == "components"
 
 
@@ -842,9 +859,10 @@ def lloyd(ops, feats, b, h, w, k, n_iter, mode, labels, partials, cent, sums, di
 # What the per-batch step needs to know of a plan, made once in Segmenter.__init__ (``colour``, ``smooth``, ``position``: is the
 # stage on). The two pieces of the step take it, the ops, a workspace and the debug switches as arguments and never the
 # Segmenter: a graph entry holds them, and an entry that held its plan would be a reference cycle (see _segment_small).
-# ``components``: SPEC.md §18 is on (then ``min_size`` = the plan's min_region_size, the m of the node map).
+# ``components``: SPEC.md §18 is on (then ``min_size`` = the plan's min_region_size, the m of the node map); ``clusters``: SPEC.md §21
+# is on (the same m).
 _StepOptions = collections.namedtuple("_StepOptions", "k n_iter colour smooth position n_superpixels spatial_weight n_regions "
-                                                      "components min_size")
+                                                      "components min_size clusters", defaults=(False,))
 
 
 def _opponent(ops, imgs, colour):
@@ -887,13 +905,13 @@ def _stage_buffers(ops, opt, ws, key, b, h, w):
     5 MB of workspace per image at D = 72, 0.32 GB for a batch of 64) join a workspace: at a stage's first use, or up front for a
     graph entry. Returns them. A stage that is off leaves no key."""
     if key not in ws:
-        _, ny, nx = superpixel_grid(h, w, opt.n_superpixels)
+        _, ny, nx = superpixel_grid(h, w, opt.n_superpixels) if opt.n_superpixels else (0, 0, 0)
         if key == "sp":
             ws[key] = ops.superpixel_buffers(b, h, w, opt.n_superpixels)
         elif key == "nd":
             ws[key] = ops.region_nodes_buffers(b, h, w)
         else:
-            ws[key] = ops.region_tree_buffers(b, h, w, NODES_MAX if opt.components else ny * nx)
+            ws[key] = ops.region_tree_buffers(b, h, w, NODES_MAX if opt.components or opt.clusters else ny * nx)
     return ws[key]
 
 
@@ -907,13 +925,34 @@ def _step_cluster(ops, opt, ws, out, b, h, w, mode, debug, dist_group=None, rows
     says (tree and cut at ``n_regions`` when that is on), True = the tree without a cut (it stays in ``ws["rt"]``), False = no
     tree. With ``tree_nodes = "components"`` (SPEC.md §18) the §13 map goes to the stage's own buffer, its node map to the output,
     and tree and cut run on that, the tree at K_cap; ``nodes=False`` leaves the §13 map as it is. A uint8 ``out`` is narrowed from
-    the int32 map of the workspace (a graph entry)."""
+    the int32 map of the workspace (a graph entry). With ``tree_nodes = "clusters"`` (SPEC.md §21) the Lloyd loop writes its int32
+    map to the node stage's own buffer, its node map goes to the output, and the tree reads its statistics from the slab
+    (``region_tree_slab``: no canonical tensor), at K_cap; ``tree`` as above."""
     if opt.n_superpixels == 0:
-        raster = out if rows is None and hasattr(ops, "assign_raster") else None      # the last pass writes the raster map itself
+        ndws = raw = n_nodes = None
+        if opt.clusters:
+            ndws, raw, n_nodes = _stage_buffers(ops, opt, ws, "nd", b, h, w)
+        out32 = out
+        if opt.clusters and out.dtype != _torch().int32:   # a uint8 result is narrowed from an int32 map the workspace keeps
+            if "out32" not in ws:
+                ws["out32"] = _torch().empty((b, h, w), dtype=_torch().int32, device=out.device)
+            out32 = ws["out32"]
+        km = raw if opt.clusters else out
+        raster = km if rows is None and hasattr(ops, "assign_raster") else None       # the last pass writes the raster map itself
         lloyd(ops, ws["feats"], b, h, w, opt.k, opt.n_iter, mode, ws["labels"], ws["partials"], ws["cent"], ws["sums"],
               dist_group, rows=rows, init=init, raster=raster, debug=debug, fold=ws.get("fold"))
         if raster is None:
-            ops.labels_widen(ws["labels"], b, h, w, out)
+            ops.labels_widen(ws["labels"], b, h, w, km)
+        if not opt.clusters:
+            return
+        ops.region_nodes(raw, opt.min_size, out32, n_nodes, scratch=ndws)
+        if opt.n_regions > 0 if tree is None else tree:
+            rtws, merges, costs, alive = _stage_buffers(ops, opt, ws, "rt", b, h, w)
+            ops.region_tree_slab(ws["feats"], out32, b, h, w, NODES_MAX, rtws, merges, costs, alive)
+            if tree is None:
+                ops.region_tree_cut(out32, merges, alive, b, h, w, NODES_MAX, opt.n_regions, out32)
+        if out32 is not out:
+            out.copy_(out32)                       # (1 <= n_regions <= 256 was checked: the narrowing keeps every label)
         return
     _, ny, nx = superpixel_grid(h, w, opt.n_superpixels)
     (canon, spws), out32 = _stage_buffers(ops, opt, ws, "sp", b, h, w), ws.get("out32", out)
@@ -982,7 +1021,12 @@ class Segmenter:
         the superpixel map (with ``min_region_size = m > 0``: merged by §9 at m first) instead of its labels, so a cut at R IS
         min(nodes, R) connected regions, numbered in raster order of first pixel, and contour map and sweeps describe the delivered
         maps. ``connectivity`` and ``min_region_size`` are not run again behind the cut. Without ``n_regions`` the node map itself
-        is delivered. The default, "superpixels", is the tree on the raw map."""
+        is delivered. The default, "superpixels", is the tree on the raw map.
+
+        ``tree_nodes = "clusters"`` (SPEC.md §21; needs ``n_superpixels = 0``): the same tree on the 4-connected components of the
+        k-means map (``k``, ``mode`` and ``n_iter`` as without it), cut at ``n_regions``: no superpixel stage, and the tree takes
+        its statistics from the feature slab itself. Everything said of "components" holds: min(nodes, R) connected regions in
+        raster order, ``min_region_size`` joins the node map, nothing runs behind the cut."""
         if not (1 <= k <= _lib.K_MAX):
             raise ValueError(f"k must be in 1..{_lib.K_MAX}")
         if n_iter < 1:
@@ -1004,13 +1048,18 @@ class Segmenter:
         self.ops = ops if ops is not None else HipOps(self.bank, device, self.smoothing, self.chroma_gain)
         if self.n_superpixels > 0 and not hasattr(self.ops, "superpixels"):
             raise ValueError("Segmenter(n_superpixels=n, ops=...) needs ops that have the superpixel stage")
-        self.n_regions = _check_regions(n_regions, self.n_superpixels)          # SPEC.md §14 (0: the superpixel map as it is)
-        if self.n_regions > 0 and not all(hasattr(self.ops, m) for m in ("region_tree_buffers", "region_tree", "region_tree_cut")):
-            raise ValueError("Segmenter(n_regions=R, ops=...) needs ops that have the region tree")
-        self.tree_nodes = tree_nodes
         self._components = _check_tree_nodes(tree_nodes, self.n_superpixels)    # SPEC.md §18
-        if self._components and not all(hasattr(self.ops, m) for m in ("region_nodes_buffers", "region_nodes")):
-            raise ValueError('Segmenter(tree_nodes="components", ops=...) needs ops that have the node map')
+        self._clusters = tree_nodes == "clusters"                               # SPEC.md §21 (checked: n_superpixels = 0)
+        self.tree_nodes = tree_nodes
+        if self._clusters and self.bank.n_features > _SP_D_MAX:
+            raise ValueError(f'tree_nodes = "clusters" needs a bank of at most {_SP_D_MAX} features, this one has {self.bank.n_features}')
+        # SPEC.md §14 (0: the map as it is); the tree merges superpixels or, in the mode of §21, the regions of the k-means map
+        self.n_regions = _check_regions(n_regions, 1 if self._clusters else self.n_superpixels)
+        tree_ops = ("region_tree_buffers", "region_tree_slab" if self._clusters else "region_tree", "region_tree_cut")
+        if self.n_regions > 0 and not all(hasattr(self.ops, m) for m in tree_ops):
+            raise ValueError("Segmenter(n_regions=R, ops=...) needs ops that have the region tree")
+        if (self._components or self._clusters) and not all(hasattr(self.ops, m) for m in ("region_nodes_buffers", "region_nodes")):
+            raise ValueError(f'Segmenter(tree_nodes="{tree_nodes}", ops=...) needs ops that have the node map')
         if self.smoothing > 0 and getattr(self.ops, "smoothing", 0.0) != self.smoothing:
             raise ValueError("Segmenter(smoothing=K, ops=...) needs ops built with the same smoothing")
         if getattr(self.ops, "chroma_gain", 0) != self.chroma_gain:
@@ -1029,7 +1078,7 @@ class Segmenter:
         self.slab_placement_ms = None
         self._opt = _StepOptions(self.k, int(n_iter), self.chroma_gain > 0, self.smoothing > 0, self.position_weight > 0,
                                  self.n_superpixels, self.spatial_weight, self.n_regions, self._components,
-                                 self.min_region_size)
+                                 self.min_region_size, self._clusters)
         self._ws = {}
         self._host = {}
         self._stream = {}
@@ -1056,7 +1105,7 @@ class Segmenter:
     @property
     def _post_passes(self):
         """Do ``connectivity`` / ``min_region_size`` run behind the step? Not in the mode of SPEC.md §18, whose maps are connected."""
-        return (self.connectivity or self.min_region_size > 0) and not self._components
+        return (self.connectivity or self.min_region_size > 0) and not (self._components or self._clusters)
 
     @property
     def n_iter(self):
@@ -1086,9 +1135,9 @@ class Segmenter:
             out_dtype = np.dtype(out_dtype)
             if out_dtype not in (np.dtype(np.int32), np.dtype(np.uint8)):
                 raise ValueError("out_dtype must be int32 or uint8")
-            if self._components:
+            if self._components or self._clusters:
                 if out_dtype == np.uint8 and not 1 <= self.n_regions <= 256:
-                    raise ValueError('tree_nodes = "components": uint8 labels need n_regions in 1..256 (the node count is data)')
+                    raise ValueError(f'tree_nodes = "{self.tree_nodes}": uint8 labels need n_regions in 1..256 (the node count is data)')
             elif self.connectivity and out_dtype == np.uint8:
                 raise ValueError("connectivity=True needs int32 labels")
             elif self.min_region_size > 0 and out_dtype == np.uint8:
@@ -1101,6 +1150,8 @@ class Segmenter:
             check_position_range(self.position_weight, h, w)
         if self.n_superpixels > 0 and cluster:
             self._superpixel_check(h, w, mode, out_dtype, dist_group)
+        if self._clusters and cluster:
+            self._cluster_check(h, w, mode, dist_group)
         return out_dtype
 
     def _may_pipeline(self, mode, superpixels=False):
@@ -1149,6 +1200,12 @@ class Segmenter:
                 _stage_buffers(ops, opt, ws, "sp", n, h, w)
                 if opt.components:
                     _stage_buffers(ops, opt, ws, "nd", n, h, w)
+                if opt.n_regions > 0:
+                    _stage_buffers(ops, opt, ws, "rt", n, h, w)
+                if private == np.uint8:
+                    ws["out32"] = _torch().empty((n, h, w), dtype=_torch().int32, device=ops.device)
+            elif opt.clusters:
+                _stage_buffers(ops, opt, ws, "nd", n, h, w)
                 if opt.n_regions > 0:
                     _stage_buffers(ops, opt, ws, "rt", n, h, w)
                 if private == np.uint8:
@@ -1276,6 +1333,37 @@ class Segmenter:
             raise ValueError(f"out_dtype uint8 cannot hold the {n_labels} labels of this superpixel grid")
         return ny, nx
 
+    def _cluster_check(self, h, w, mode="per_image", dist_group=None):
+        """The argument rules of SPEC.md §21 (``h`` None: only those that need no shape), before anything is launched: the tree is
+        per image, so one rank's global codebook is fine and a group of ranks is not."""
+        if dist_group is not None:
+            raise ValueError('tree_nodes = "clusters" does not run over a dist_group')
+        if mode == "global":
+            import torch.distributed as td
+            if td.is_available() and td.is_initialized() and td.get_world_size() > 1:
+                raise ValueError('tree_nodes = "clusters" with mode "global" runs on one rank only')
+        if h is not None and (h > _SP_SIDE_MAX or w > _SP_SIDE_MAX):
+            raise ValueError(f'tree_nodes = "clusters" needs images of at most {_SP_SIDE_MAX} x {_SP_SIDE_MAX} pixels')
+
+    def _cluster_maps(self, imgs, tree):
+        """The step of SPEC.md §21 on a (B,H,W,3) uint8 device tensor without a cut: the fresh int32 node map and the workspace;
+        ``tree``: the uncut tree is in its ``"rt"``, built behind one read of the batch's node counts at K = the largest of them
+        rounded up to a multiple of 64 (as ``_superpixel_maps`` does for SPEC.md §18)."""
+        torch = _torch()
+        self._check_args(imgs, kind="tensor")
+        imgs = imgs.contiguous()
+        b, h, w, _ = imgs.shape
+        with self._device():
+            ws = self._tail_workspace(b, h, w, "per_image")
+            _step_features(self.ops, self._opt, ws, imgs, b, h, w)
+            out = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
+            _step_cluster(self.ops, self._opt, ws, out, b, h, w, "per_image", self.debug, tree=False)
+            if tree:
+                K = min(NODES_MAX, -(-int(ws["nd"][2].max()) // 64) * 64)
+                ws["rt"] = self.ops.region_tree_buffers(b, h, w, K)
+                self.ops.region_tree_slab(ws["feats"], out, b, h, w, K, *ws["rt"])
+        return out, ws
+
     def _superpixel_maps(self, imgs, tree, centres=False, nodes=None):
         """The step on a (B,H,W,3) uint8 device tensor with SPEC.md §13 as its second piece and no post-passes: the fresh int32 §13
         map (the node map of SPEC.md §18 in that mode, unless ``nodes=False``), the workspace (``tree``: the uncut tree of SPEC.md
@@ -1306,7 +1394,13 @@ class Segmenter:
         unsigned 64-bit costs, all below 2^62; alive (B,) int32) of SPEC.md §14, K = ny * nx: no cut, no post-passes. Any
         ``n_regions`` of the plan is ignored; ``cut_regions_device`` cuts the tree at any R for the cost of a relabel. With
         ``tree_nodes = "components"`` (SPEC.md §18) ``labels`` is the node map N and K the batch's largest node count rounded up to
-        a multiple of 64 (one read of B integers from the device): the first rows of the tree at K_cap."""
+        a multiple of 64 (one read of B integers from the device): the first rows of the tree at K_cap. With ``tree_nodes =
+        "clusters"`` (SPEC.md §21) the same, on the node map of the k-means map."""
+        if self._clusters:                                 # SPEC.md §21: the node map of the k-means map, the tree from the slab
+            if not hasattr(self.ops, "region_tree_slab"):
+                raise ValueError("region_tree_device needs ops that have the region tree")
+            out, ws = self._cluster_maps(imgs, tree=True)
+            return (out,) + ws["rt"][1:]
         if self.n_superpixels == 0:
             raise ValueError("region_tree_device needs Segmenter(n_superpixels=n) with n > 0")
         if not hasattr(self.ops, "region_tree"):
@@ -1511,6 +1605,8 @@ class Segmenter:
         """The options the two row-strip entry points refuse."""
         if self.n_superpixels > 0:
             raise ValueError("n_superpixels > 0 is not supported on row strips")
+        if self._clusters:
+            raise ValueError('tree_nodes = "clusters" is not supported on row strips (regions would cross strip boundaries)')
         if self.min_region_size > 0:
             raise ValueError("min_region_size is not supported on row strips (regions would cross strip boundaries)")
         if self.smoothing > 0:
@@ -2055,8 +2151,8 @@ def segment_contours(img, **kw) -> np.ndarray:
     img = np.ascontiguousarray(img)
     if img.ndim != 3 or img.shape[2] != 3 or img.dtype != np.uint8:
         raise ValueError("img must be an (H,W,3) uint8 array")
-    if not kw.get("n_superpixels"):
-        raise ValueError("segment_contours needs n_superpixels=n with n > 0")
+    if not kw.get("n_superpixels") and kw.get("tree_nodes") != "clusters":
+        raise ValueError('segment_contours needs n_superpixels=n with n > 0, or tree_nodes="clusters"')
     seg = _plan(kw)
     dev = torch.from_numpy(img[None]).to(seg.ops.device) if seg.native else torch.from_numpy(img[None])
     contours, alive = seg.contours_device(dev)

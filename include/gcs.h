@@ -456,6 +456,19 @@ int gcs_region_tree(const uint16_t *feats_canonical_dev, const int32_t *labels_d
 int gcs_region_tree_cut(const int32_t *labels_dev, const int32_t *merges_dev, const int32_t *alive_dev, int B, int H, int W, int K,
                         int R, int32_t *labels_out_dev, gcs_stream_t stream);
 
+/* gcs_region_tree with the statistics taken from the feature slab itself (SPEC.md §21): feats_slab_dev is the slab gcs_gabor_features
+ * (and gcs_smooth_features / gcs_position_features) filled for B images of H x W and the bank (n_scales, n_orient = slots per scale),
+ * either slab format; D = 3 n_scales n_orient. One launch replaces the statistics launch: every level's values are read at the level's
+ * own resolution and added to the labels of the full-resolution pixels they cover. Sums, adjacency, merges, costs and alive are, bit
+ * for bit, those of gcs_region_tree on gcs_features_unpack of the same slab; workspace_dev: gcs_region_tree_workspace_bytes(B, H, W,
+ * D, K), whose head holds the [B][K][D + 1] uint64 sums after the call's second launch (the merge kernel adds merged rows in place).
+ * Three launches, no allocation, no host synchronisation (capturable).
+ * GCS_EINVAL, with nothing launched: as gcs_region_tree, and a bank gcs_feature_slab_bytes refuses or of more than 207 features.
+ * Added within ABI 18: a new entry point changes no existing call, so GCS_ABI_VERSION did not move. */
+int gcs_region_tree_slab(const uint16_t *feats_slab_dev, const int32_t *labels_dev, int B, int H, int W, int n_scales, int n_orient,
+                         int K, void *workspace_dev, int32_t *merges_out_dev, uint64_t *costs_out_dev, int32_t *alive_out_dev,
+                         gcs_stream_t stream);
+
 /* ---- contour map of the region tree, and the boundary counts of every cut at once (SPEC.md §15) ---- */
 
 /* U(y, x) = the largest s(L(y, x), L(y', x')) over the 4-neighbours inside the image, s(p, q) = t + 1 for the row t of merges_dev whose
