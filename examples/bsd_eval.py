@@ -49,6 +49,9 @@ map instead of running behind every cut, and the sweeps describe the delivered m
 of the k-means map of K clusters (SPEC.md §21: `Segmenter(tree_nodes="clusters", k=K)`, default K = 16), the rest as for `components`
 (the n and lambda columns print 0): `--tree-nodes clusters --k 16 --regions 4,6,8,12,16,32 --sweep --agreement --reference-metrics
 --n-orient 5 --color-weight 0.125 --chroma-gain 4` prints the mode's table of `DESIGN.md` §7 from one tree per batch.
+`--edges [--smoothing K] [--n-orient N --color-weight W --chroma-gain G]`: the texture-gradient edge map of the 24 images (SPEC.md
+§22: `Segmenter.edges_device`, no clustering) swept at 256 absolute thresholds (`evaluate_gpu.edge_sweep_resident`, one step for the
+whole set): ODS with its threshold and OIS of the map.
 """
 import os
 import sys
@@ -247,8 +250,40 @@ def sweep_rows(n, lam, n_orient, cw, g, regions, agreement=False, reference=Fals
         print("%-8s ODS %.4f at R = %d   OIS %.4f" % (key, best["ODS"], best["ODS_regions"], best["OIS"]))
 
 
+def edge_rows(n_orient, cw, g, smoothing, levels=256):
+    """`--edges`: the texture-gradient edge map (SPEC.md §22) of the 24 val images at `levels` absolute thresholds."""
+    import numpy as np
+    import torch
+    from gabor_color_image_segmentation_amd import Segmenter
+    from gabor_color_image_segmentation_amd.evaluate import ods_ois
+    from gabor_color_image_segmentation_amd.evaluate_gpu import edge_sweep_resident
+    from gabor_color_image_segmentation_amd.groundtruth import PackedTruth
+    gold = os.path.join(ROOT, "tests", "golden")
+    pack = np.load(os.path.join(gold, "bsd_val_images.npz"))
+    truth = PackedTruth(os.path.join(gold, "bsd500_truth.npz"))
+    ids = [str(i) for i in pack["ids"]]
+    seg = Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, smoothing=smoothing)
+    groups = [[i for i in ids if pack["img_" + i].shape[:2] == shape] for shape in sorted({pack["img_" + i].shape[:2] for i in ids})]
+    maps = [seg.edges_device(torch.from_numpy(np.stack([pack["img_" + i] for i in group])).cuda()) for group in groups]
+    step = -(-(max(int(m.max()) for m in maps) + 1) // levels)             # one step for the set: the thresholds are absolute
+    table = []
+    for group, m in zip(groups, maps):
+        table += edge_sweep_resident(m, truth.to_device(group), levels=levels, step=step)[2].tolist()
+    best = ods_ois(table, [step * (tau + 1) - 1 for tau in range(levels)])
+    print("| n_orient | w | g | K | levels | step | ODS | threshold | OIS |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    print("| %d | %g | %d | %g | %d | %d | %.4f | G > %d | %.4f |" % (n_orient, cw, g, smoothing, levels, step, best["ODS"],
+                                                                    best["ODS_regions"], best["OIS"]))
+
+
 if __name__ == '__main__':
-    clusters = "--tree-nodes" in sys.argv and sys.argv[sys.argv.index("--tree-nodes") + 1] == "clusters"
+    if "--edges" in sys.argv:
+        def opt(name, conv, default):
+            return conv(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
+        edge_rows(opt("--n-orient", int, 6), opt("--color-weight", float, 0.0), opt("--chroma-gain", int, 0),
+                  opt("--smoothing", float, 0.0))
+        sys.exit(0)
+    clusters ="--tree-nodes" in sys.argv and sys.argv[sys.argv.index("--tree-nodes") + 1] == "clusters"
     if "--superpixels" in sys.argv or (clusters and "--regions" in sys.argv):
         def one(name, conv, default):
             return conv(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default

@@ -146,6 +146,57 @@ def boundary_scores(labels, segments_truth) -> dict:
     return {"recall": m.recall, "precision": m.precision, "fmeasure": m.fmeasure}
 
 
+# ---- boundary scores of an edge-strength map at every threshold (SPEC.md §22)
+
+def edge_scores_from_counts(g, ann) -> dict:
+    """metrics.py:69-74 and :88-96 with the map ``edges > theta`` in place of ``find_boundaries(lb)``, on the integer counts of one
+    threshold as Python floats: g = #{edges > theta}, ann = per annotator [recall numerator, #bd(T), precision numerator], flat.
+    The zero rule: g = 0 (no boundary pixel) gives recall = precision = F = 0 instead of the reference's ZeroDivisionError."""
+    if g == 0:
+        return {"recall": 0.0, "precision": 0.0, "fmeasure": 0.0}
+    a = len(ann) // 3
+    recall = 0
+    precision = 0
+    for i in range(0, 3 * a, 3):                                 # in annotator order
+        recall += ann[i] / ann[i + 1]                            # ZeroDivisionError as metrics.py:72: an annotator map without a boundary
+        precision += ann[i + 2] / g
+    recall /= a
+    precision /= a
+    s = recall + precision
+    return {"recall": recall, "precision": precision, "fmeasure": 0.0 if s == 0 else 2.0 * precision * recall / s}
+
+
+def edge_scores(edges, segments_truth, thresholds) -> dict:
+    """Boundary recall / precision / F of an (H,W) integer edge-strength map against its annotator maps at every threshold of
+    ``thresholds`` (integers, any order): the boundary map of threshold theta is ``edges > theta``, the arithmetic is the
+    reference's (``metrics.set_boundary_recall`` / ``set_boundary_precision`` / ``set_fmeasure``) in its order. Returns
+    ``{"recall", "precision", "fmeasure"}``, float64 arrays with one entry per threshold. The counts are taken from sorted values
+    (dil5(edges > theta) = (the 5 x 5 maximum of edges) > theta), not from one dilation per threshold."""
+    edges = np.asarray(edges)
+    if edges.ndim != 2 or edges.dtype.kind not in "iu":
+        raise ValueError("edges must be an (H,W) integer array")
+    if len(segments_truth) == 0:
+        raise ZeroDivisionError("no annotator maps")
+    edges = edges.astype(np.int64)
+    th = np.asarray(thresholds).astype(np.int64).ravel()
+    above = lambda vals: vals.size - np.searchsorted(np.sort(vals, axis=None), th, side="right")    # #{vals > theta}
+    m5 = ndi.maximum_filter(edges, size=5, mode="nearest")       # the window clipped to the image: what _dilate's reflection sees
+    g = above(edges)
+    per = []
+    for s in segments_truth:
+        truth = find_boundaries(s)
+        per.append((above(m5[truth]), int(np.sum(truth)), above(edges[_dilate(truth, 5)])))
+    out = {"recall": np.zeros(len(th)), "precision": np.zeros(len(th)), "fmeasure": np.zeros(len(th))}
+    for j in range(len(th)):
+        ann = []
+        for rec, n_truth, prec in per:
+            ann += [float(rec[j]), float(n_truth), float(prec[j])]
+        sc = edge_scores_from_counts(float(g[j]), ann)
+        for key in out:
+            out[key][j] = sc[key]
+    return out
+
+
 # ---- region agreement: PRI, VoI, segmentation covering (SPEC.md §8; not part of the reference's ``metrics``)
 
 def agreement_sums(labels, truth):

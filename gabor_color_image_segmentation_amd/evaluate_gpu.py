@@ -623,6 +623,53 @@ def sweep_scores(hists, alive, bd_counts, first, regions) -> list:
     return [[_boundary_scores(c[i], c[b + 3 * first[i]:b + 3 * first[i + 1]]) for c in counts] for i in range(b)]
 
 
+def edge_sweep_resident(edges, truth: DeviceTruth, levels=256, step=None):
+    """Boundary scores of an edge-strength map at ``levels`` thresholds at once (SPEC.md §22). edges: (B,H,W) int32 device tensor of
+    non-negative strengths (``Segmenter.edges_device``); truth: the resident ground truth of the same images. The map is quantised
+    on the device, q = min(levels, edges // step) with ``step`` defaulting to ceil((batch max + 1) / levels) (one read from the
+    device), and swept like a contour map (gcs_boundary_sweep_resident with K = levels): level tau = 0 .. levels - 1 is the
+    boundary map q > tau, i.e. edges >= step (tau + 1). Returns ``(recall, precision, fmeasure, step)``, float64 host arrays
+    [B][levels]: the floats of ``evaluate.edge_scores`` at the thresholds step (tau + 1) - 1 (the same integer counts through the
+    same float operations), zeros where a level leaves an image without a boundary pixel. ``evaluate.ods_ois(fmeasure,
+    [step * (tau + 1) - 1 for tau in range(levels)])`` serves the table: its "regions" axis is then the threshold (ties go to the
+    lowest)."""
+    import torch
+    from .evaluate import edge_scores_from_counts
+    lib = _lib.load()
+    _need_labels(edges, 3, "edges")
+    b, h, w = edges.shape
+    _need_match((b, h, w), edges.device, truth, "edge map")
+    levels = int(levels)
+    if not 1 <= levels <= SWEEP_LEVELS:
+        raise ValueError(f"levels must be in 1 .. {SWEEP_LEVELS}")
+    if h > 4096 or w > 4096:
+        raise ValueError("the sweep takes images of at most 4096 x 4096 pixels")
+    with torch.cuda.device(truth.device):
+        if step is None:
+            step = -(-(int(edges.max().item()) + 1) // levels)
+        step = int(step)
+        if step < 1:
+            raise ValueError("step must be at least 1")
+        q = torch.clamp(torch.div(edges, step, rounding_mode="floor"), max=levels).to(torch.int32).contiguous()
+        hist = torch.empty((b + 2 * truth.t, levels + 1), dtype=torch.int32, device=truth.device)
+        _lib.check(lib.gcs_boundary_sweep_resident(q.data_ptr(), truth.planes.data_ptr(), truth.img_of_d.data_ptr(), b, truth.t,
+                                                   h, w, levels, hist.data_ptr(), torch.cuda.current_stream(truth.device).cuda_stream),
+                   "gcs_boundary_sweep_resident")
+        raw = hist.cpu().numpy().view(np.uint32)
+        bd_counts = truth.bd_counts.cpu().numpy()
+    ann = raw[b:].reshape(truth.t, 2, levels + 1)
+    # q > tau is the cut of a tree with `levels` leaves at R = levels - tau: sweep_counts' suffix sums as they are
+    counts = sweep_counts((raw[:b], ann[:, 0], ann[:, 1]), np.full(b, levels), bd_counts, truth.first,
+                          [levels - tau for tau in range(levels)]).astype(np.float64).tolist()
+    first = truth.first.tolist()
+    out = np.zeros((3, b, levels))
+    for tau, c in enumerate(counts):
+        for i in range(b):
+            sc = edge_scores_from_counts(c[i], c[b + 3 * first[i]:b + 3 * first[i + 1]])
+            out[0, i, tau], out[1, i, tau], out[2, i, tau] = sc["recall"], sc["precision"], sc["fmeasure"]
+    return out[0], out[1], out[2], step
+
+
 # ------------------------------------------------------------------------------------------------------------------------
 # 4b. The region metrics of every cut of a region tree at once (SPEC.md §16): the leaf tables from one pass over the pixels,
 # every coarser table from the merge list by adding rows.

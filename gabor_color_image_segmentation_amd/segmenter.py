@@ -610,6 +610,16 @@ class HipOps:
                                                       cap, n, cap_out, workspace.data_ptr(), edges_out.data_ptr(), vals_out.data_ptr(),
                                                       count_out.data_ptr(), self._stream()), "gcs_region_adjacency_cuts")
 
+    @_on_device
+    def feature_gradient(self, feats, b, h, w, out):
+        """SPEC.md §22: the texture-gradient edge map of the slab ``feats`` (as ``gabor_features`` and the stages behind it left
+        it) into ``out``, a contiguous (B,H,W) int32 tensor. One launch, no workspace (capturable as it is)."""
+        self._need(out, self.torch.int32, (b, h, w), "out must be a contiguous (B,H,W) int32 tensor")
+        if out is None:
+            raise ValueError("out must be a contiguous (B,H,W) int32 tensor")
+        _lib.check(self.lib.gcs_feature_gradient(feats.data_ptr(), b, h, w, *self._bk, out.data_ptr(), self._stream()),
+                   "gcs_feature_gradient")
+
     def download(self, dst_pinned, src):
         """Device tensor -> pinned host tensor of the same bytes on the current stream, by SDMA (gcs_download)."""
         self._check_dev(src)
@@ -1729,6 +1739,26 @@ class Segmenter:
         _step_features(self.ops, self._opt, ws, imgs, b, h, w)
         return _unpack(self.ops, ws, b, h, w)
 
+    def edges_device(self, imgs, y0=0):
+        """(B,H,W,3) uint8 device tensor -> (B,H,W) int32 texture-gradient edge map of SPEC.md §22: how fast the plan's features
+        (``smoothing``, the colour and the position options included) change from one pixel to the next, every pyramid level
+        differenced at its own resolution, read from the feature slab (the canonical tensor is never made). ``k``, ``n_iter`` and
+        the region options play no part. ``y0``: only 0 - a row strip of a taller image is refused (its differences at the strip's
+        edges are not the image's, and its halo rows are not the caller's)."""
+        if int(y0) != 0:
+            raise ValueError("edges_device is not supported on row strips (differences would be clamped at the strip's edges)")
+        if not hasattr(self.ops, "feature_gradient"):
+            raise ValueError("the edge map needs ops that have it")
+        self._check_args(imgs, kind="tensor", cluster=False)
+        imgs = imgs.contiguous()
+        b, h, w, _ = imgs.shape
+        with self._device():
+            ws = self._tail_workspace(b, h, w, "per_image", slab_only=True)
+            _step_features(self.ops, self._opt, ws, imgs, b, h, w)
+            out = _torch().empty((b, h, w), dtype=_torch().int32, device=imgs.device)
+            self.ops.feature_gradient(ws["feats"], b, h, w, out)
+        return out
+
     # ---- host API: the slot
     def segment_batch(self, imgs: np.ndarray, mode="per_image", out_dtype=np.int32) -> np.ndarray:
         """(B,H,W,3) uint8 host array -> fresh (B,H,W) host label array (the calling convention of script.py:25,30).
@@ -2159,6 +2189,22 @@ def segment_contours(img, **kw) -> np.ndarray:
     return (contours[0].cpu().numpy().astype(np.float32) / np.float32(max(1, int(alive[0])))).astype(np.float32)
 
 
+def segment_edges(img, **kw) -> np.ndarray:
+    """(H,W,3) uint8 -> (H,W) float32 edge strengths in [0, 1]: the texture-gradient map of SPEC.md §22
+    (``Segmenter.edges_device``) divided by its largest value, all zeros for a map that is zero everywhere. ``kw``: the plan's
+    options (the bank, ``smoothing``, colour and position options shape the map; clustering options play no part); the plan is
+    cached like ``segment``'s."""
+    torch = _torch()
+    img = _one_image(img)
+    seg = _plan(kw)
+    dev = torch.from_numpy(img[None]).to(seg.ops.device) if seg.native else torch.from_numpy(img[None])
+    g = seg.edges_device(dev)[0].cpu().numpy()
+    top = int(g.max())
+    if top == 0:
+        return np.zeros(g.shape, np.float32)
+    return (g.astype(np.float32) / np.float32(top)).astype(np.float32)
+
+
 def segment_images(images, batch=64, **kw):
     """Generator form of the loop at script.py:22-38: yields ``segment(img)`` for every image of an iterable, in order, with
     the images batched per shape behind the scenes (``Segmenter.segment_images``)."""
@@ -2179,13 +2225,18 @@ def _one_image(img):
     return img
 
 
-def segment_regions(img, adjacency=False, **kw):
+def segment_regions(img, adjacency=False, gradient=False, **kw):
     """(H,W,3) uint8 -> ``(labels (H,W) int32, table)``: ``segment(img, **kw)`` and the descriptors of its regions (SPEC.md §19,
     ``regions.region_table``: area, centroid, bbox, mean_rgb, mean_features, used; one entry per label 0 .. labels.max()). The table
     is made from the delivered map, behind every post-pass of the plan, so it describes what the caller gets. ``adjacency=True``: the
     table gains the key ``"adjacency"``, the region adjacency graph of the delivered map (SPEC.md §20, ``regions.adjacency_table``
     with ``n_regions`` = the number of labels: pairs, length, mean_contrast from ``img``, mean_strength 0, degree, neighbours).
-    A delivered map with more than 16 384 edges (no map of connected regions of fewer than 5 463 labels has) raises ``ValueError``."""
+    A delivered map with more than 16 384 edges (no map of connected regions of fewer than 5 463 labels has) raises ``ValueError``.
+    ``gradient=True`` (with ``adjacency=True``): the texture-gradient edge map of SPEC.md §22 (``Segmenter.edges_device`` of the
+    same plan) is the graph's strength plane, so ``mean_strength`` is the mean gradient along each shared boundary; without it the
+    output is what it was, bit for bit."""
+    if gradient and not adjacency:
+        raise ValueError("gradient=True needs adjacency=True (the gradient is the strength plane of the adjacency graph)")
     from .regions import region_table, adjacency_table
     torch = _torch()
     img = _one_image(img)
@@ -2198,9 +2249,10 @@ def segment_regions(img, adjacency=False, **kw):
     table = region_table(sums[0].cpu().numpy(), bbox[0].cpu().numpy())
     if adjacency:
         k = int(sums.shape[1])
-        edges, vals, count = seg.region_adjacency_device(lab_d, K=k, imgs=imgs_d)
+        strength = seg.edges_device(imgs_d) if gradient else None
+        edges, vals, count = seg.region_adjacency_device(lab_d, K=k, imgs=imgs_d, strength=strength)
         if int(count[0]) < 0:                                      # more edges than the default capacity: once more at the largest
-            edges, vals, count = seg.region_adjacency_device(lab_d, K=k, imgs=imgs_d, capacity=16384)
+            edges, vals, count = seg.region_adjacency_device(lab_d, K=k, imgs=imgs_d, strength=strength, capacity=16384)
         table["adjacency"] = adjacency_table(edges[0].cpu().numpy(), vals[0].cpu().numpy(), int(count[0]), n_regions=k)
     return labels, table
 

@@ -648,6 +648,20 @@ int gcs_region_adjacency_cuts(const int32_t *edges_dev, const uint64_t *vals_dev
                               int B, int K, int G, int E_cap, int n_cuts, int E_out_cap, void *workspace_dev, int32_t *edges_out_dev,
                               uint64_t *vals_out_dev, int32_t *count_out_dev, gcs_stream_t stream);
 
+/* ---- texture-gradient edge map of the feature slab (SPEC.md §22) ---- */
+
+/* grad_out_dev int32 [B][H][W]: G = floor(sqrt(E)), E = the sum over the bank's pyramid levels L of (DX_L >> 2L) + (DY_L >> 2L),
+ * DX_L / DY_L = the squared central differences (clamped at the level's edge) of the level's planes at the level pixel
+ * (y >> L, x >> L), summed over the planes. feats_slab_dev: the slab gcs_gabor_features (and gcs_smooth_features /
+ * gcs_position_features) filled for B images of H x W and the bank (n_scales, n_orient = slots per scale), either slab format; every
+ * level is read at its own resolution, the canonical tensor is never made. E < 2^41 for any 16-bit values and the root is exact.
+ * One launch, no workspace, no allocation, no host synchronisation (capturable). grad_out_dev must not overlap the slab.
+ * GCS_EINVAL, with nothing launched: a NULL pointer, B outside 1..65535, H or W outside 1..4096, a bank gcs_feature_slab_bytes refuses
+ * or of more than 207 features.
+ * Added within ABI 18: a new entry point changes no existing call, so GCS_ABI_VERSION did not move. */
+int gcs_feature_gradient(const uint16_t *feats_slab_dev, int B, int H, int W, int n_scales, int n_orient, int32_t *grad_out_dev,
+                         gcs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
