@@ -45,6 +45,8 @@ density and regions - of every listed R from the same tree and contour map (SPEC
 `--tree-nodes components` beside `--regions` (with or without `--sweep`): the tree on the connected regions of the superpixel map
 (SPEC.md §18: `Segmenter(tree_nodes="components")`): every cut at R is R connected regions, `--min-region-size` goes into the node
 map instead of running behind every cut, and the sweeps describe the delivered maps.
+`--merge-cost boundary` beside `--regions` (any `--tree-nodes`): the tree merges the pair of regions whose common boundary is weakest
+on average in the texture-gradient map (SPEC.md §23: `Segmenter(merge_cost="boundary")`); the default, `features`, is the tree of §14.
 `--tree-nodes clusters [--k K]` beside `--regions` (with or without `--sweep`; no `--superpixels`): the tree on the connected regions
 of the k-means map of K clusters (SPEC.md §21: `Segmenter(tree_nodes="clusters", k=K)`, default K = 16), the rest as for `components`
 (the n and lambda columns print 0): `--tree-nodes clusters --k 16 --regions 4,6,8,12,16,32 --sweep --agreement --reference-metrics
@@ -162,10 +164,12 @@ def superpixel_row(n, lam, n_orient, cw, g, merge):
 def region_plan(n, lam, n_orient, cw, g, tree_nodes, k, m=0):
     """The plan of `--regions`: on superpixels (SPEC.md §14, §18) or, with `--tree-nodes clusters`, on the k-means map (§21)."""
     from gabor_color_image_segmentation_amd import Segmenter
+    cost = sys.argv[sys.argv.index("--merge-cost") + 1] if "--merge-cost" in sys.argv else "features"    # SPEC.md §23
     if tree_nodes == "clusters":
-        return Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, k=k, tree_nodes=tree_nodes, min_region_size=m)
+        return Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, k=k, tree_nodes=tree_nodes, min_region_size=m,
+                         merge_cost=cost)
     return Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, n_superpixels=n, spatial_weight=lam, tree_nodes=tree_nodes,
-                     min_region_size=m)
+                     min_region_size=m, merge_cost=cost)
 
 
 def region_rows(n, lam, n_orient, cw, g, merge, regions, tree_nodes="superpixels", k=16):

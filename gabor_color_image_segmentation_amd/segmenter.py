@@ -190,6 +190,7 @@ def _on_device(fn):
     return wrapper
 
 
+EDGES_MAX = 16384             # SPEC.md §20: the largest capacity of an edge table (§23 builds its leaf table at it)
 NODES_MAX = 4096              # SPEC.md §18: K_cap, the most nodes an image's tree can have (= §14's largest K)
 
 
@@ -620,6 +621,52 @@ class HipOps:
         _lib.check(self.lib.gcs_feature_gradient(feats.data_ptr(), b, h, w, *self._bk, out.data_ptr(), self._stream()),
                    "gcs_feature_gradient")
 
+    def region_tree_edges_buffers(self, b, h, w, K, capacity=EDGES_MAX):
+        """What SPEC.md §23 needs for one (batch, shape, K): ``(stage, merges (B, K-1, 2) int32, costs (B, K-1) int64, alive (B,)
+        int32)``, the shape of ``region_tree_buffers``; ``stage`` is a dict of the plane G (``grad``), the leaf table of SPEC.md §20
+        at ``capacity`` (``edges``, ``vals``, ``count``) with its workspace (``adj``), the flags of the labels in use (``used``)
+        and the merge kernel's workspace (``tree``) (a captured graph must own them)."""
+        torch, K, cap = self.torch, int(K), int(capacity)
+        need = self.lib.gcs_region_tree_edges_workspace_bytes(b, K, cap)
+        if need == 0 or h > _SP_SIDE_MAX or w > _SP_SIDE_MAX:
+            raise ValueError("no region tree for this shape (1 <= B <= 65535, H, W <= 4096, 1 <= K <= 4096, 1 <= capacity <= 16384)")
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=self.device)
+        stage = dict(grad=new((b, h, w), torch.int32), adj=self.adjacency_buffers(b, cap), edges=new((b, cap, 2), torch.int32),
+                     vals=new((b, cap, 3), torch.int64), count=new((b,), torch.int32), used=new((b, K), torch.int32),
+                     tree=self.empty_bytes(need))
+        return stage, new((b, K - 1, 2), torch.int32), new((b, K - 1), torch.int64), new((b,), torch.int32)
+
+    @_on_device
+    def label_used(self, labels, b, h, w, K, out):
+        """``out`` (B, K) int32 := 1 where a pixel of the int32 (B,H,W) map ``labels`` carries the label, else 0. One launch, capturable."""
+        K = int(K)
+        self._need(labels, self.torch.int32, (b, h, w), "labels must be a contiguous (B,H,W) int32 tensor")
+        self._need(out, self.torch.int32, (b, K), "out must be a contiguous (B, K) int32 tensor")
+        if labels is None or out is None:
+            raise ValueError("labels and out are needed")
+        _lib.check(self.lib.gcs_label_used(labels.data_ptr(), b, h, w, K, out.data_ptr(), self._stream()), "gcs_label_used")
+
+    @_on_device
+    def region_tree_edges(self, edges, vals, count, used, b, K, workspace, merges, costs, alive):
+        """SPEC.md §23 on a leaf table of SPEC.md §20 (``edges``, ``vals``, ``count`` as ``region_adjacency`` wrote them; the
+        strength column weighs the edges) and ``used`` (B, K) int32 (not 0: the label owns a pixel): fills ``merges`` (B, K-1, 2)
+        int32, ``costs`` (None or (B, K-1) int64) and ``alive`` (B,) int32 in the format of ``region_tree``. ``workspace``: the
+        ``tree`` of ``region_tree_edges_buffers``. One launch, capturable."""
+        torch, K = self.torch, int(K)
+        cap = self._need_graph(edges, vals, count, (b,), "region_tree_edges")
+        self._need(used, torch.int32, (b, K), "used must be a contiguous (B, K) int32 tensor")
+        self._need(merges, torch.int32, (b, K - 1, 2), "merges must be a contiguous (B, K - 1, 2) int32 tensor")
+        self._need(costs, torch.int64, (b, K - 1), "costs must be a contiguous (B, K - 1) int64 tensor")
+        self._need(alive, torch.int32, (b,), "alive must be a contiguous (B,) int32 tensor")
+        need = self.lib.gcs_region_tree_edges_workspace_bytes(b, K, cap)
+        if used is None or merges is None or alive is None or need == 0 or workspace is None \
+                or workspace.numel() * workspace.element_size() < need:
+            raise ValueError("used, merges, alive and the workspace of region_tree_edges_buffers are needed (1 <= K <= 4096)")
+        _lib.check(self.lib.gcs_region_tree_edges(edges.data_ptr(), vals.data_ptr(), count.data_ptr(), used.data_ptr(), b, K, cap,
+                                                  workspace.data_ptr(), merges.data_ptr() if K > 1 else None,
+                                                  None if costs is None or K == 1 else costs.data_ptr(), alive.data_ptr(),
+                                                  self._stream()), "gcs_region_tree_edges")
+
     def download(self, dst_pinned, src):
         """Device tensor -> pinned host tensor of the same bytes on the current stream, by SDMA (gcs_download)."""
         self._check_dev(src)
@@ -870,9 +917,9 @@ def lloyd(ops, feats, b, h, w, k, n_iter, mode, labels, partials, cent, sums, di
 # stage on). The two pieces of the step take it, the ops, a workspace and the debug switches as arguments and never the
 # Segmenter: a graph entry holds them, and an entry that held its plan would be a reference cycle (see _segment_small).
 # ``components``: SPEC.md §18 is on (then ``min_size`` = the plan's min_region_size, the m of the node map); ``clusters``: SPEC.md §21
-# is on (the same m).
+# is on (the same m). ``boundary``: the tree is SPEC.md §23's (merge_cost = "boundary").
 _StepOptions = collections.namedtuple("_StepOptions", "k n_iter colour smooth position n_superpixels spatial_weight n_regions "
-                                                      "components min_size clusters", defaults=(False,))
+                                                      "components min_size clusters boundary", defaults=(False, False))
 
 
 def _opponent(ops, imgs, colour):
@@ -921,8 +968,36 @@ def _stage_buffers(ops, opt, ws, key, b, h, w):
         elif key == "nd":
             ws[key] = ops.region_nodes_buffers(b, h, w)
         else:
-            ws[key] = ops.region_tree_buffers(b, h, w, NODES_MAX if opt.components or opt.clusters else ny * nx)
+            make = ops.region_tree_edges_buffers if opt.boundary else ops.region_tree_buffers
+            ws[key] = make(b, h, w, NODES_MAX if opt.components or opt.clusters else ny * nx)
     return ws[key]
+
+
+_BOUNDARY_OPS = ("region_tree_edges_buffers", "feature_gradient", "label_used", "region_adjacency", "region_tree_edges")
+
+
+def _check_merge_cost(merge_cost):
+    """SPEC.md §23: which cost the tree merges by."""
+    if not isinstance(merge_cost, str) or merge_cost not in ("features", "boundary"):
+        raise ValueError(f'merge_cost must be "features" or "boundary", got {merge_cost!r}')
+    return merge_cost == "boundary"
+
+
+def _step_tree(ops, opt, ws, rt, labels, b, h, w, K, canon=None):
+    """The tree of the int32 node map ``labels`` into the buffers ``rt`` of ``_stage_buffers``: SPEC.md §14 on the canonical tensor
+    ``canon`` or, without one (SPEC.md §21), on the slab; with ``merge_cost = "boundary"`` SPEC.md §23: the edge map of §22 from the
+    slab, the labels in use, the leaf table of §20 with that map as its strength plane, and the merges on that table. No node
+    statistics are gathered and no feature is read behind the edge map."""
+    stage, merges, costs, alive = rt
+    if opt.boundary:
+        ops.feature_gradient(ws["feats"], b, h, w, stage["grad"])
+        ops.label_used(labels, b, h, w, K, stage["used"])
+        ops.region_adjacency(labels, None, stage["grad"], b, h, w, K, stage["adj"], stage["edges"], stage["vals"], stage["count"])
+        ops.region_tree_edges(stage["edges"], stage["vals"], stage["count"], stage["used"], b, K, stage["tree"], merges, costs, alive)
+    elif canon is None:
+        ops.region_tree_slab(ws["feats"], labels, b, h, w, K, stage, merges, costs, alive)
+    else:
+        ops.region_tree(canon, labels, b, h, w, K, stage, merges, costs, alive)
 
 
 def _step_cluster(ops, opt, ws, out, b, h, w, mode, debug, dist_group=None, rows=None, init=None, centres=None, tree=None,
@@ -958,7 +1033,7 @@ def _step_cluster(ops, opt, ws, out, b, h, w, mode, debug, dist_group=None, rows
         ops.region_nodes(raw, opt.min_size, out32, n_nodes, scratch=ndws)
         if opt.n_regions > 0 if tree is None else tree:
             rtws, merges, costs, alive = _stage_buffers(ops, opt, ws, "rt", b, h, w)
-            ops.region_tree_slab(ws["feats"], out32, b, h, w, NODES_MAX, rtws, merges, costs, alive)
+            _step_tree(ops, opt, ws, (rtws, merges, costs, alive), out32, b, h, w, NODES_MAX)
             if tree is None:
                 ops.region_tree_cut(out32, merges, alive, b, h, w, NODES_MAX, opt.n_regions, out32)
         if out32 is not out:
@@ -977,7 +1052,7 @@ def _step_cluster(ops, opt, ws, out, b, h, w, mode, debug, dist_group=None, rows
         ops.superpixels(canon, b, h, w, ny, nx, opt.spatial_weight, opt.n_iter, out32, spws, centres)
     if opt.n_regions > 0 if tree is None else tree:
         rtws, merges, costs, alive = _stage_buffers(ops, opt, ws, "rt", b, h, w)
-        ops.region_tree(canon, out32, b, h, w, K, rtws, merges, costs, alive)
+        _step_tree(ops, opt, ws, (rtws, merges, costs, alive), out32, b, h, w, K, canon)
         if tree is None:
             ops.region_tree_cut(out32, merges, alive, b, h, w, K, opt.n_regions, out32)
     if out32 is not out:
@@ -1016,7 +1091,8 @@ class Segmenter:
     def __init__(self, n_scales=4, n_orient=6, k=8, n_iter=10, ksize=13, f_max=0.4,
                  ratio=math.sqrt(2.0), bandwidth=1.0, connectivity=False, device="cuda:0", ops=None,
                  slab_candidates=1, min_region_size=0, smoothing=0.0, color_weight=0.0, chroma_gain=0,
-                 position_weight=0, n_superpixels=0, spatial_weight=576, n_regions=0, tree_nodes="superpixels"):
+                 position_weight=0, n_superpixels=0, spatial_weight=576, n_regions=0, tree_nodes="superpixels",
+                 merge_cost="features"):
         """``n_superpixels = n`` (SPEC.md §13; 0 = off, 2..4096): grid-local k-means instead of the Lloyd stage - about n compact
         superpixels per image (K = ny * nx of ``superpixel_grid``) on the same features; ``k`` and ``mode`` are then unused (centres
         are per image). ``spatial_weight`` = lambda (1..65535, default 576) weighs the squared pixel distance to a centre against
@@ -1036,7 +1112,13 @@ class Segmenter:
         ``tree_nodes = "clusters"`` (SPEC.md §21; needs ``n_superpixels = 0``): the same tree on the 4-connected components of the
         k-means map (``k``, ``mode`` and ``n_iter`` as without it), cut at ``n_regions``: no superpixel stage, and the tree takes
         its statistics from the feature slab itself. Everything said of "components" holds: min(nodes, R) connected regions in
-        raster order, ``min_region_size`` joins the node map, nothing runs behind the cut."""
+        raster order, ``min_region_size`` joins the node map, nothing runs behind the cut.
+
+        ``merge_cost = "boundary"`` (SPEC.md §23; wherever a tree is valid, in all three ``tree_nodes`` modes): the tree merges the
+        pair of adjacent groups whose common boundary is weakest on average in the texture-gradient map of SPEC.md §22 (the
+        UCM rule) instead of the pair of closest mean features: cost = floor(128 strength / length) of the pair's edge in the
+        region adjacency graph of SPEC.md §20. Merge list, cuts, contour map and sweeps keep their format and meaning. The
+        default, "features", is the tree of SPEC.md §14, bit for bit."""
         if not (1 <= k <= _lib.K_MAX):
             raise ValueError(f"k must be in 1..{_lib.K_MAX}")
         if n_iter < 1:
@@ -1055,6 +1137,10 @@ class Segmenter:
         self.n_superpixels, self.spatial_weight = _check_superpixels(n_superpixels, spatial_weight)   # SPEC.md §13 (0: §4's Lloyd stage)
         if self.n_superpixels > 0 and self.bank.n_features > _SP_D_MAX:
             raise ValueError(f"n_superpixels needs a bank of at most {_SP_D_MAX} features, this one has {self.bank.n_features}")
+        self._boundary = _check_merge_cost(merge_cost)                          # SPEC.md §23
+        self.merge_cost = merge_cost
+        if self._boundary and self.n_superpixels == 0 and tree_nodes != "clusters":
+            raise ValueError('merge_cost = "boundary" weighs a region tree: it needs n_superpixels > 0 or tree_nodes = "clusters"')
         self.ops = ops if ops is not None else HipOps(self.bank, device, self.smoothing, self.chroma_gain)
         if self.n_superpixels > 0 and not hasattr(self.ops, "superpixels"):
             raise ValueError("Segmenter(n_superpixels=n, ops=...) needs ops that have the superpixel stage")
@@ -1066,6 +1152,10 @@ class Segmenter:
         # SPEC.md §14 (0: the map as it is); the tree merges superpixels or, in the mode of §21, the regions of the k-means map
         self.n_regions = _check_regions(n_regions, 1 if self._clusters else self.n_superpixels)
         tree_ops = ("region_tree_buffers", "region_tree_slab" if self._clusters else "region_tree", "region_tree_cut")
+        if self._boundary:
+            tree_ops = _BOUNDARY_OPS + ("region_tree_cut",)
+            if not all(hasattr(self.ops, m) for m in tree_ops):
+                raise ValueError('Segmenter(merge_cost="boundary", ops=...) needs ops that have the stages of SPEC.md §23')
         if self.n_regions > 0 and not all(hasattr(self.ops, m) for m in tree_ops):
             raise ValueError("Segmenter(n_regions=R, ops=...) needs ops that have the region tree")
         if (self._components or self._clusters) and not all(hasattr(self.ops, m) for m in ("region_nodes_buffers", "region_nodes")):
@@ -1088,13 +1178,14 @@ class Segmenter:
         self.slab_placement_ms = None
         self._opt = _StepOptions(self.k, int(n_iter), self.chroma_gain > 0, self.smoothing > 0, self.position_weight > 0,
                                  self.n_superpixels, self.spatial_weight, self.n_regions, self._components,
-                                 self.min_region_size, self._clusters)
+                                 self.min_region_size, self._clusters, self._boundary)
         self._ws = {}
         self._host = {}
         self._stream = {}
         self._copy_pair = None
         self._stagers = None
         self._graphs = {}
+        self._last_plane = None
 
     def __del__(self):
         # a plan dropped in one thread while another thread captures: its graphs leave through the guard (parked until that
@@ -1309,6 +1400,7 @@ class Segmenter:
                 ws = self._workspace(n, h, w, mode) if n == g else self._tail_workspace(n, h, w, mode)
                 _step_features(self.ops, self._opt, ws, imgs[g0:g0 + n], n, h, w)
                 _step_cluster(self.ops, self._opt, ws, out[g0:g0 + n], n, h, w, mode, self.debug, dist_group)
+                self._note_plane(ws)
             if not self._post_passes:                      # (SPEC.md §18: the step's map is connected and numbered as §7 numbers)
                 return out
             if self.min_region_size > 0:
@@ -1355,6 +1447,17 @@ class Segmenter:
         if h is not None and (h > _SP_SIDE_MAX or w > _SP_SIDE_MAX):
             raise ValueError(f'tree_nodes = "clusters" needs images of at most {_SP_SIDE_MAX} x {_SP_SIDE_MAX} pixels')
 
+    def _note_plane(self, ws):
+        """SPEC.md §23: the step that has just run left the edge map of its batch in its tree stage; ``segment_regions`` takes it
+        from there instead of computing it again (it is valid until the next step on the same workspace). ``segment_regions``
+        clears the note before its call and takes it once behind it, so a host path that leaves no note costs one ``edges_device``
+        and never a plane of another image."""
+        if self._boundary and ws.get("rt") is not None:
+            self._last_plane = ws["rt"][0]["grad"]
+
+    def _tree_buffers(self, b, h, w, K):
+        return (self.ops.region_tree_edges_buffers if self._boundary else self.ops.region_tree_buffers)(b, h, w, K)
+
     def _cluster_maps(self, imgs, tree):
         """The step of SPEC.md §21 on a (B,H,W,3) uint8 device tensor without a cut: the fresh int32 node map and the workspace;
         ``tree``: the uncut tree is in its ``"rt"``, built behind one read of the batch's node counts at K = the largest of them
@@ -1370,8 +1473,8 @@ class Segmenter:
             _step_cluster(self.ops, self._opt, ws, out, b, h, w, "per_image", self.debug, tree=False)
             if tree:
                 K = min(NODES_MAX, -(-int(ws["nd"][2].max()) // 64) * 64)
-                ws["rt"] = self.ops.region_tree_buffers(b, h, w, K)
-                self.ops.region_tree_slab(ws["feats"], out, b, h, w, K, *ws["rt"])
+                ws["rt"] = self._tree_buffers(b, h, w, K)
+                _step_tree(self.ops, self._opt, ws, ws["rt"], out, b, h, w, K)
         return out, ws
 
     def _superpixel_maps(self, imgs, tree, centres=False, nodes=None):
@@ -1395,8 +1498,8 @@ class Segmenter:
                           tree=False if trim else tree, nodes=nodes)
             if trim:
                 K = min(NODES_MAX, -(-int(ws["nd"][2].max()) // 64) * 64)
-                ws["rt"] = self.ops.region_tree_buffers(b, h, w, K)
-                self.ops.region_tree(ws["sp"][0], out, b, h, w, K, *ws["rt"])
+                ws["rt"] = self._tree_buffers(b, h, w, K)
+                _step_tree(self.ops, self._opt, ws, ws["rt"], out, b, h, w, K, ws["sp"][0])
         return out, ws, centres
 
     def region_tree_device(self, imgs):
@@ -1407,13 +1510,13 @@ class Segmenter:
         a multiple of 64 (one read of B integers from the device): the first rows of the tree at K_cap. With ``tree_nodes =
         "clusters"`` (SPEC.md §21) the same, on the node map of the k-means map."""
         if self._clusters:                                 # SPEC.md §21: the node map of the k-means map, the tree from the slab
-            if not hasattr(self.ops, "region_tree_slab"):
+            if not hasattr(self.ops, "region_tree_edges" if self._boundary else "region_tree_slab"):
                 raise ValueError("region_tree_device needs ops that have the region tree")
             out, ws = self._cluster_maps(imgs, tree=True)
             return (out,) + ws["rt"][1:]
         if self.n_superpixels == 0:
             raise ValueError("region_tree_device needs Segmenter(n_superpixels=n) with n > 0")
-        if not hasattr(self.ops, "region_tree"):
+        if not hasattr(self.ops, "region_tree_edges" if self._boundary else "region_tree"):
             raise ValueError("region_tree_device needs ops that have the region tree")
         out, ws, _ = self._superpixel_maps(imgs, tree=True)
         return (out,) + ws["rt"][1:]
@@ -1808,6 +1911,7 @@ class Segmenter:
             _step_features(ops, opt, ws, None, b, h, w)            # once for the batch, behind every chunk's Gabor stage on `cur`
             dev_out = st["dev_out"] if out_dtype == np.uint8 else st["dev_out32"]
             _step_cluster(ops, opt, ws, dev_out, b, h, w, mode, self.debug)
+            self._note_plane(ws)
             # The result is a FRESH pinned host buffer per call, handed to the caller as the base of the returned
             # array (torch's caching host allocator recycles it once the caller drops the array): the device-to-host
             # copy lands directly in caller-owned memory, with no pageable copy and no first-touch page faults.
@@ -1889,6 +1993,7 @@ class Segmenter:
                 ent["graph"].replay()
             else:
                 ent["step"]()
+            self._note_plane(ent["ws"])
             res = torch.empty((b, h, w), dtype=ent["dev_out"].dtype, pin_memory=True)   # caller-owned pinned result
             res.copy_(ent["dev_out"], non_blocking=True)
             cur.synchronize()
@@ -2160,6 +2265,12 @@ def _stage(pinned, imgs):
 _default: dict = {}
 
 
+def _need_cut(kw):
+    """A one-shot call that delivers a label map builds a tree only to cut it: SPEC.md §23 without ``n_regions`` has nothing to weigh."""
+    if kw.get("merge_cost", "features") == "boundary" and not kw.get("n_regions"):
+        raise ValueError('merge_cost = "boundary" needs n_regions = R with R > 0 here: without a cut no tree is built')
+
+
 def _plan(kw) -> Segmenter:
     key = tuple(sorted(kw.items()))
     if key not in _default:
@@ -2170,6 +2281,7 @@ def _plan(kw) -> Segmenter:
 
 def segment(img, **kw) -> np.ndarray:
     """Drop-in for ``slic(img, ...)`` at script.py:30: (H,W,3) uint8 -> (H,W) int32 labels 0..k-1."""
+    _need_cut(kw)
     return _plan(kw)(img)
 
 
@@ -2209,12 +2321,14 @@ def segment_images(images, batch=64, **kw):
     """Generator form of the loop at script.py:22-38: yields ``segment(img)`` for every image of an iterable, in order, with
     the images batched per shape behind the scenes (``Segmenter.segment_images``)."""
     out_dtype = kw.pop("out_dtype", np.int32)
+    _need_cut(kw)
     return _plan(kw).segment_images(images, batch=batch, out_dtype=out_dtype)
 
 
 def segment_batch(imgs, mode="per_image", **kw) -> np.ndarray:
     """(B,H,W,3) uint8 -> (B,H,W) int32; equals stack([segment(i) for i in imgs]) in per_image mode."""
     out_dtype = kw.pop("out_dtype", np.int32)
+    _need_cut(kw)
     return _plan(kw).segment_batch(imgs, mode, out_dtype=out_dtype)
 
 
@@ -2238,9 +2352,11 @@ def segment_regions(img, adjacency=False, gradient=False, **kw):
     if gradient and not adjacency:
         raise ValueError("gradient=True needs adjacency=True (the gradient is the strength plane of the adjacency graph)")
     from .regions import region_table, adjacency_table
+    _need_cut(kw)
     torch = _torch()
     img = _one_image(img)
     seg = _plan(kw)
+    seg._last_plane = None                                         # only a plane this very call's step leaves is taken below
     labels = seg(img)
     dev = seg.ops.device
     imgs_d = torch.from_numpy(img[None]).to(dev)
@@ -2249,7 +2365,11 @@ def segment_regions(img, adjacency=False, gradient=False, **kw):
     table = region_table(sums[0].cpu().numpy(), bbox[0].cpu().numpy())
     if adjacency:
         k = int(sums.shape[1])
-        strength = seg.edges_device(imgs_d) if gradient else None
+        strength = None
+        if gradient:                                               # SPEC.md §23: the tree's step has left the plane of this image
+            strength, seg._last_plane = seg._last_plane, None
+            if strength is None or tuple(strength.shape) != tuple(lab_d.shape):    # (no such step ran: the map on its own)
+                strength = seg.edges_device(imgs_d)
         edges, vals, count = seg.region_adjacency_device(lab_d, K=k, imgs=imgs_d, strength=strength)
         if int(count[0]) < 0:                                      # more edges than the default capacity: once more at the largest
             edges, vals, count = seg.region_adjacency_device(lab_d, K=k, imgs=imgs_d, strength=strength, capacity=16384)

@@ -662,6 +662,38 @@ int gcs_region_adjacency_cuts(const int32_t *edges_dev, const uint64_t *vals_dev
 int gcs_feature_gradient(const uint16_t *feats_slab_dev, int B, int H, int W, int n_scales, int n_orient, int32_t *grad_out_dev,
                          gcs_stream_t stream);
 
+/* ---- region tree merged by boundary strength, from an edge table (SPEC.md §23) ---- */
+
+/* The tree of SPEC.md §14 with the cost of an adjacent pair of groups cost(A, B) = floor(128 s / l), l and s = the length and the
+ * strength of SPEC.md §20 summed over the leaf edges between A and B (256 times the mean of the strength plane over the pixels on
+ * both sides of the common boundary; computed as 128 q + floor(128 r / l), s = q l + r; below 2^40 for s <= 2^32 l). Rounds, ties,
+ * merge list and outputs are §14's, so gcs_region_tree_cut, gcs_region_tree_contours, the sweeps, gcs_region_props_cuts and
+ * gcs_region_adjacency_cuts consume the result unchanged. On a merge the edges of the dead node move to the rep, edges that become
+ * parallel add their l and s, the pair's own edge disappears. No features, no node statistics, no float.
+ * Precondition: 1 <= l < 2^57 and s <= 2^32 l in every row and every sum of rows (every table of gcs_region_adjacency meets it).
+ * Beyond it a cost no longer fits the 40 bits the picks give it and the merge order is undefined (every access stays in bounds,
+ * every output element is still written); l = 0 counts as 1.
+ *   gcs_region_tree_edges  one launch: a workgroup per image runs every round. edges_dev int32 [B][E_cap][2], vals_dev uint64
+ *                          [B][E_cap][3] and count_dev int32 [B] are what gcs_region_adjacency wrote (the contrast column is not
+ *                          read; a row with a label outside 0 .. K-1, with a = b or with a label that is not in use is ignored; rows
+ *                          of the same pair add up). used_dev int32 [B][K]: not 0 = the label owns a pixel (a per-label pixel count
+ *                          or the flags of gcs_label_used); alive = the number of such labels. A label in use without an edge never
+ *                          merges. An image with count outside 0 .. E_cap (-1: more edges than E_cap) gets alive as defined, every row
+ *                          (-1, -1) with cost 0; the other images are unaffected.
+ *                          workspace_dev: gcs_region_tree_edges_workspace_bytes(B, K, E_cap) bytes, 8-byte aligned.
+ *                            merges_out_dev int32 [B][K-1][2], costs_out_dev uint64 [B][K-1] (may be NULL), alive_out_dev int32 [B]
+ *   gcs_label_used         one launch: used_out_dev int32 [B][K] = 1 where a pixel of labels_dev int32 [B][H][W] carries the label, else 0.
+ * Every output element is written; outputs and workspace may hold anything on entry; inputs are read only. Integer adds and minima
+ * only: the same bits in any execution order. No allocation, no host synchronisation (capturable). GCS_EINVAL, with nothing
+ * launched: a NULL pointer (costs_out_dev may be; merges_out_dev with K = 1 may be), B outside 1..65535, K outside 1..4096, E_cap
+ * outside 1..16384, H or W outside 1..4096. gcs_region_tree_edges_workspace_bytes returns 0 for such a shape.
+ * Added within ABI 18: new entry points change no existing call, so GCS_ABI_VERSION did not move. */
+size_t gcs_region_tree_edges_workspace_bytes(int B, int K, int E_cap);
+int gcs_region_tree_edges(const int32_t *edges_dev, const uint64_t *vals_dev, const int32_t *count_dev, const int32_t *used_dev, int B,
+                          int K, int E_cap, void *workspace_dev, int32_t *merges_out_dev, uint64_t *costs_out_dev,
+                          int32_t *alive_out_dev, gcs_stream_t stream);
+int gcs_label_used(const int32_t *labels_dev, int B, int H, int W, int K, int32_t *used_out_dev, gcs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
