@@ -54,6 +54,9 @@ of the k-means map of K clusters (SPEC.md §21: `Segmenter(tree_nodes="clusters"
 `--edges [--smoothing K] [--n-orient N --color-weight W --chroma-gain G]`: the texture-gradient edge map of the 24 images (SPEC.md
 §22: `Segmenter.edges_device`, no clustering) swept at 256 absolute thresholds (`evaluate_gpu.edge_sweep_resident`, one step for the
 whole set): ODS with its threshold and OIS of the map.
+`--texton-edges [--radius R] [--k K] [--smoothing S] [--n-orient N --color-weight W --chroma-gain G]`: the same sweep for the three maps
+of SPEC.md §24 on the plan's k-means map (default R = 8, K = 8, 8 directions): E = floor(sqrt(TG * G))
+(`Segmenter.texton_edges_device`), TG alone (`joined=False`) and G (`edges_device`), one row each.
 """
 import os
 import sys
@@ -280,7 +283,43 @@ def edge_rows(n_orient, cw, g, smoothing, levels=256):
                                                                     best["ODS_regions"], best["OIS"]))
 
 
+def texton_edge_rows(n_orient, cw, g, smoothing, k, radius, levels=256):
+    """`--texton-edges`: E, TG and G (SPEC.md §24, §22) of the 24 val images at `levels` absolute thresholds each."""
+    import numpy as np
+    import torch
+    from gabor_color_image_segmentation_amd import Segmenter
+    from gabor_color_image_segmentation_amd.evaluate import ods_ois
+    from gabor_color_image_segmentation_amd.evaluate_gpu import edge_sweep_resident
+    from gabor_color_image_segmentation_amd.groundtruth import PackedTruth
+    gold = os.path.join(ROOT, "tests", "golden")
+    pack = np.load(os.path.join(gold, "bsd_val_images.npz"))
+    truth = PackedTruth(os.path.join(gold, "bsd500_truth.npz"))
+    ids = [str(i) for i in pack["ids"]]
+    seg = Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, smoothing=smoothing, k=k)
+    groups = [[i for i in ids if pack["img_" + i].shape[:2] == shape] for shape in sorted({pack["img_" + i].shape[:2] for i in ids})]
+    batches = [torch.from_numpy(np.stack([pack["img_" + i] for i in group])).cuda() for group in groups]
+    print("| map | n_orient | w | g | K | k | radius | levels | step | ODS | threshold | OIS |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|")
+    for name, make in (("E", lambda d: seg.texton_edges_device(d, radius=radius)),
+                       ("TG", lambda d: seg.texton_edges_device(d, radius=radius, joined=False)),
+                       ("G", lambda d: seg.edges_device(d))):
+        maps = [make(d) for d in batches]
+        step = -(-(max(int(m.max()) for m in maps) + 1) // levels)          # one step for the set: the thresholds are absolute
+        table = []
+        for group, m in zip(groups, maps):
+            table += edge_sweep_resident(m, truth.to_device(group), levels=levels, step=step)[2].tolist()
+        best = ods_ois(table, [step * (tau + 1) - 1 for tau in range(levels)])
+        print("| %s | %d | %g | %d | %g | %d | %d | %d | %d | %.4f | %s > %d | %.4f |" % (
+            name, n_orient, cw, g, smoothing, k, radius, levels, step, best["ODS"], name, best["ODS_regions"], best["OIS"]))
+
+
 if __name__ == '__main__':
+    if "--texton-edges" in sys.argv:
+        def opt(name, conv, default):
+            return conv(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
+        texton_edge_rows(opt("--n-orient", int, 6), opt("--color-weight", float, 0.0), opt("--chroma-gain", int, 0),
+                         opt("--smoothing", float, 0.0), opt("--k", int, 8), opt("--radius", int, 8))
+        sys.exit(0)
     if "--edges" in sys.argv:
         def opt(name, conv, default):
             return conv(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default

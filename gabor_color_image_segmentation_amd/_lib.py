@@ -100,6 +100,8 @@ SIGNATURES = {
     "gcs_region_tree_edges_workspace_bytes": (_sz, [_i, _i, _i]),
     "gcs_region_tree_edges": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "gcs_label_used": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "gcs_texton_masks": (_i, [_i, _i, _vp]),
+    "gcs_texton_gradient": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -28,6 +28,14 @@ int gcs_cu_count();
 static inline int round_up(int a, int m) { return (a + m - 1) / m * m; }
 static inline int mtiles(int F) { return (F + 3) / 4; }   // 32-row MFMA tiles of a level: four filters each (csrc/abi.hip)
 
+// floor(sqrt(e)) for e < 2^52 (SPEC.md §22, §24): the double root is within one of it, the integer steps make it exact.
+__device__ __forceinline__ int fg_isqrt(unsigned long long e) {
+    unsigned long long r = (unsigned long long)sqrt((double)e);
+    while (r * r > e) --r;
+    while ((r + 1) * (r + 1) <= e) ++r;
+    return (int)r;
+}
+
 // ------------------------------------------------------------------------ slab geometry
 // The feature slab keeps every pyramid level at its own resolution (SPEC.md §3). The image is cut into
 // 8x8-pixel BLOCKS; a block owns 8x8 level-0 pixel SLOTS (iy, ix) and the slots of their parents: 4x4 level-1, 2x2 level-2

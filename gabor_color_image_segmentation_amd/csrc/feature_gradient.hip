@@ -73,14 +73,6 @@ __device__ __forceinline__ u64 fg_level(const GcsLayout &lo, const unsigned char
     return (dx >> (2 * L)) + (dy >> (2 * L));
 }
 
-// floor(sqrt(e)) for e < 2^52: the double root is within one of it, the integer steps make it exact.
-__device__ __forceinline__ int fg_isqrt(u64 e) {
-    u64 r = (u64)sqrt((double)e);
-    while (r * r > e) --r;
-    while ((r + 1) * (r + 1) <= e) ++r;
-    return (int)r;
-}
-
 template <bool SPLIT>
 __global__ __launch_bounds__(FG_THREADS) void fg_kernel(const unsigned char *__restrict__ slab, GcsLayout lo, int32_t *__restrict__ out) {
     __shared__ u64 s_term[64 + 16 + 4];                                   // level 1: 4 x 16, level 2: 2 x 8, level 3: 1 x 4

@@ -1,0 +1,199 @@
+// texton_gradient.hip — the texton gradient of SPEC.md §24: per pixel and direction the chi-square distance between the label
+// histograms of the two halves of a disc, the maximum over the directions, optionally joined with an edge map G (§22) as
+// floor(sqrt(TG * G)).
+//
+//   tg_kernel   one workgroup per 8 x 32 output pixels, one thread per pixel. The tile and its halo are (8 + 2r) rows of
+//               32 + 2r <= 62 columns, so ONE ROW OF ONE LABEL'S INDICATOR PLANE IS ONE 64-BIT WORD in LDS. Load phase: a wave owns
+//               whole halo rows (a lane per column, mirrored through two small index tables), and one ballot per label the row
+//               holds is that label's word - no atomics, and the labels the window holds fall out as a bit mask. Count phase: a
+//               pixel at tile column c takes window = (word >> c) & (2^(2r+1) - 1) of every row of its disc; a half's count is the
+//               sum of popcount(window & mask row), the mask rows being wave-uniform: LDS broadcasts of a copy of the table laid out
+//               as the loop walks it (-DGCS_TG_SCALAR_MASKS: scalar loads from the caller's table instead). Directions go CH at a
+//               time so that their counters are registers; labels absent from the tile's window are skipped for the whole
+//               workgroup (-DGCS_TG_NO_SKIP: every label 0 .. K-1 is walked). Both flags are for same-box A/B runs: DESIGN.md §4.22.
+// The kernel knows no trigonometry: gcs_texton_masks (host) makes §24's table, and any table of 2r + 1 rows of 2r + 1 bits is exact.
+// No workspace, no allocation, no host synchronisation: one launch (capturable).
+#include <math.h>
+
+#include "common.h"
+
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr int TG_TW = 32, TG_TH = 8, TG_THREADS = TG_TW * TG_TH, TG_WAVES = TG_THREADS / 64;
+constexpr int TG_R_MAX = 15, TG_N_MAX = 16, TG_K_MAX = 64, TG_HW_MAX = 4096;
+constexpr int TG_ROWS_MAX = TG_TH + 2 * TG_R_MAX, TG_COLS_MAX = TG_TW + 2 * TG_R_MAX;      // 38 rows of 62 columns
+static_assert(TG_COLS_MAX <= 64, "a halo row must fit one 64-bit word and one wave");
+
+// mir(t, N) of SPEC.md §24: reflection without repeating the edge pixel, any t.
+__device__ __forceinline__ int tg_mirror(int t, int N) {
+    if (N == 1) return 0;
+    const int p = 2 * (N - 1);
+    int u = t % p;
+    if (u < 0) u += p;
+    return u < N ? u : p - u;
+}
+
+// floor(64 (g - h)^2 / (g + h)), 0 for g + h = 0. g, h <= 961 (a 31 x 31 frame): the numerator is below 2^26, the quotient below
+// 2^17, so the float estimate (conversion, reciprocal and product: relative error below 2^-21) is within one of the quotient and
+// the integer steps (two each way) make it exact for any mask table.
+__device__ __forceinline__ unsigned tg_chi_term(unsigned g, unsigned h) {
+    const unsigned s = g + h, d = g > h ? g - h : h - g;
+    const unsigned num = 64u * d * d, den = s ? s : 1u;
+    unsigned q = (unsigned)((float)num * __builtin_amdgcn_rcpf((float)den));
+    int rem = (int)(num - q * den);
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        if (rem < 0) --q, rem += (int)den;
+        if (rem >= (int)den) ++q, rem -= (int)den;
+    }
+    return q;
+}
+
+template <int CH>
+__global__ __launch_bounds__(TG_THREADS) void tg_kernel(const int32_t *__restrict__ lab, int H, int W, int K, int r, int n,
+                                                        const uint32_t *__restrict__ masks, const int32_t *__restrict__ grad,
+                                                        int32_t *__restrict__ out, uint8_t *__restrict__ dir_out) {
+    __shared__ u64 s_plane[TG_K_MAX * TG_ROWS_MAX];          // [label][halo row]: bit c = halo column c holds the label
+    __shared__ int s_my[TG_ROWS_MAX], s_mx[TG_COLS_MAX];     // mirrored image row / column of every halo row / column
+    __shared__ u64 s_present[TG_WAVES];                      // labels each wave met
+#ifndef GCS_TG_SCALAR_MASKS
+    // the mask rows as the count loop reads them: [chunk of CH directions][row][direction in chunk][side], zeros past direction n
+    __shared__ __attribute__((aligned(16))) uint32_t s_mask[2 * TG_N_MAX * (2 * TG_R_MAX + 1)];
+#endif
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int y0 = (int)blockIdx.y * TG_TH, x0 = (int)blockIdx.x * TG_TW;
+    const int R = 2 * r + 1, rows = TG_TH + 2 * r, cols = TG_TW + 2 * r;
+    for (int idx = tid; idx < K * rows; idx += TG_THREADS) s_plane[idx] = 0ull;
+    if (tid < rows) s_my[tid] = tg_mirror(y0 - r + tid, H);
+    if (tid >= 64 && tid < 64 + cols) s_mx[tid - 64] = tg_mirror(x0 - r + tid - 64, W);
+#ifndef GCS_TG_SCALAR_MASKS
+    for (int idx = tid; idx < (n + CH - 1) / CH * R * 2 * CH; idx += TG_THREADS) {
+        const int e = idx % (2 * CH), m = idx / (2 * CH) % R, i = idx / (2 * CH * R) * CH + (e >> 1);
+        s_mask[idx] = i < n ? masks[(2 * i + (e & 1)) * R + m] : 0u;
+    }
+#endif
+    __syncthreads();
+
+    // ---- load: wave w owns halo rows w, w + 4, ...; a lane per halo column
+    const int32_t *img = lab + (size_t)blockIdx.z * (size_t)H * (size_t)W;
+    u64 met = 0ull;
+    for (int row = wave; row < rows; row += TG_WAVES) {
+        int l = -1;
+        if (lane < cols) l = img[(size_t)s_my[row] * (size_t)W + (size_t)s_mx[lane]];
+        const bool counted = (unsigned)l < (unsigned)K;      // a value outside 0 .. K-1 counts in no bin
+        u64 todo = __ballot(counted);
+        while (todo) {                                       // wave-uniform: one turn per label of the row
+            const int l0 = __builtin_amdgcn_readlane(l, __ffsll((long long)todo) - 1);
+            const u64 word = __ballot(counted && l == l0);
+            if (lane == 0) s_plane[l0 * rows + row] = word;
+            met |= 1ull << l0;
+            todo &= ~word;
+        }
+    }
+    if (lane == 0) s_present[wave] = met;
+    __syncthreads();
+
+    // ---- count: a thread per output pixel
+#ifdef GCS_TG_NO_SKIP
+    u64 present = K == 64 ? ~0ull : (1ull << K) - 1ull;
+#else
+    u64 present = s_present[0] | s_present[1] | s_present[2] | s_present[3];
+#endif
+    present = (u64)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)present) |
+              (u64)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(present >> 32)) << 32;
+    const int ty = tid / TG_TW, tx = tid % TG_TW;
+    const unsigned full = (1u << R) - 1u;                    // R <= 31
+    unsigned best = 0u;
+    int best_dir = 0;
+    for (int i0 = 0; i0 < n; i0 += CH) {
+        unsigned chi[CH];
+#pragma unroll
+        for (int u = 0; u < CH; ++u) chi[u] = 0u;
+        for (u64 pm = present; pm; pm &= pm - 1ull) {
+            const u64 *pl = s_plane + (__ffsll((long long)pm) - 1) * rows + ty;
+            unsigned g[CH], h[CH];
+#pragma unroll
+            for (int u = 0; u < CH; ++u) g[u] = h[u] = 0u;
+            for (int m = 0; m < R; ++m) {
+                const unsigned win = (unsigned)(pl[m] >> tx) & full;
+#ifndef GCS_TG_SCALAR_MASKS
+                const uint4 *row = reinterpret_cast<const uint4 *>(s_mask + (i0 / CH * R + m) * 2 * CH);      // one address: broadcast
+#pragma unroll
+                for (int u = 0; u < CH; u += 2) {
+                    const uint4 q = row[u >> 1];
+                    g[u] += (unsigned)__popc(win & q.x), h[u] += (unsigned)__popc(win & q.y);
+                    g[u + 1] += (unsigned)__popc(win & q.z), h[u + 1] += (unsigned)__popc(win & q.w);
+                }
+#else
+#pragma unroll
+                for (int u = 0; u < CH; ++u) {
+                    // directions past n: direction n - 1's rows with nothing kept (empty halves, chi 0, never the first maximum);
+                    // unconditional scalar loads, no branch in this loop
+                    const int i = i0 + u < n ? i0 + u : n - 1;
+                    const unsigned keep = i0 + u < n ? ~0u : 0u;
+                    g[u] += (unsigned)__popc(win & masks[(2 * i) * R + m] & keep);
+                    h[u] += (unsigned)__popc(win & masks[(2 * i + 1) * R + m] & keep);
+                }
+#endif
+            }
+#pragma unroll
+            for (int u = 0; u < CH; ++u) chi[u] += tg_chi_term(g[u], h[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < CH; ++u)
+            if (chi[u] > best) best = chi[u], best_dir = i0 + u;     // the lowest direction that attains the maximum
+    }
+    const int y = y0 + ty, x = x0 + tx;
+    if (y >= H || x >= W) return;
+    const size_t at = ((size_t)blockIdx.z * (size_t)H + (size_t)y) * (size_t)W + (size_t)x;
+    if (grad) {
+        const int gv = grad[at];                              // TG < 2^17 and G < 2^31: the product is below 2^48
+        out[at] = fg_isqrt((u64)best * (u64)(gv > 0 ? gv : 0));
+    } else {
+        out[at] = (int32_t)best;
+    }
+    if (dir_out) dir_out[at] = (uint8_t)best_dir;
+}
+
+}  // namespace
+
+extern "C" int gcs_texton_masks(int r, int n, uint32_t *masks_out) {
+    if (!masks_out) return gcs_fail(GCS_EINVAL, "gcs_texton_masks: NULL pointer");
+    if (r < 1 || r > TG_R_MAX || n < 1 || n > TG_N_MAX)
+        return gcs_fail(GCS_EINVAL, "gcs_texton_masks: bad argument (1 <= r <= 15, 1 <= n <= 16)");
+    const int R = 2 * r + 1;
+    const double pi = 3.14159265358979323846;
+    for (int i = 0; i < n; ++i) {
+        const int a = (int)floor(1024.0 * cos(pi * i / n) + 0.5), b = (int)floor(1024.0 * sin(pi * i / n) + 0.5);
+        for (int dy = -r; dy <= r; ++dy) {
+            uint32_t ma = 0u, mb = 0u;
+            for (int dx = -r; dx <= r; ++dx) {
+                if (dy * dy + dx * dx > r * r) continue;
+                const int s = dx * a + dy * b;
+                if (s > 0) ma |= 1u << (dx + r);
+                if (s < 0) mb |= 1u << (dx + r);
+            }
+            masks_out[(2 * i) * R + dy + r] = ma;
+            masks_out[(2 * i + 1) * R + dy + r] = mb;
+        }
+    }
+    return GCS_OK;
+}
+
+extern "C" int gcs_texton_gradient(const int32_t *labels, int B, int H, int W, int K, int r, int n, const uint32_t *masks,
+                                   const int32_t *grad, int32_t *out, uint8_t *dir_out, gcs_stream_t stream) {
+    if (!labels || !masks || !out) return gcs_fail(GCS_EINVAL, "gcs_texton_gradient: NULL pointer");
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || H > TG_HW_MAX || W > TG_HW_MAX)
+        return gcs_fail(GCS_EINVAL, "gcs_texton_gradient: bad shape (1 <= B <= 65535, 1 <= H, W <= 4096)");
+    if (K < 1 || K > TG_K_MAX || r < 1 || r > TG_R_MAX || n < 1 || n > TG_N_MAX)
+        return gcs_fail(GCS_EINVAL, "gcs_texton_gradient: bad argument (1 <= K <= 64, 1 <= r <= 15, 1 <= n <= 16)");
+    const dim3 grid((W + TG_TW - 1) / TG_TW, (H + TG_TH - 1) / TG_TH, B);
+    if (n > 4)
+        hipLaunchKernelGGL(tg_kernel<8>, grid, dim3(TG_THREADS), 0, stream, labels, H, W, K, r, n, masks, grad, out, dir_out);
+    else
+        hipLaunchKernelGGL(tg_kernel<4>, grid, dim3(TG_THREADS), 0, stream, labels, H, W, K, r, n, masks, grad, out, dir_out);
+    GCS_CHECK_LAUNCH("gcs_texton_gradient");
+    return GCS_OK;
+}

@@ -217,6 +217,7 @@ class HipOps:
         self.packed = torch.from_numpy(packed).to(self.device)
         self.bias = torch.from_numpy(bias).to(self.device)
         self._gabor_ws = None
+        self._texton_masks = {}                  # SPEC.md §24: the half-disc tables on the device, per (r, n)
         self.chroma_gain = _check_chroma_gain(chroma_gain)        # SPEC.md §11 (0: colour_opponent is never called)
         # SPEC.md §10: the smoothing taps of every scale on the device (K = 0: none, and smooth_features is never called)
         self.smoothing = _check_smoothing(smoothing, bank)
@@ -621,6 +622,38 @@ class HipOps:
         _lib.check(self.lib.gcs_feature_gradient(feats.data_ptr(), b, h, w, *self._bk, out.data_ptr(), self._stream()),
                    "gcs_feature_gradient")
 
+    def texton_masks(self, r, n):
+        """SPEC.md §24: the half-disc table of radius ``r`` and ``n`` directions, a (n, 2, 2r+1) int32 device tensor holding the
+        uint32 rows of gcs_texton_masks; made on the host once per (r, n) and kept (a captured step must find it made)."""
+        key = (int(r), int(n))
+        if key not in self._texton_masks:
+            if not (1 <= key[0] <= 15 and 1 <= key[1] <= 16):
+                raise ValueError("the texton gradient takes a radius in 1..15 and 1..16 directions")
+            host = np.zeros((key[1], 2, 2 * key[0] + 1), np.uint32)
+            _lib.check(self.lib.gcs_texton_masks(key[0], key[1], host.ctypes.data), "gcs_texton_masks")
+            self._texton_masks[key] = self.torch.from_numpy(host.view(np.int32)).to(self.device)
+        return self._texton_masks[key]
+
+    @_on_device
+    def texton_gradient(self, labels, b, h, w, K, r, n, grad, out, dir_out, masks=None):
+        """SPEC.md §24: the texton gradient of the (B,H,W) int32 label map ``labels`` (values outside 0 .. K-1 count nowhere) at
+        radius ``r`` and ``n`` directions into ``out``, a contiguous (B,H,W) int32 tensor: TG, or floor(sqrt(TG * grad)) with
+        ``grad`` a (B,H,W) int32 edge map (None: TG). ``dir_out``: (B,H,W) uint8 or None. ``masks``: a (n, 2, 2r+1) int32 device
+        tensor in place of ``texton_masks(r, n)`` (any table is exact). One launch, no workspace (capturable as it is)."""
+        i32 = self.torch.int32
+        for name, t in (("labels", labels), ("grad", grad), ("out", out)):
+            self._need(t, i32, (b, h, w), f"{name} must be a contiguous (B,H,W) int32 tensor")
+        self._need(dir_out, self.torch.uint8, (b, h, w), "dir_out must be a contiguous (B,H,W) uint8 tensor")
+        if labels is None or out is None:
+            raise ValueError("labels and out must be contiguous (B,H,W) int32 tensors")
+        if masks is None:
+            masks = self.texton_masks(r, n)
+        self._need(masks, i32, (int(n), 2, 2 * int(r) + 1), "masks must be a contiguous (n, 2, 2r+1) int32 tensor")
+        _lib.check(self.lib.gcs_texton_gradient(labels.data_ptr(), b, h, w, int(K), int(r), int(n), masks.data_ptr(),
+                                                None if grad is None else grad.data_ptr(), out.data_ptr(),
+                                                None if dir_out is None else dir_out.data_ptr(), self._stream()),
+                   "gcs_texton_gradient")
+
     def region_tree_edges_buffers(self, b, h, w, K, capacity=EDGES_MAX):
         """What SPEC.md §23 needs for one (batch, shape, K): ``(stage, merges (B, K-1, 2) int32, costs (B, K-1) int64, alive (B,)
         int32)``, the shape of ``region_tree_buffers``; ``stage`` is a dict of the plane G (``grad``), the leaf table of SPEC.md §20
@@ -974,6 +1007,16 @@ def _stage_buffers(ops, opt, ws, key, b, h, w):
 
 
 _BOUNDARY_OPS = ("region_tree_edges_buffers", "feature_gradient", "label_used", "region_adjacency", "region_tree_edges")
+
+
+def _check_texton(radius, n_directions):
+    """SPEC.md §24: the radius and the number of directions of the texton gradient as integers."""
+    r, n = _as_int(radius), _as_int(n_directions)
+    if not 1 <= r <= 15:
+        raise ValueError(f"radius must be in 1..15, got {radius!r}")
+    if not 1 <= n <= 16:
+        raise ValueError(f"n_directions must be in 1..16, got {n_directions!r}")
+    return r, n
 
 
 def _check_merge_cost(merge_cost):
@@ -1862,6 +1905,64 @@ class Segmenter:
             self.ops.feature_gradient(ws["feats"], b, h, w, out)
         return out
 
+    def texton_gradient_device(self, labels, K=None, radius=8, n_directions=8, gradient=None, directions=False):
+        """(B,H,W) int32 device label map -> (B,H,W) int32 texton gradient of SPEC.md §24: the largest chi-square distance, over
+        ``n_directions`` directions, between the label histograms of the two halves of a disc of ``radius`` pixels (mirrored at
+        the border). ``K``: the number of labels (None: one read of ``labels.max()`` from the device; at most 64; values outside
+        0 .. K-1 count in no bin). ``gradient``: a (B,H,W) int32 edge map G >= 0 (``edges_device``): the result is then
+        floor(sqrt(TG * G)). ``directions=True``: returns ``(map, dir)``, dir (B,H,W) uint8 = the lowest direction of the
+        maximum, 0 where TG = 0."""
+        if not hasattr(self.ops, "texton_gradient"):
+            raise ValueError("the texton gradient needs ops that have it")
+        torch = _torch()
+        if getattr(labels, "ndim", 0) != 3 or labels.dtype != torch.int32:
+            raise ValueError("labels must be a (B,H,W) int32 device tensor")
+        r, n = _check_texton(radius, n_directions)
+        labels = labels.contiguous()
+        b, h, w = labels.shape
+        with self._device():
+            K = int(labels.max()) + 1 if K is None else _as_int(K)
+            if not 1 <= K <= 64:
+                raise ValueError(f"the texton gradient takes 1 <= K <= 64 labels, got {K}")
+            out = torch.empty((b, h, w), dtype=torch.int32, device=labels.device)
+            dirs = torch.empty((b, h, w), dtype=torch.uint8, device=labels.device) if directions else None
+            self.ops.texton_gradient(labels, b, h, w, K, r, n, None if gradient is None else gradient.contiguous(), out, dirs)
+        return (out, dirs) if directions else out
+
+    def texton_edges_device(self, imgs, radius=8, n_directions=8, mode="per_image", joined=True):
+        """(B,H,W,3) uint8 device tensor -> (B,H,W) int32 edge map E = floor(sqrt(TG * G)) of SPEC.md §24, the whole chain on one
+        feature slab: the features, G = the texture gradient of §22 (``edges_device``), the plan's Lloyd loop (``mode`` as in
+        ``segment_device``), its int32 label map, and the texton gradient TG of that map at ``radius`` and ``n_directions``.
+        ``joined=False``: TG alone (G is not computed). The labels are the plain k-means map: a plan with ``n_superpixels > 0``,
+        ``tree_nodes = "clusters"`` or a post-pass (``connectivity``, ``min_region_size``) is refused, and so are row strips, a
+        ``dist_group`` (there is no such argument) and a global codebook over more than one rank."""
+        for name in ("texton_gradient", "feature_gradient"):
+            if not hasattr(self.ops, name):
+                raise ValueError("the texton edge map needs ops that have it")
+        if self.n_superpixels > 0 or self._clusters or self._post_passes:
+            raise ValueError("texton_edges_device needs the plain k-means map (no n_superpixels, tree_nodes or post-pass)")
+        r, n = _check_texton(radius, n_directions)
+        self._check_args(imgs, mode, kind="tensor")
+        if mode == "global":
+            import torch.distributed as td
+            if td.is_available() and td.is_initialized() and td.get_world_size() > 1:
+                raise ValueError("texton_edges_device runs on one rank only")
+        torch = _torch()
+        imgs = imgs.contiguous()
+        b, h, w, _ = imgs.shape
+        with self._device():
+            ws = self._tail_workspace(b, h, w, mode)
+            _step_features(self.ops, self._opt, ws, imgs, b, h, w)
+            grad = None
+            if joined:
+                grad = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
+                self.ops.feature_gradient(ws["feats"], b, h, w, grad)
+            labels = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
+            _step_cluster(self.ops, self._opt, ws, labels, b, h, w, mode, self.debug)
+            out = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
+            self.ops.texton_gradient(labels, b, h, w, self._opt.k, r, n, grad, out, None)
+        return out
+
     # ---- host API: the slot
     def segment_batch(self, imgs: np.ndarray, mode="per_image", out_dtype=np.int32) -> np.ndarray:
         """(B,H,W,3) uint8 host array -> fresh (B,H,W) host label array (the calling convention of script.py:25,30).
@@ -2315,6 +2416,21 @@ def segment_edges(img, **kw) -> np.ndarray:
     if top == 0:
         return np.zeros(g.shape, np.float32)
     return (g.astype(np.float32) / np.float32(top)).astype(np.float32)
+
+
+def segment_texton_edges(img, radius=8, n_directions=8, **kw) -> np.ndarray:
+    """(H,W,3) uint8 -> (H,W) float32 edge strengths in [0, 1]: the map E of SPEC.md §24 (``Segmenter.texton_edges_device``: the
+    texton gradient of the plan's k-means map joined with the texture gradient of §22) divided by its largest value, all zeros
+    for a map that is zero everywhere, as ``segment_edges`` normalises. ``kw``: the plan's options, cached like ``segment``'s."""
+    torch = _torch()
+    img = _one_image(img)
+    seg = _plan(kw)
+    dev = torch.from_numpy(img[None]).to(seg.ops.device) if seg.native else torch.from_numpy(img[None])
+    e = seg.texton_edges_device(dev, radius=radius, n_directions=n_directions)[0].cpu().numpy()
+    top = int(e.max())
+    if top == 0:
+        return np.zeros(e.shape, np.float32)
+    return (e.astype(np.float32) / np.float32(top)).astype(np.float32)
 
 
 def segment_images(images, batch=64, **kw):

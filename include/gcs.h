@@ -694,6 +694,27 @@ int gcs_region_tree_edges(const int32_t *edges_dev, const uint64_t *vals_dev, co
                           int32_t *alive_out_dev, gcs_stream_t stream);
 int gcs_label_used(const int32_t *labels_dev, int B, int H, int W, int K, int32_t *used_out_dev, gcs_stream_t stream);
 
+/* ---- texton gradient of a label map, joined with an edge map (SPEC.md §24) ---- */
+
+/* The chi-square distance between the label histograms of the two halves of a disc of radius r around every pixel, at n directions:
+ * chi_i = the sum over the labels j of floor(64 (g_j - h_j)^2 / (g_j + h_j)) (bins with g_j + h_j = 0 add nothing), g_j / h_j = the
+ * number of offsets of half A / half B of direction i whose pixel, mirrored at the image's border without repeating the edge pixel,
+ * carries label j; TG = the maximum over i, dir = the lowest i that attains it (0 where TG = 0).
+ *   gcs_texton_masks      host only: masks_out uint32 [n][2][2r+1], the half discs of SPEC.md §24 (side 0 = A, 1 = B; row dy + r,
+ *                         bit dx + r). GCS_EINVAL: a NULL pointer, r outside 1..15, n outside 1..16.
+ *   gcs_texton_gradient   one launch. labels_dev int32 [B][H][W]; a value outside 0 .. K-1 counts in no bin. masks_dev: a table laid
+ *                         out as above, on the device; the kernel is exact for ANY table (bits above 2r of a row are ignored), also
+ *                         one whose B is not the mirror image of A. grad_dev int32 [B][H][W] or NULL: given, out = floor(sqrt(TG *
+ *                         G)) with the exact root of SPEC.md §22 (a negative G counts as 0); NULL, out = TG. out_dev int32
+ *                         [B][H][W]; dir_out_dev uint8 [B][H][W] or NULL. TG <= 64 * 2 * 961 < 2^17.
+ * Every output element is written; inputs are read only and must not overlap the outputs. No workspace, no allocation, no host
+ * synchronisation (capturable). GCS_EINVAL, with nothing launched: a NULL pointer (grad_dev and dir_out_dev may be), B outside
+ * 1..65535, H or W outside 1..4096, K outside 1..64, r outside 1..15, n outside 1..16.
+ * Added within ABI 18: new entry points change no existing call, so GCS_ABI_VERSION did not move. */
+int gcs_texton_masks(int r, int n, uint32_t *masks_out);
+int gcs_texton_gradient(const int32_t *labels_dev, int B, int H, int W, int K, int r, int n, const uint32_t *masks_dev,
+                        const int32_t *grad_dev, int32_t *out_dev, uint8_t *dir_out_dev, gcs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
