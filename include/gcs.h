@@ -15,6 +15,14 @@
  * use) between an event fork from and an event join back into `stream` — the pattern stream capture records as a
  * graph. Return 0 on success, GCS_E* otherwise, with a thread-local message in gcs_last_error(). Not thread-safe per
  * buffer.
+ *
+ * Buffers: a buffer of exactly the stated size - an array's element count, or what its *_bytes() function returns - is enough: no
+ * call writes a byte outside it. Unless a function's comment says otherwise, every output and every workspace / scratch buffer may
+ * hold anything on entry (what a call accumulates into is zeroed by the call), every output element is written, workspace and
+ * scratch contents are undefined afterwards, and inputs are read only. The exceptions are named where they occur: buffers updated in
+ * place (the slab under gcs_smooth_features and gcs_position_features, centroids_dev of gcs_kmeans_finalize and
+ * gcs_kmeans_reduce_finalize, leaf_hist_dev of the sweeps), the workspace of gcs_kmeans_pass_fused (the caller zeroes it once), and
+ * the slots of a feature slab that hold no pixel (no call writes them: they keep their bytes).
  */
 #ifndef GCS_H
 #define GCS_H
@@ -98,23 +106,25 @@ size_t gcs_gabor_workspace_bytes(int B, int H, int W, int n_scales);
  * (ksize <= 13 and shift == 8, i.e. every default-style Q15 bank, take the shorter kernels). shift is in 0..23; at shift == 8 the
  * bounds of gcs_bank_pack keep every response a 16-bit value and re^2 + im^2 < 2^31 (features <= 36 635); with any smaller shift
  * the caller guarantees that domain for its bank and images (SPEC.md §3 "Value range": features <= 46 340). workspace_dev:
- * gcs_gabor_workspace_bytes() bytes of device scratch, contents undefined before and after. */
+ * gcs_gabor_workspace_bytes() bytes of device scratch, contents undefined before and after. feats_dev: gcs_feature_slab_bytes()
+ * bytes that may hold anything on entry: every slot that holds a pixel and every flag word of a split slab is written. */
 int gcs_gabor_features(const uint8_t *img_dev, int B, int H, int W, const int8_t *packed_dev,
                        const int32_t *bias_dev, int n_scales, int n_orient, int ksize, int shift, void *workspace_dev,
                        uint16_t *feats_dev, gcs_stream_t stream);
 
-/* Slab -> canonical [B][D][H][W] uint16 (level-L responses replicated over 2^L blocks; tests / debugging). */
+/* Slab -> canonical [B][D][H][W] uint16 (level-L responses replicated over 2^L blocks; tests / debugging). out_dev may hold
+ * anything on entry; every element is written. */
 int gcs_features_unpack(const uint16_t *feats_dev, int B, int H, int W, int n_scales, int n_orient,
                         uint16_t *out_dev, gcs_stream_t stream);
 
 /* SPEC.md §4 init. n_sets == B: per-image codebooks (set s from image s); n_sets == 1:
- * global codebook from image 0. centroids_dev: uint16 [n_sets][k][D]. */
+ * global codebook from image 0. centroids_dev: uint16 [n_sets][k][D], may hold anything on entry, written whole. */
 int gcs_kmeans_init(const uint16_t *feats_dev, int B, int H, int W, int n_scales, int n_orient, int k,
                     int n_sets, uint16_t *centroids_dev, gcs_stream_t stream);
 
 /* out_dev uint16 [n][D] = feature vectors of the n pixels byx_dev[i] = (image, row, col) (int32 triples in
- * device memory); b < 0 yields a zero row. Used to publish init centroids when one image is
- * sharded by rows over several ranks (BASELINE config 5). */
+ * device memory); b < 0 yields a zero row. out_dev may hold anything on entry; every row is written. Used to publish
+ * init centroids when one image is sharded by rows over several ranks (BASELINE config 5). */
 int gcs_features_gather(const uint16_t *feats_dev, int B, int H, int W, int n_scales, int n_orient, int n,
                         const int32_t *byx_dev, uint16_t *out_dev, gcs_stream_t stream);
 
@@ -125,7 +135,7 @@ int gcs_features_gather(const uint16_t *feats_dev, int B, int H, int W, int n_sc
  * Infinity Cache (results do not depend on it). Long sweeps load the part of the slab that no later pass finds in that cache
  * with the nontemporal hint (gcs_selftest_pass_nt_limit): the hint only affects performance, results are identical bit for bit
  * with either load form. labels_dev: uint8 [B][H][W] label map (every pixel of every image is
- * labelled, rows outside the voting window included); partials_dev:
+ * labelled, rows outside the voting window included: B * H * W bytes, no byte behind them is written); partials_dev:
  * gcs_kmeans_partial_bytes() bytes, fully overwritten (no zeroing needed). D <= 207 (every BASELINE bank) runs on
  * the matrix cores, wider feature vectors on a generic VALU pass; k <= GCS_K_MAX. The same n_sets must be passed
  * to the reduce call that follows (it selects the partial layout).
@@ -141,23 +151,27 @@ int gcs_kmeans_assign_accumulate(const uint16_t *feats_dev, const uint16_t *cent
  * (out_u8 != 0). Same result as gcs_kmeans_assign_accumulate(labels, NULL) (followed by gcs_labels_widen for int32).
  * scratch_labels_dev: a uint8 label map (gcs_label_slab_bytes) that is needed, and then also filled, only for int32 output of
  * feature vectors of 208 or more planes (the generic pass); may be NULL otherwise - for D <= 207 it is never written, even when
- * passed. Whole images only (no row window). */
+ * passed. out_dev may hold anything on entry; every element is written. Whole images only (no row window). */
 int gcs_kmeans_assign_raster(const uint16_t *feats_dev, const uint16_t *centroids_dev, int B, int H, int W, int n_scales,
                              int n_orient, int k, int n_sets, int reverse, void *out_dev, int out_u8,
                              uint8_t *scratch_labels_dev, gcs_stream_t stream);
 
 /* partials -> sums_dev int64 [n_sets][k][D+1] ([..][D] = count). Deterministic slab
- * reduction (no float, no atomics). In global mode the caller all-reduces sums_dev across
+ * reduction (no float, no atomics). sums_dev may hold anything on entry: every element is written (nothing is added to what it
+ * held). In global mode the caller all-reduces sums_dev across
  * ranks (RCCL, int64 sum) between this call and gcs_kmeans_finalize. */
 int gcs_kmeans_reduce(const uint64_t *partials_dev, int B, int H, int W, int D, int k, int n_sets,
                       int64_t *sums_dev, gcs_stream_t stream);
 
-/* SPEC.md §4 update: c = floor((2S + n) / (2n)), empty cluster keeps its centroid. */
+/* SPEC.md §4 update: c = floor((2S + n) / (2n)), empty cluster keeps its centroid. centroids_dev uint16 [n_sets][k][D] is
+ * updated in place: on entry it holds the previous centroids; the rows of the clusters that own a pixel are written, the others
+ * are kept. */
 int gcs_kmeans_finalize(const int64_t *sums_dev, int n_sets, int k, int D,
                         uint16_t *centroids_dev, gcs_stream_t stream);
 
 /* Single-rank update: gcs_kmeans_reduce + gcs_kmeans_finalize in ONE launch (no all-reduce needed
- * in between). sums_dev may be NULL (then only the centroids are written). */
+ * in between). sums_dev may be NULL (then only the centroids are written); given, it may hold anything on entry and is written
+ * whole. centroids_dev: in place, as in gcs_kmeans_finalize. */
 int gcs_kmeans_reduce_finalize(const uint64_t *partials_dev, int B, int H, int W, int D, int k,
                                int n_sets, int64_t *sums_dev, uint16_t *centroids_dev,
                                gcs_stream_t stream);
@@ -170,23 +184,31 @@ int gcs_kmeans_reduce_finalize(const uint64_t *partials_dev, int B, int H, int W
  *                                     entry points above): today the split-slab banks (at most two pyramid levels, D <= 79, a
  *                                     tile of at most 12 288 slots) with k <= 8. A pure host function.
  *   workspace_dev                     ZEROED once by the caller when it is allocated; every complete loop (passes 0 .. n - 1, the
- *                                     last with last != 0) leaves it as it found it, whatever n, so loops may follow one another
- *                                     (also as replays of one captured graph). One loop at a time per workspace.
+ *                                     last with last != 0) leaves everything a pass reads before writing it - the sum buffers, the
+ *                                     counter of finished workgroups and all padding: every byte but the two centroid arrays - zero
+ *                                     as it found it, whatever n, so loops may follow one another (also as replays of one captured
+ *                                     graph). The two centroid arrays inside ([n_sets][k][D] uint16 each) keep the centroids of the
+ *                                     loop's last two passes; pass 0 reads neither. This holds for loops of the SAME shape (B, H, W,
+ *                                     bank, k, n_sets): another shape lays the workspace out differently and would find the old
+ *                                     centroids inside its sum buffers, so the caller zeroes the workspace again before it is used
+ *                                     for another shape. One loop at a time per workspace.
  *   pass                              t, counted from 0; `reverse` as in gcs_kmeans_assign_accumulate.
- *   centroids_dev                     uint16 [n_sets][k][D], WRITTEN: the centroids pass t used (nothing is read from it).
- *   out_dev, out_u8                   the raster label map of the last pass, as in gcs_kmeans_assign_raster; ignored otherwise. */
+ *   centroids_dev                     uint16 [n_sets][k][D], WRITTEN whole: the centroids pass t used (nothing is read from it).
+ *   out_dev, out_u8                   the raster label map of the last pass, as in gcs_kmeans_assign_raster (may hold anything
+ *                                     on entry, written whole); ignored otherwise. */
 size_t gcs_kmeans_fused_workspace_bytes(int B, int H, int W, int n_scales, int n_orient, int k, int n_sets);
 int gcs_kmeans_pass_fused(const uint16_t *feats_dev, int B, int H, int W, int n_scales, int n_orient, int k, int n_sets,
                           int reverse, int pass, int last, void *workspace_dev, uint16_t *centroids_dev, void *out_dev,
                           int out_u8, gcs_stream_t stream);
 
-/* uint8 label map [B][H][W] -> int32 [B][H][W] (the dtype handed to metrics.py:43). Both pointers 4-byte aligned. */
+/* uint8 label map [B][H][W] -> int32 [B][H][W] (the dtype handed to metrics.py:43). Both pointers 4-byte aligned. out_dev may
+ * hold anything on entry; every element is written, and no byte behind the B * H * W bytes of labels_dev is needed. */
 int gcs_labels_widen(const uint8_t *labels_dev, int B, int H, int W, int32_t *out_dev,
                      gcs_stream_t stream);
 
 /* Test hook: counts in *bad_dev (uint32, device) the 4096-value chunks of [0, n_max] on which the kernels' 7-instruction
  * exact integer square root and its biased form in the epilogue (SPEC.md §3: n <= 2 * 32767^2 < 2^31, guaranteed by the
- * tap-sum bound of gcs_bank_pack) is wrong. Expected 0. */
+ * tap-sum bound of gcs_bank_pack) is wrong. Expected 0. *bad_dev may hold anything on entry: it is zeroed by the call. */
 int gcs_selftest_isqrt(unsigned n_max, unsigned *bad_dev, gcs_stream_t stream);
 /* Test hook (host only): working workgroups per image of the deep-bank Lloyd pass for a batch shape, computed from the
  * shape's tile count WITHOUT packed edge strips (an upper bound of every bank's tile count; the launcher uses the bank's own
@@ -226,7 +248,8 @@ int gcs_selftest_gabor_plan(int B, int H, int W, int n_scales, int n_orient, int
  * counts_dev uint64 [1 + 3A]: [0] = #boundary pixels of the label map (metrics.py:90); for
  * annotator a: [1+3a] = sum(dilate5(bd(labels)) & bd(T_a)) and [2+3a] = sum(bd(T_a)) (metrics.py:69-72),
  * [3+3a] = sum(bd(labels) & dilate5(bd(T_a))) (metrics.py:93-94). The caller divides and averages in
- * the reference's order. scratch_dev: gcs_boundary_scratch_bytes() bytes. */
+ * the reference's order. scratch_dev: gcs_boundary_scratch_bytes() bytes. scratch_dev and counts_dev may hold anything on entry:
+ * counts_dev is zeroed by the call and every element of it is a result. */
 size_t gcs_boundary_scratch_bytes(int A, int H, int W);
 int gcs_boundary_counts(const int32_t *labels_dev, const uint16_t *truth_dev, int A, int H, int W,
                         void *scratch_dev, uint64_t *counts_dev, gcs_stream_t stream);
@@ -234,7 +257,8 @@ int gcs_boundary_counts(const int32_t *labels_dev, const uint16_t *truth_dev, in
 /* Batched form: labels_dev int32 [B][H][W], truth_dev uint16 [T][H][W] = the annotator maps of image 0, then of image 1, ...
  * (T = total annotators; ragged: BSD500 has 4-9 per image, groundtruth.py:33-50), img_of_dev int32 [T] = image of each
  * annotator map. ONE pair of launches for the whole batch. counts_dev uint64 [B + 3T]: [b] = #boundary pixels of label map
- * b; for annotator t: [B+3t], [B+3t+1], [B+3t+2] = the three sums above. scratch_dev: gcs_boundary_batch_scratch_bytes(). */
+ * b; for annotator t: [B+3t], [B+3t+1], [B+3t+2] = the three sums above. scratch_dev: gcs_boundary_batch_scratch_bytes().
+ * scratch_dev and counts_dev may hold anything on entry: counts_dev is zeroed by the call. */
 size_t gcs_boundary_batch_scratch_bytes(int B, int T, int H, int W);
 int gcs_boundary_counts_batch(const int32_t *labels_dev, const uint16_t *truth_dev, const int32_t *img_of_dev, int B, int T,
                               int H, int W, void *scratch_dev, uint64_t *counts_dev, gcs_stream_t stream);
@@ -248,14 +272,17 @@ int gcs_boundary_counts_batch(const int32_t *labels_dev, const uint16_t *truth_d
  * bd_counts_dev uint64 [T] = sum bd(T_t) (the recall denominators, metrics.py:72), and - when truth8_dev is not NULL - the maps
  * narrowed to uint8 [T][H][W] for gcs_region_counts_batch_u8. The CALLER guarantees that every annotator label is below 256 when
  * it passes truth8_dev (BSD500: at most 208; the narrowing keeps the low byte and does not check: evaluate_gpu.DeviceTruth does).
- * The caller keeps all of it on the device for as long as it scores images of these ids. */
+ * The caller keeps all of it on the device for as long as it scores images of these ids. planes_dev, bd_counts_dev and truth8_dev
+ * may hold anything on entry; every word of the planes (the bits at and beyond column W are 0), every count and every byte of
+ * truth8_dev ([T][H][W] bytes exactly) is written. */
 size_t gcs_bit_planes_bytes(int M, int H, int W);
 int gcs_truth_prepare(const uint16_t *truth_dev, int T, int H, int W, void *planes_dev, uint64_t *bd_counts_dev,
                       uint8_t *truth8_dev, gcs_stream_t stream);
 
 /* gcs_boundary_counts_batch on prepared annotator planes: the same counts_dev uint64 [B + 3T] (every element written, no
  * atomics), from the bit planes of the B label maps (scratch_dev: gcs_bit_planes_bytes(B, H, W)) ANDed with the resident planes.
- * seg_max_dev int32 [B] (may be NULL): the largest label of each map (metrics.py:51 wants max + 1). */
+ * seg_max_dev int32 [B] (may be NULL): the largest label of each map (metrics.py:51 wants max + 1). scratch_dev, counts_dev and
+ * seg_max_dev may hold anything on entry (seg_max_dev is zeroed by the call). */
 int gcs_boundary_counts_resident(const int32_t *labels_dev, const void *truth_planes_dev, const uint64_t *truth_bd_counts_dev,
                                  const int32_t *img_of_dev, int B, int T, int H, int W, void *scratch_dev, uint64_t *counts_dev,
                                  int32_t *seg_max_dev, gcs_stream_t stream);
@@ -267,7 +294,8 @@ int gcs_boundary_counts_resident(const int32_t *labels_dev, const void *truth_pl
  * labels_dev int32 [H][W] with values in [0, n_segments) (metrics.py:51: n_segments = max + 1); truth_dev
  * uint16 [A][H][W] with values < n_truth_labels (the largest `max(truth) + 1` over the annotators,
  * metrics.py:116). Writes hist_dev uint32 [A][n_segments][n_truth_labels], area_dev and perim_dev uint32
- * [n_segments] (zeroed here). The caller does the reference's float arithmetic in the reference's order. */
+ * [n_segments]. hist_dev, area_dev and perim_dev may hold anything on entry: all three are zeroed by the call. The caller does the
+ * reference's float arithmetic in the reference's order. */
 int gcs_region_counts(const int32_t *labels_dev, const uint16_t *truth_dev, int A, int H, int W,
                       int n_segments, int n_truth_labels, uint32_t *hist_dev, uint32_t *area_dev,
                       uint32_t *perim_dev, gcs_stream_t stream);
@@ -275,7 +303,8 @@ int gcs_region_counts(const int32_t *labels_dev, const uint16_t *truth_dev, int 
 /* Batched form (same ragged truth stack as gcs_boundary_counts_batch): first_dev int32 [B+1] = index of each image's first
  * annotator map (first[B] = T), max_annotators = the largest per-image count (it sizes the
  * workgroup-private tables; an image that brings more annotators than stated falls back to global atomics, still exact). hist_dev uint32 [T][n_segments][n_truth_labels],
- * area_dev / perim_dev uint32 [B][n_segments]. One launch for the whole batch. */
+ * area_dev / perim_dev uint32 [B][n_segments]; the three may hold anything on entry and are zeroed by the call. One launch for the
+ * whole batch behind the zeroing. */
 int gcs_region_counts_batch(const int32_t *labels_dev, const uint16_t *truth_dev, const int32_t *first_dev, int B, int T,
                             int max_annotators, int H, int W, int n_segments, int n_truth_labels, uint32_t *hist_dev,
                             uint32_t *area_dev, uint32_t *perim_dev, gcs_stream_t stream);
@@ -283,7 +312,8 @@ int gcs_region_counts_batch(const int32_t *labels_dev, const uint16_t *truth_dev
 /* What metrics.py:128-140 takes from the tables of gcs_region_counts_batch, per annotator map t of image img_of[t]:
  * under_dev[t] = sum_seg (area[seg] - max_col hist[t][seg][col]) (metrics.py:129-130) and under_np_dev[t] = sum_seg sum_col
  * min(hist, rowsum - hist) (metrics.py:137-139), uint64 [T] each, integers. The host divides by H * W and averages over the
- * annotators in the reference's order without ever fetching the tables. */
+ * annotators in the reference's order without ever fetching the tables. under_dev and under_np_dev may hold anything on entry;
+ * every element is written; the tables are read only. */
 int gcs_region_reduce(const uint32_t *hist_dev, const uint32_t *area_dev, const int32_t *img_of_dev, int T, int n_segments,
                       int n_truth_labels, uint64_t *under_dev, uint64_t *under_np_dev, gcs_stream_t stream);
 
@@ -295,7 +325,8 @@ int gcs_region_counts_batch_u8(const int32_t *labels_dev, const uint8_t *truth8_
 /* Everything metrics.get_metrics() (metrics.py:246-255) needs of a batch, on resident ground truth, in one call (six launches:
  * gcs_boundary_counts_resident + gcs_region_counts_batch[_u8] + gcs_region_reduce with their zeroing folded into one launch). truth_maps_dev: the uint8 (truth_is_u8 != 0) or uint16 annotator maps; scratch_dev:
  * gcs_bit_planes_bytes(B, H, W); hist_dev [T][n_segments][n_truth_labels] is scratch the caller may keep on the device; the other
- * outputs as documented at the three calls. */
+ * outputs as documented at the three calls. Every output, hist_dev and scratch_dev may hold anything on entry (the call zeroes
+ * what it accumulates into); the resident planes, counts and maps are read only. */
 int gcs_score_batch_resident(const int32_t *labels_dev, const void *truth_planes_dev, const uint64_t *truth_bd_counts_dev,
                              const void *truth_maps_dev, int truth_is_u8, const int32_t *first_dev, const int32_t *img_of_dev, int B,
                              int T, int max_annotators, int H, int W, int n_segments, int n_truth_labels, void *scratch_dev,
@@ -316,7 +347,8 @@ int gcs_score_batch_resident(const int32_t *labels_dev, const void *truth_planes
  * seg_max_dev int32 [B] (may be NULL; needs img_of_dev int32 [T] = image of map t): rows above seg_max[img_of[t]] are not
  * read (tables allocated at a capacity of segments). scratch_dev: gcs_region_agreement_scratch_bytes(T, n_segments,
  * n_truth_labels) bytes. Float sums run in an order fixed by the table indices alone: the same maps give the same bits at any
- * table shape, from run to run. */
+ * table shape, from run to run. scratch_dev, sums_dev and terms_dev may hold anything on entry; every element of the two outputs
+ * is written; hist_dev is read only. */
 size_t gcs_region_agreement_scratch_bytes(int T, int n_segments, int n_truth_labels);
 int gcs_region_agreement(const uint32_t *hist_dev, const int32_t *img_of_dev, const int32_t *seg_max_dev, int T, int n_segments,
                          int n_truth_labels, void *scratch_dev, uint64_t *sums_dev, double *terms_dev, gcs_stream_t stream);
@@ -326,7 +358,8 @@ int gcs_region_agreement(const uint32_t *hist_dev, const int32_t *img_of_dev, co
 /* labels_dev int32 [B][H][W] -> out_dev int32 [B][H][W]: 4-connected components of equal labels,
  * renumbered 0,1,2,... in raster order of each component's first pixel, per image. Makes
  * `Regions = max + 1` (/root/reference/BSD_metrics/metrics.py:51) count connected regions.
- * scratch_dev: gcs_connected_scratch_bytes() bytes. out_dev may not alias labels_dev. */
+ * scratch_dev: gcs_connected_scratch_bytes() bytes. out_dev may not alias labels_dev. scratch_dev and out_dev may hold anything
+ * on entry; every element of out_dev is written. */
 size_t gcs_connected_scratch_bytes(int B, int H, int W);
 int gcs_connected_regions(const int32_t *labels_dev, int B, int H, int W, void *scratch_dev,
                           int32_t *out_dev, gcs_stream_t stream);
@@ -337,7 +370,8 @@ int gcs_connected_regions(const int32_t *labels_dev, int B, int H, int W, void *
  * of fewer than min_size pixels that has a neighbour joins its largest neighbour (ties: the earlier first pixel), until
  * none is left; numbered 0,1,2,... in raster order of first pixel, per image. min_size <= 1 gives gcs_connected_regions
  * bit for bit. Stream-ordered, no host synchronisation. scratch_dev: gcs_merge_scratch_bytes() bytes (about 20 per pixel;
- * 0 for a bad shape or min_size < 0). out_dev may not alias labels_dev. */
+ * 0 for a bad shape or min_size < 0). out_dev may not alias labels_dev. scratch_dev and out_dev may hold anything on entry; every
+ * element of out_dev is written. */
 size_t gcs_merge_scratch_bytes(int B, int H, int W, int min_size);
 int gcs_merge_small_regions(const int32_t *labels_dev, int B, int H, int W, int min_size, void *scratch_dev,
                             int32_t *out_dev, gcs_stream_t stream);
@@ -368,7 +402,7 @@ int gcs_region_nodes(const int32_t *labels_dev, int B, int H, int W, int min_siz
  * scale whose radius is outside 1..24 or whose taps are negative or do not sum to 4096 is left unsmoothed (the host validates
  * before it uploads; bank.smoothing_taps). Stream-ordered, two launches, no host synchronisation, no allocation (capturable).
  * workspace_dev: gcs_smooth_workspace_bytes() bytes (the level planes, 2 bytes per value; 0 for a bad shape), contents undefined
- * before and after. Requires H, W >= 8. */
+ * before and after. Slab slots that hold no pixel keep their bytes. Requires H, W >= 8. */
 size_t gcs_smooth_workspace_bytes(int B, int H, int W, int n_scales, int n_orient);
 int gcs_smooth_features(uint16_t *feats_dev, int B, int H, int W, int n_scales, int n_orient, const int32_t *taps_dev,
                         const int32_t *radius_dev, void *workspace_dev, gcs_stream_t stream);
@@ -447,6 +481,8 @@ int gcs_superpixel_segment(const uint16_t *feats_canonical_dev, int B, int H, in
  *                                    0 <= a < b < K with both still reps at that step is skipped, as in gcs_region_sweep.
  * A pixel whose label is outside 0 .. K-1 is counted nowhere, is adjacent to nothing and leaves the cut as -1. feats_canonical_dev is
  * the [B][D][H][W] uint16 tensor of gcs_features_unpack. With K = 1 there are no rows: merges / costs pointers are not read.
+ * Every output (merges, costs, alive, labels_out) may hold anything on entry and is written whole; inputs are read only. The one
+ * exception is the in-place cut: labels_out_dev == labels_dev then holds the input on entry, and every element is replaced.
  * GCS_EINVAL, with nothing launched: a NULL feats / labels / workspace / alive / labels_out pointer, a NULL merges pointer with K > 1,
  * B outside 1..65535, H or W outside 1..4096, D outside 1..207, K outside 1..4096, R < 1.
  * Added within ABI 18: new entry points change no existing call, so GCS_ABI_VERSION did not move. */
@@ -488,6 +524,7 @@ int gcs_region_tree_slab(const uint16_t *feats_slab_dev, const int32_t *labels_d
  *                                    counts [b], [B + 3t] and [B + 3t + 2] of gcs_boundary_counts_resident for the cut at R.
  *                                    truth_planes_dev: what gcs_truth_prepare wrote; img_of_dev int32 [T], non-decreasing (the
  *                                    annotators of an image are consecutive). No allocation, no host synchronisation (capturable).
+ * contours_out_dev and hist_out_dev may hold anything on entry and are written whole; inputs are read only.
  * GCS_EINVAL, with nothing launched: a NULL pointer (merges_dev may be NULL with K = 1), contours_out_dev == labels_dev, B outside
  * 1..65535, H or W outside 1..4096, K outside 1..4096, T outside 1..1000000, (B + 2T)(K + 1) >= 2^31.
  * Added within ABI 18: new entry points change no existing call, so GCS_ABI_VERSION did not move. */
@@ -655,7 +692,8 @@ int gcs_region_adjacency_cuts(const int32_t *edges_dev, const uint64_t *vals_dev
  * (y >> L, x >> L), summed over the planes. feats_slab_dev: the slab gcs_gabor_features (and gcs_smooth_features /
  * gcs_position_features) filled for B images of H x W and the bank (n_scales, n_orient = slots per scale), either slab format; every
  * level is read at its own resolution, the canonical tensor is never made. E < 2^41 for any 16-bit values and the root is exact.
- * One launch, no workspace, no allocation, no host synchronisation (capturable). grad_out_dev must not overlap the slab.
+ * One launch, no workspace, no allocation, no host synchronisation (capturable). grad_out_dev must not overlap the slab; it may
+ * hold anything on entry and every element is written.
  * GCS_EINVAL, with nothing launched: a NULL pointer, B outside 1..65535, H or W outside 1..4096, a bank gcs_feature_slab_bytes refuses
  * or of more than 207 features.
  * Added within ABI 18: a new entry point changes no existing call, so GCS_ABI_VERSION did not move. */
@@ -707,7 +745,8 @@ int gcs_label_used(const int32_t *labels_dev, int B, int H, int W, int K, int32_
  *                         one whose B is not the mirror image of A. grad_dev int32 [B][H][W] or NULL: given, out = floor(sqrt(TG *
  *                         G)) with the exact root of SPEC.md §22 (a negative G counts as 0); NULL, out = TG. out_dev int32
  *                         [B][H][W]; dir_out_dev uint8 [B][H][W] or NULL. TG <= 64 * 2 * 961 < 2^17.
- * Every output element is written; inputs are read only and must not overlap the outputs. No workspace, no allocation, no host
+ * Every output element is written (out_dev and dir_out_dev may hold anything on entry; dir_out_dev is B * H * W bytes exactly);
+ * inputs are read only and must not overlap the outputs. No workspace, no allocation, no host
  * synchronisation (capturable). GCS_EINVAL, with nothing launched: a NULL pointer (grad_dev and dir_out_dev may be), B outside
  * 1..65535, H or W outside 1..4096, K outside 1..64, r outside 1..15, n outside 1..16.
  * Added within ABI 18: new entry points change no existing call, so GCS_ABI_VERSION did not move. */
