@@ -83,7 +83,18 @@ size_t gcs_feature_slab_bytes(int B, int H, int W, int n_scales, int n_orient);
  * profiles/r6_notes.md). A Lloyd pass streams the first two arrays and, for flagged tiles only, the third: exact for any data.
  * gcs_feature_slab_bytes(B, ...) == B * gcs_feature_slab_bytes(1, ...) for every bank: image b's slab starts at b times that
  * (callers may hand a sub-batch's part of a slab to any entry point). gcs_feature_pass_bytes: the feature bytes ONE Lloyd
- * pass reads when no tile is flagged (3/4 of the feature bytes of a split slab, all of them otherwise; padding included). */
+ * pass reads when no tile is flagged (3/4 of the feature bytes of a split slab, all of them otherwise; padding included).
+ * Size bounds (img_bytes = gcs_feature_slab_bytes(1, ...); tests/test_gpu_large_offsets.py runs both sides of byte offsets 2^31 and
+ * 2^32, tests/test_large_offset_geometry.py both sides of every bound):
+ *   - one image of a SPLIT slab: img_bytes < 2^32 (held as: value bytes + 4 flag bytes per tile + 256 <= 2^32 - 1), else both size
+ *     functions return 0 and every slab entry point refuses the shape (the MID / TOP / FLAG arrays are addressed by 32-bit offsets
+ *     from the image's base);
+ *   - one image of a wide slab: the size functions take any img_bytes; gcs_gabor_features refuses img_bytes > 2^32 - 1 (32-bit lane
+ *     offsets inside one image);
+ *   - a batch: B * img_bytes is a 64-bit product everywhere, so a slab may be far larger than 4 GiB; gcs_gabor_features refuses B >
+ *     65535 and B * img_bytes >= 2^47; the Lloyd-pass entry points refuse B > 65535 and B * (tiles per image) > 2^29 - 1 (four times
+ *     a tile's position in the batch list is kept in an int);
+ *   - the entry points that take H, W <= 4096 only (gcs_feature_gradient, gcs_region_tree_slab) are inside all of these per image. */
 size_t gcs_feature_pass_bytes(int B, int H, int W, int n_scales, int n_orient);
 size_t gcs_label_slab_bytes(int B, int H, int W);
 /* uint64 partial sums written by one assign pass: one row of k * (D+1) values per k-means workgroup, stored in chunks

@@ -92,12 +92,32 @@ def test_fused_workspace_follows_the_choice(lib, table):
     assert lib.gcs_kmeans_fused_workspace_bytes(3, 40, 56, 4, 6, 8, 2) == 0
 
 
+# The same table, continued past what the fixture recorded: the first batch kp_batch_fits refuses (2048 x 2048 has 16 384 tiles on
+# every bank, 32 768 * 16 384 = 2^29 > 2^29 - 1; 32 767 images fit: tests/test_large_offset_geometry.py) and a split image of more
+# than 2^32 - 1 bytes (30 001 x 1002 on a 2x13 bank: gcs_make_layout refuses it, so "image too large for the split slab's pass" is
+# never reached), through the three entry points.
+_BATCH = "batch too large for one launch"
+LIMIT_ERRORS = [
+    {"fn": "gcs_kmeans_assign_accumulate", "args": ["P", "P", 32768, 2048, 2048, ns, no, 8, n_sets, 0, 2048, 0, "P", "P", None], "rc": 1,
+     "message": "gcs_kmeans_assign_accumulate: " + _BATCH} for ns, no in ((4, 6), (8, 8), (7, 10)) for n_sets in (1, 32768)] + [
+    {"fn": "gcs_kmeans_assign_raster", "args": ["P", "P", 32768, 2048, 2048, 4, 6, 8, 1, 0, "P", 0, None, None], "rc": 1,
+     "message": "gcs_kmeans_assign_accumulate: " + _BATCH},
+    {"fn": "gcs_kmeans_pass_fused", "args": ["P", 32768, 2048, 2048, 4, 6, 8, 1, 0, 0, 0, "P", "P", None, 0, None], "rc": 1,
+     "message": "gcs_kmeans_pass_fused: batch or image too large for one launch"},
+    {"fn": "gcs_kmeans_assign_accumulate", "args": ["P", "P", 1, 30001, 1002, 2, 13, 8, 1, 0, 30001, 0, "P", "P", None], "rc": 1,
+     "message": "gcs_kmeans_assign_accumulate: bad shape or bank"},
+    {"fn": "gcs_kmeans_assign_raster", "args": ["P", "P", 1, 30001, 1002, 2, 13, 8, 1, 0, "P", 0, None, None], "rc": 1,
+     "message": "gcs_kmeans_assign_accumulate: bad shape or bank"},
+    {"fn": "gcs_kmeans_pass_fused", "args": ["P", 1, 30001, 1002, 2, 13, 8, 1, 0, 0, 0, "P", "P", None, 0, None], "rc": 1,
+     "message": "gcs_kmeans_pass_fused: bad shape or bank"}]
+
+
 def test_bad_arguments_keep_their_code_and_message(lib, table):
     """Every rule of lloyd_pass and of gcs_kmeans_pass_fused, through the three entry points: (rc, gcs_last_error()) as recorded. The
     calls return before any launch ("P": a pointer that is never dereferenced)."""
     fake = C.c_void_p(4096)
-    errors = table["errors"]
-    for e in errors:
+    errors = table["errors"]                         # (what the fixture must hold is asked of the fixture alone, below)
+    for e in errors + LIMIT_ERRORS:
         args = [fake if a == "P" else C.c_void_p(None) if a is None else C.c_int(a) for a in e["args"]]
         rc = getattr(lib, e["fn"])(*args)
         assert (rc, lib.gcs_last_error().decode()) == (e["rc"], e["message"]), e
