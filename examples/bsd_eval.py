@@ -57,6 +57,10 @@ whole set): ODS with its threshold and OIS of the map.
 `--texton-edges [--radius R] [--k K] [--smoothing S] [--n-orient N --color-weight W --chroma-gain G]`: the same sweep for the three maps
 of SPEC.md §24 on the plan's k-means map (default R = 8, K = 8, 8 directions): E = floor(sqrt(TG * G))
 (`Segmenter.texton_edges_device`), TG alone (`joined=False`) and G (`edges_device`), one row each.
+`--cue-edges [--bins N] [--weights a,b,c,d] [--radius R] [--k K] [--n-orient N --color-weight W --chroma-gain G]`: the same sweep for
+the maps of SPEC.md §25 (defaults: 16 bins, weights 2,2,1,1 for textons and the three channels, R = 8, K = 8, 8 directions):
+E' = floor(sqrt(PB * G)) (`Segmenter.cue_edges_device`), PB alone (`joined=False`) and, beside them, E of §24; with a first weight of 0 no
+k-means runs. `--cue-edges --n-orient 5 --color-weight 0.125 --chroma-gain 4` prints the default row of `DESIGN.md` §7.
 """
 import os
 import sys
@@ -313,7 +317,45 @@ def texton_edge_rows(n_orient, cw, g, smoothing, k, radius, levels=256):
             name, n_orient, cw, g, smoothing, k, radius, levels, step, best["ODS"], name, best["ODS_regions"], best["OIS"]))
 
 
+def cue_edge_rows(n_orient, cw, g, k, radius, bins, weights, levels=256):
+    """`--cue-edges`: E' and PB (SPEC.md §25) and E (§24) of the 24 val images at `levels` absolute thresholds each."""
+    import numpy as np
+    import torch
+    from gabor_color_image_segmentation_amd import Segmenter
+    from gabor_color_image_segmentation_amd.evaluate import ods_ois
+    from gabor_color_image_segmentation_amd.evaluate_gpu import edge_sweep_resident
+    from gabor_color_image_segmentation_amd.groundtruth import PackedTruth
+    gold = os.path.join(ROOT, "tests", "golden")
+    pack = np.load(os.path.join(gold, "bsd_val_images.npz"))
+    truth = PackedTruth(os.path.join(gold, "bsd500_truth.npz"))
+    ids = [str(i) for i in pack["ids"]]
+    seg = Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, k=k)
+    groups = [[i for i in ids if pack["img_" + i].shape[:2] == shape] for shape in sorted({pack["img_" + i].shape[:2] for i in ids})]
+    batches = [torch.from_numpy(np.stack([pack["img_" + i] for i in group])).cuda() for group in groups]
+    print("| map | n_orient | w | g | k | radius | bins | weights | levels | step | ODS | threshold | OIS |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+    cue = dict(radius=radius, bins=bins, weights=weights)
+    for name, make in (("E'", lambda d: seg.cue_edges_device(d, **cue)), ("PB", lambda d: seg.cue_edges_device(d, joined=False, **cue)),
+                       ("E", lambda d: seg.texton_edges_device(d, radius=radius))):
+        maps = [make(d) for d in batches]
+        step = -(-(max(int(m.max()) for m in maps) + 1) // levels)          # one step for the set: the thresholds are absolute
+        table = []
+        for group, m in zip(groups, maps):
+            table += edge_sweep_resident(m, truth.to_device(group), levels=levels, step=step)[2].tolist()
+        best = ods_ois(table, [step * (tau + 1) - 1 for tau in range(levels)])
+        print("| %s | %d | %g | %d | %d | %d | %s | %s | %d | %d | %.4f | %s > %d | %.4f |" % (
+            name, n_orient, cw, g, k, radius, "-" if name == "E" else bins, "-" if name == "E" else ",".join(str(v) for v in weights),
+            levels, step, best["ODS"], name, best["ODS_regions"], best["OIS"]))
+
+
 if __name__ == '__main__':
+    if "--cue-edges" in sys.argv:
+        def opt(name, conv, default):
+            return conv(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
+        cue_edge_rows(opt("--n-orient", int, 6), opt("--color-weight", float, 0.0), opt("--chroma-gain", int, 0), opt("--k", int, 8),
+                      opt("--radius", int, 8), opt("--bins", int, 16),
+                      tuple(int(v) for v in opt("--weights", str, "2,2,1,1").split(",")))
+        sys.exit(0)
     if "--texton-edges" in sys.argv:
         def opt(name, conv, default):
             return conv(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default

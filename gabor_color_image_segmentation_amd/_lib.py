@@ -104,6 +104,12 @@ SIGNATURES = {
     "gcs_texton_gradient": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes): every symbol include/gcs_cues.h declares. They belong to ABI 18 too, but a library built before
+# that header existed does not export them: ``load`` sets up the ones it finds, and the ops refuse a stage whose symbol is missing.
+EXTENSIONS = {
+    "gcs_cue_gradient": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+}
+
 
 class GcsError(RuntimeError):
     pass
@@ -132,6 +138,10 @@ def load():
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)      # AttributeError here = header/library mismatch
         fn.restype, fn.argtypes = res, args
+    for name, (res, args) in EXTENSIONS.items():
+        fn = getattr(lib, name, None)    # optional: an older library of the same ABI lacks it
+        if fn is not None:
+            fn.restype, fn.argtypes = res, args
     if lib.gcs_abi_version() != ABI_VERSION:
         raise GcsError(f"libgcs ABI {lib.gcs_abi_version()} != expected {ABI_VERSION}")
     _lib = lib

@@ -654,6 +654,32 @@ class HipOps:
                                                 None if dir_out is None else dir_out.data_ptr(), self._stream()),
                    "gcs_texton_gradient")
 
+    @_on_device
+    def cue_gradient(self, labels, imgs, b, h, w, K, bins, weights, r, n, grad, out, dir_out, masks=None):
+        """SPEC.md §25: the boundary map of up to four cues - the (B,H,W) int32 label map ``labels`` (K bins, as in
+        ``texton_gradient``) and the three channels of the (B,H,W,3) uint8 tensor ``imgs`` quantised to ``bins`` bins - their
+        chi-square distances added per direction with the integer ``weights`` (w0, w1, w2, w3) before the maximum is taken, into
+        ``out``: PB, or floor(sqrt(PB * grad)). A cue of weight 0 is not read and its tensor may be None. ``dir_out``, ``masks``:
+        as in ``texton_gradient``. One launch, no workspace (capturable as it is)."""
+        if not hasattr(self.lib, "gcs_cue_gradient"):
+            raise ValueError("the cue gradient needs ops that have it (this libgcs.so does not export gcs_cue_gradient)")
+        i32, wts = self.torch.int32, _check_cues(bins, weights)[1]
+        for name, t in (("labels", labels), ("grad", grad), ("out", out)):
+            self._need(t, i32, (b, h, w), f"{name} must be a contiguous (B,H,W) int32 tensor")
+        self._need(imgs, self.torch.uint8, (b, h, w, 3), "imgs must be a contiguous (B,H,W,3) uint8 tensor")
+        self._need(dir_out, self.torch.uint8, (b, h, w), "dir_out must be a contiguous (B,H,W) uint8 tensor")
+        if out is None:
+            raise ValueError("out must be a contiguous (B,H,W) int32 tensor")
+        if (wts[0] and labels is None) or (any(wts[1:]) and imgs is None):
+            raise ValueError("a cue of non-zero weight needs its tensor (labels for weights[0], imgs for weights[1:])")
+        if masks is None:
+            masks = self.texton_masks(r, n)
+        self._need(masks, i32, (int(n), 2, 2 * int(r) + 1), "masks must be a contiguous (n, 2, 2r+1) int32 tensor")
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(self.lib.gcs_cue_gradient(ptr(labels) if wts[0] else None, ptr(imgs) if any(wts[1:]) else None, b, h, w, int(K),
+                                             8 - (int(bins).bit_length() - 1), *wts, int(r), int(n), masks.data_ptr(), ptr(grad),
+                                             out.data_ptr(), ptr(dir_out), self._stream()), "gcs_cue_gradient")
+
     def region_tree_edges_buffers(self, b, h, w, K, capacity=EDGES_MAX):
         """What SPEC.md §23 needs for one (batch, shape, K): ``(stage, merges (B, K-1, 2) int32, costs (B, K-1) int64, alive (B,)
         int32)``, the shape of ``region_tree_buffers``; ``stage`` is a dict of the plane G (``grad``), the leaf table of SPEC.md §20
@@ -1017,6 +1043,19 @@ def _check_texton(radius, n_directions):
     if not 1 <= n <= 16:
         raise ValueError(f"n_directions must be in 1..16, got {n_directions!r}")
     return r, n
+
+
+def _check_cues(bins, weights):
+    """SPEC.md §25: the number of bins of a quantised channel and the four cue weights (textons, channel 0, 1, 2) as integers."""
+    nb = _as_int(bins)
+    if nb not in (2, 4, 8, 16, 32, 64):
+        raise ValueError(f"bins must be one of 2, 4, 8, 16, 32, 64, got {bins!r}")
+    if isinstance(weights, (str, bytes)) or not hasattr(weights, "__len__") or len(weights) != 4:
+        raise ValueError(f"weights must be four integers (textons, channel 0, 1, 2), got {weights!r}")
+    wts = tuple(_as_int(v) for v in weights)
+    if any(v is None or not 0 <= v <= 16 for v in wts) or not any(wts):
+        raise ValueError(f"weights must be integers in 0..16, not all zero, got {weights!r}")
+    return nb, wts
 
 
 def _check_merge_cost(merge_cost):
@@ -1963,6 +2002,82 @@ class Segmenter:
             self.ops.texton_gradient(labels, b, h, w, self._opt.k, r, n, grad, out, None)
         return out
 
+    def cue_gradient_device(self, labels, imgs, K=None, radius=8, n_directions=8, bins=16, weights=(2, 2, 1, 1), gradient=None,
+                            directions=False):
+        """The boundary map PB of SPEC.md §25 of any (B,H,W) int32 device label map and any (B,H,W,3) uint8 device image: the
+        chi-square distances of the label histograms (weight ``weights[0]``) and of the histograms of the three channels quantised
+        to ``bins`` bins (``weights[1:]``), added per direction before the maximum over ``n_directions`` is taken. ``labels`` /
+        ``imgs`` may be None when their weights are 0. ``K``, ``radius``, ``gradient``, ``directions``: as in
+        ``texton_gradient_device`` (``K`` plays no part when ``weights[0]`` is 0)."""
+        if not hasattr(self.ops, "cue_gradient"):
+            raise ValueError("the cue gradient needs ops that have it")
+        torch = _torch()
+        r, n = _check_texton(radius, n_directions)
+        nb, wts = _check_cues(bins, weights)
+        if wts[0] and (getattr(labels, "ndim", 0) != 3 or labels.dtype != torch.int32):
+            raise ValueError("labels must be a (B,H,W) int32 device tensor")
+        if any(wts[1:]) and (getattr(imgs, "ndim", 0) != 4 or imgs.shape[3] != 3 or imgs.dtype != torch.uint8):
+            raise ValueError("imgs must be a (B,H,W,3) uint8 device tensor")
+        labels = labels.contiguous() if wts[0] else None
+        imgs = imgs.contiguous() if any(wts[1:]) else None
+        b, h, w = (labels.shape if labels is not None else imgs.shape[:3])
+        if labels is not None and imgs is not None and tuple(imgs.shape[:3]) != (b, h, w):
+            raise ValueError("labels and imgs must cover the same (B,H,W) pixels")
+        with self._device():
+            if labels is None:
+                K = 1
+            else:
+                K = int(labels.max()) + 1 if K is None else _as_int(K)
+            if K is None or not 1 <= K <= 64:
+                raise ValueError(f"the cue gradient takes 1 <= K <= 64 labels, got {K}")
+            dev = (labels if labels is not None else imgs).device
+            out = torch.empty((b, h, w), dtype=torch.int32, device=dev)
+            dirs = torch.empty((b, h, w), dtype=torch.uint8, device=dev) if directions else None
+            self.ops.cue_gradient(labels, imgs, b, h, w, K, nb, wts, r, n, None if gradient is None else gradient.contiguous(),
+                                  out, dirs)
+        return (out, dirs) if directions else out
+
+    def cue_edges_device(self, imgs, radius=8, n_directions=8, bins=16, weights=(2, 2, 1, 1), mode="per_image", joined=True):
+        """(B,H,W,3) uint8 device tensor -> (B,H,W) int32 boundary map E' = floor(sqrt(PB * G)) of SPEC.md §25, the whole chain on
+        one feature slab: the features, G = the texture gradient of §22, the plan's Lloyd loop and its int32 label map (``mode`` as
+        in ``segment_device``), then ONE launch that adds, per direction, the chi-square distances of the label histograms and of
+        the three channels of the image the Gabor stage saw (Y, Co, Cg of §11 when the plan has ``chroma_gain``, else R, G, B),
+        quantised to ``bins`` bins, with the integer ``weights`` (textons, channel 0, 1, 2). ``joined=False``: PB alone (G is not
+        computed). With ``weights[0] == 0`` NO Lloyd pass is enqueued, and the plan's clustering options play no part; otherwise
+        the labels are the plain k-means map and ``texton_edges_device``'s refusals hold. Row strips are refused either way (there
+        is no such argument)."""
+        for name in ("cue_gradient", "feature_gradient"):
+            if not hasattr(self.ops, name):
+                raise ValueError("the cue edge map needs ops that have it")
+        r, n = _check_texton(radius, n_directions)
+        nb, wts = _check_cues(bins, weights)
+        textons = wts[0] > 0
+        if textons and (self.n_superpixels > 0 or self._clusters or self._post_passes):
+            raise ValueError("cue_edges_device with weights[0] > 0 needs the plain k-means map (no n_superpixels, tree_nodes or "
+                             "post-pass)")
+        self._check_args(imgs, mode, kind="tensor", cluster=textons)
+        if textons and mode == "global":
+            import torch.distributed as td
+            if td.is_available() and td.is_initialized() and td.get_world_size() > 1:
+                raise ValueError("cue_edges_device runs on one rank only")
+        torch = _torch()
+        imgs = imgs.contiguous()
+        b, h, w, _ = imgs.shape
+        with self._device():
+            ws = self._tail_workspace(b, h, w, mode if textons else "per_image", slab_only=not textons)
+            _step_features(self.ops, self._opt, ws, imgs, b, h, w)
+            grad = labels = None
+            if joined:
+                grad = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
+                self.ops.feature_gradient(ws["feats"], b, h, w, grad)
+            if textons:
+                labels = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
+                _step_cluster(self.ops, self._opt, ws, labels, b, h, w, mode, self.debug)
+            out = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
+            self.ops.cue_gradient(labels, ws["colour"] if self._opt.colour else imgs, b, h, w, self._opt.k, nb, wts, r, n, grad,
+                                  out, None)
+        return out
+
     # ---- host API: the slot
     def segment_batch(self, imgs: np.ndarray, mode="per_image", out_dtype=np.int32) -> np.ndarray:
         """(B,H,W,3) uint8 host array -> fresh (B,H,W) host label array (the calling convention of script.py:25,30).
@@ -2427,6 +2542,24 @@ def segment_texton_edges(img, radius=8, n_directions=8, **kw) -> np.ndarray:
     seg = _plan(kw)
     dev = torch.from_numpy(img[None]).to(seg.ops.device) if seg.native else torch.from_numpy(img[None])
     e = seg.texton_edges_device(dev, radius=radius, n_directions=n_directions)[0].cpu().numpy()
+    top = int(e.max())
+    if top == 0:
+        return np.zeros(e.shape, np.float32)
+    return (e.astype(np.float32) / np.float32(top)).astype(np.float32)
+
+
+def segment_cue_edges(img, radius=8, n_directions=8, bins=16, weights=(2, 2, 1, 1), **kw) -> np.ndarray:
+    """(H,W,3) uint8 -> (H,W) float32 edge strengths in [0, 1]: the map E' of SPEC.md §25 (``Segmenter.cue_edges_device``: the
+    brightness, colour and texton cues joined per direction, then with the texture gradient of §22) divided by its largest value,
+    all zeros for a map that is zero everywhere, as ``segment_edges`` normalises. ``kw``: the plan's options, cached like
+    ``segment``'s."""
+    torch = _torch()
+    img = _one_image(img)
+    r, n = _check_texton(radius, n_directions)
+    nb, wts = _check_cues(bins, weights)
+    seg = _plan(kw)
+    dev = torch.from_numpy(img[None]).to(seg.ops.device) if seg.native else torch.from_numpy(img[None])
+    e = seg.cue_edges_device(dev, radius=r, n_directions=n, bins=nb, weights=wts)[0].cpu().numpy()
     top = int(e.max())
     if top == 0:
         return np.zeros(e.shape, np.float32)
