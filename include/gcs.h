@@ -16,6 +16,17 @@
  * graph. Return 0 on success, GCS_E* otherwise, with a thread-local message in gcs_last_error(). Not thread-safe per
  * buffer.
  *
+ * Streams: a caller may rely on three things, for every entry point that takes a `stream` (tests/test_gpu_stream_contract.py holds
+ * them on each one). Order on `stream` alone: every kernel, memset and copy of a call is enqueued on `stream` - none on the null
+ * stream, none on a stream the call did not tie to `stream` -, so inputs may still be in the making by earlier work on `stream`
+ * when the call is made, and outputs are complete for whatever follows on `stream`; no other stream or event need be waited for.
+ * The Gabor side stream is joined before return: where gcs_gabor_features uses it (eager calls on a two-level bank whose batch holds 2^21
+ * pixels or more: GCS_GABOR_FORK_MIN_PIXELS, csrc/gabor_plan.h), it waits for an event recorded on `stream` before its first launch and `stream` waits for it behind
+ * its last, both enqueued inside the call; under stream capture the same work runs on `stream` alone and writes the same bytes.
+ * No host wait: no call synchronises a stream, an event or the device, so a call returns while earlier work on `stream` is still
+ * running. There is no exception: gcs_download included (its copies are asynchronous for pinned host memory, which it requires).
+ * The entry points marked "(capturable)" can be recorded into a graph on any stream and replayed on other buffer contents.
+ *
  * Buffers: a buffer of exactly the stated size - an array's element count, or what its *_bytes() function returns - is enough: no
  * call writes a byte outside it. Unless a function's comment says otherwise, every output and every workspace / scratch buffer may
  * hold anything on entry (what a call accumulates into is zeroed by the call), every output element is written, workspace and
