@@ -5,7 +5,8 @@
 //   cg_kernel   tg_kernel's method (texton_gradient.hip) with the cues walked outermost: one workgroup per
 //               8 x 32 output pixels, one thread per pixel; one row of one bin's indicator plane is one 64-bit LDS word made by a
 //               wave ballot; a half's count is a sum of popcounts against mask rows broadcast from LDS; bins absent from the
-//               tile's window are skipped; the division is tg_chi_term. What differs: the mirror tables and the transposed mask
+//               tile's window are skipped; the division is tg_chi_term - the steps of texton_tile.h, which both kernels call.
+//               What differs, and is this kernel's own: the mirror tables and the transposed mask
 //               table are built once per tile and serve every cue; a lane loads the three bytes of its halo pixels ONCE, keeps
 //               them packed in registers (a wave owns at most 10 halo rows) and ballots one channel of them per cue; ONE set of
 //               planes in LDS is re-used cue after cue; and the per-direction sums P_i = sum_c w_c chi_{c,i} live in registers
@@ -30,17 +31,13 @@ __global__ __launch_bounds__(TG_THREADS) void cg_kernel(const int32_t *__restric
     __shared__ u64 s_plane[TG_K_MAX * TG_ROWS_MAX];          // [bin][halo row] of the cue at hand: bit c = halo column c holds the bin
     __shared__ int s_my[TG_ROWS_MAX], s_mx[TG_COLS_MAX];     // mirrored image row / column of every halo row / column
     __shared__ u64 s_present[TG_WAVES];                      // bins each wave met
-    // the mask rows as the count loop reads them: [chunk of CH directions][row][direction in chunk][side], zeros past direction n
-    __shared__ __attribute__((aligned(16))) uint32_t s_mask[2 * TG_N_MAX * (2 * TG_R_MAX + 1)];
+    __shared__ __attribute__((aligned(16))) uint32_t s_mask[2 * TG_N_MAX * (2 * TG_R_MAX + 1)];      // tg_fill_masks
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int y0 = (int)blockIdx.y * TG_TH, x0 = (int)blockIdx.x * TG_TW;
     const int R = 2 * r + 1, rows = TG_TH + 2 * r, cols = TG_TW + 2 * r;
     if (tid < rows) s_my[tid] = tg_mirror(y0 - r + tid, H);
     if (tid >= 64 && tid < 64 + cols) s_mx[tid - 64] = tg_mirror(x0 - r + tid - 64, W);
-    for (int idx = tid; idx < NCH * R * 2 * CH; idx += TG_THREADS) {
-        const int e = idx % (2 * CH), m = idx / (2 * CH) % R, i = idx / (2 * CH * R) * CH + (e >> 1);
-        s_mask[idx] = i < n ? masks[(2 * i + (e & 1)) * R + m] : 0u;
-    }
+    tg_fill_masks<CH>(s_mask, masks, NCH, R, n, tid);
     __syncthreads();
 
     // ---- load: wave w owns halo rows w, w + 4, ...; a lane per halo column; the three bytes of a pixel are read once
@@ -57,7 +54,6 @@ __global__ __launch_bounds__(TG_THREADS) void cg_kernel(const int32_t *__restric
     }
 
     const int ty = tid / TG_TW, tx = tid % TG_TW;
-    const unsigned full = (1u << R) - 1u;                    // R <= 31
     unsigned P[CH * NCH];
 #pragma unroll
     for (int i = 0; i < CH * NCH; ++i) P[i] = 0u;
@@ -79,46 +75,17 @@ __global__ __launch_bounds__(TG_THREADS) void cg_kernel(const int32_t *__restric
             } else if (lane < cols) {
                 v = (int)((px[j] >> (8 * (c - 1))) & 255u) >> shift;
             }
-            const bool counted = (unsigned)v < (unsigned)Kc;  // a label outside 0 .. K-1 counts in no bin
-            u64 todo = __ballot(counted);
-            while (todo) {                                   // wave-uniform: one turn per bin of the row
-                const int v0 = __builtin_amdgcn_readlane(v, __ffsll((long long)todo) - 1);
-                const u64 word = __ballot(counted && v == v0);
-                if (lane == 0) s_plane[v0 * rows + row] = word;
-                met |= 1ull << v0;
-                todo &= ~word;
-            }
+            tg_ballot_row(s_plane, v, Kc, rows, row, lane, met);
         }
         if (lane == 0) s_present[wave] = met;
         __syncthreads();
 
         // ---- count: a thread per output pixel, the bins the window holds only
-        u64 present = s_present[0] | s_present[1] | s_present[2] | s_present[3];
-        present = (u64)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)present) |
-                  (u64)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(present >> 32)) << 32;
+        const u64 present = tg_present(s_present, Kc);
 #pragma unroll
         for (int ch = 0; ch < NCH; ++ch) {
             unsigned chi[CH];
-#pragma unroll
-            for (int u = 0; u < CH; ++u) chi[u] = 0u;
-            for (u64 pm = present; pm; pm &= pm - 1ull) {
-                const u64 *pl = s_plane + (__ffsll((long long)pm) - 1) * rows + ty;
-                unsigned g[CH], h[CH];
-#pragma unroll
-                for (int u = 0; u < CH; ++u) g[u] = h[u] = 0u;
-                for (int m = 0; m < R; ++m) {
-                    const unsigned win = (unsigned)(pl[m] >> tx) & full;
-                    const uint4 *mrow = reinterpret_cast<const uint4 *>(s_mask + (ch * R + m) * 2 * CH);      // one address: broadcast
-#pragma unroll
-                    for (int u = 0; u < CH; u += 2) {
-                        const uint4 q = mrow[u >> 1];
-                        g[u] += (unsigned)__popc(win & q.x), h[u] += (unsigned)__popc(win & q.y);
-                        g[u + 1] += (unsigned)__popc(win & q.z), h[u + 1] += (unsigned)__popc(win & q.w);
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < CH; ++u) chi[u] += tg_chi_term(g[u], h[u]);
-            }
+            tg_chunk_chi<CH>(chi, s_plane, s_mask + ch * R * 2 * CH, present, rows, R, ty, tx);
 #pragma unroll
             for (int u = 0; u < CH; ++u) P[ch * CH + u] += wc * chi[u];      // the weight: once per cue and direction
         }
@@ -132,14 +99,7 @@ __global__ __launch_bounds__(TG_THREADS) void cg_kernel(const int32_t *__restric
         if (P[i] > best) best = P[i], best_dir = i;          // the lowest direction that attains the maximum (P_i = 0 past n)
     const int y = y0 + ty, x = x0 + tx;
     if (y >= H || x >= W) return;
-    const size_t at = plane + (size_t)y * (size_t)W + (size_t)x;
-    if (grad) {
-        const int gv = grad[at];                              // PB <= 2^23 and G < 2^20 (§22): the product is below 2^43
-        out[at] = fg_isqrt((u64)best * (u64)(gv > 0 ? gv : 0));
-    } else {
-        out[at] = (int32_t)best;
-    }
-    if (dir_out) dir_out[at] = (uint8_t)best_dir;
+    tg_store(plane + (size_t)y * (size_t)W + (size_t)x, best, best_dir, grad, out, dir_out);
 }
 
 bool cg_overlap(const void *a, size_t na, const void *b, size_t nb) {

@@ -8,15 +8,16 @@
 //               holds is that label's word - no atomics, and the labels the window holds fall out as a bit mask. Count phase: a
 //               pixel at tile column c takes window = (word >> c) & (2^(2r+1) - 1) of every row of its disc; a half's count is the
 //               sum of popcount(window & mask row), the mask rows being wave-uniform: LDS broadcasts of a copy of the table laid out
-//               as the loop walks it (-DGCS_TG_SCALAR_MASKS: scalar loads from the caller's table instead). Directions go CH at a
-//               time so that their counters are registers; labels absent from the tile's window are skipped for the whole
-//               workgroup (-DGCS_TG_NO_SKIP: every label 0 .. K-1 is walked). Both flags are for same-box A/B runs: DESIGN.md §4.22.
+//               as the loop walks it. Directions go CH at a time so that their counters are registers; labels absent from the
+//               tile's window are skipped for the whole workgroup (-DGCS_TG_NO_SKIP, for same-box A/B runs: every label 0 .. K-1
+//               is walked). The steps are texton_tile.h's, shared with cue_gradient.hip; the kernel's own part
+//               is the single label load per halo row and the maximum over the chunks.
 // The kernel knows no trigonometry: gcs_texton_masks (host) makes §24's table, and any table of 2r + 1 rows of 2r + 1 bits is exact.
 // No workspace, no allocation, no host synchronisation: one launch (capturable).
 #include <math.h>
 
 #include "common.h"
-#include "texton_tile.h"      // the tile geometry, tg_mirror and tg_chi_term, shared with cue_gradient.hip
+#include "texton_tile.h"
 
 namespace {
 
@@ -27,22 +28,14 @@ __global__ __launch_bounds__(TG_THREADS) void tg_kernel(const int32_t *__restric
     __shared__ u64 s_plane[TG_K_MAX * TG_ROWS_MAX];          // [label][halo row]: bit c = halo column c holds the label
     __shared__ int s_my[TG_ROWS_MAX], s_mx[TG_COLS_MAX];     // mirrored image row / column of every halo row / column
     __shared__ u64 s_present[TG_WAVES];                      // labels each wave met
-#ifndef GCS_TG_SCALAR_MASKS
-    // the mask rows as the count loop reads them: [chunk of CH directions][row][direction in chunk][side], zeros past direction n
-    __shared__ __attribute__((aligned(16))) uint32_t s_mask[2 * TG_N_MAX * (2 * TG_R_MAX + 1)];
-#endif
+    __shared__ __attribute__((aligned(16))) uint32_t s_mask[2 * TG_N_MAX * (2 * TG_R_MAX + 1)];      // tg_fill_masks
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int y0 = (int)blockIdx.y * TG_TH, x0 = (int)blockIdx.x * TG_TW;
     const int R = 2 * r + 1, rows = TG_TH + 2 * r, cols = TG_TW + 2 * r;
     for (int idx = tid; idx < K * rows; idx += TG_THREADS) s_plane[idx] = 0ull;
     if (tid < rows) s_my[tid] = tg_mirror(y0 - r + tid, H);
     if (tid >= 64 && tid < 64 + cols) s_mx[tid - 64] = tg_mirror(x0 - r + tid - 64, W);
-#ifndef GCS_TG_SCALAR_MASKS
-    for (int idx = tid; idx < (n + CH - 1) / CH * R * 2 * CH; idx += TG_THREADS) {
-        const int e = idx % (2 * CH), m = idx / (2 * CH) % R, i = idx / (2 * CH * R) * CH + (e >> 1);
-        s_mask[idx] = i < n ? masks[(2 * i + (e & 1)) * R + m] : 0u;
-    }
-#endif
+    tg_fill_masks<CH>(s_mask, masks, (n + CH - 1) / CH, R, n, tid);
     __syncthreads();
 
     // ---- load: wave w owns halo rows w, w + 4, ...; a lane per halo column
@@ -51,79 +44,26 @@ __global__ __launch_bounds__(TG_THREADS) void tg_kernel(const int32_t *__restric
     for (int row = wave; row < rows; row += TG_WAVES) {
         int l = -1;
         if (lane < cols) l = img[(size_t)s_my[row] * (size_t)W + (size_t)s_mx[lane]];
-        const bool counted = (unsigned)l < (unsigned)K;      // a value outside 0 .. K-1 counts in no bin
-        u64 todo = __ballot(counted);
-        while (todo) {                                       // wave-uniform: one turn per label of the row
-            const int l0 = __builtin_amdgcn_readlane(l, __ffsll((long long)todo) - 1);
-            const u64 word = __ballot(counted && l == l0);
-            if (lane == 0) s_plane[l0 * rows + row] = word;
-            met |= 1ull << l0;
-            todo &= ~word;
-        }
+        tg_ballot_row(s_plane, l, K, rows, row, lane, met);
     }
     if (lane == 0) s_present[wave] = met;
     __syncthreads();
 
     // ---- count: a thread per output pixel
-#ifdef GCS_TG_NO_SKIP
-    u64 present = K == 64 ? ~0ull : (1ull << K) - 1ull;
-#else
-    u64 present = s_present[0] | s_present[1] | s_present[2] | s_present[3];
-#endif
-    present = (u64)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)present) |
-              (u64)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(present >> 32)) << 32;
+    const u64 present = tg_present(s_present, K);
     const int ty = tid / TG_TW, tx = tid % TG_TW;
-    const unsigned full = (1u << R) - 1u;                    // R <= 31
     unsigned best = 0u;
     int best_dir = 0;
     for (int i0 = 0; i0 < n; i0 += CH) {
         unsigned chi[CH];
-#pragma unroll
-        for (int u = 0; u < CH; ++u) chi[u] = 0u;
-        for (u64 pm = present; pm; pm &= pm - 1ull) {
-            const u64 *pl = s_plane + (__ffsll((long long)pm) - 1) * rows + ty;
-            unsigned g[CH], h[CH];
-#pragma unroll
-            for (int u = 0; u < CH; ++u) g[u] = h[u] = 0u;
-            for (int m = 0; m < R; ++m) {
-                const unsigned win = (unsigned)(pl[m] >> tx) & full;
-#ifndef GCS_TG_SCALAR_MASKS
-                const uint4 *row = reinterpret_cast<const uint4 *>(s_mask + (i0 / CH * R + m) * 2 * CH);      // one address: broadcast
-#pragma unroll
-                for (int u = 0; u < CH; u += 2) {
-                    const uint4 q = row[u >> 1];
-                    g[u] += (unsigned)__popc(win & q.x), h[u] += (unsigned)__popc(win & q.y);
-                    g[u + 1] += (unsigned)__popc(win & q.z), h[u + 1] += (unsigned)__popc(win & q.w);
-                }
-#else
-#pragma unroll
-                for (int u = 0; u < CH; ++u) {
-                    // directions past n: direction n - 1's rows with nothing kept (empty halves, chi 0, never the first maximum);
-                    // unconditional scalar loads, no branch in this loop
-                    const int i = i0 + u < n ? i0 + u : n - 1;
-                    const unsigned keep = i0 + u < n ? ~0u : 0u;
-                    g[u] += (unsigned)__popc(win & masks[(2 * i) * R + m] & keep);
-                    h[u] += (unsigned)__popc(win & masks[(2 * i + 1) * R + m] & keep);
-                }
-#endif
-            }
-#pragma unroll
-            for (int u = 0; u < CH; ++u) chi[u] += tg_chi_term(g[u], h[u]);
-        }
+        tg_chunk_chi<CH>(chi, s_plane, s_mask + i0 / CH * R * 2 * CH, present, rows, R, ty, tx);
 #pragma unroll
         for (int u = 0; u < CH; ++u)
             if (chi[u] > best) best = chi[u], best_dir = i0 + u;     // the lowest direction that attains the maximum
     }
     const int y = y0 + ty, x = x0 + tx;
     if (y >= H || x >= W) return;
-    const size_t at = ((size_t)blockIdx.z * (size_t)H + (size_t)y) * (size_t)W + (size_t)x;
-    if (grad) {
-        const int gv = grad[at];                              // TG < 2^17 and G < 2^31: the product is below 2^48
-        out[at] = fg_isqrt((u64)best * (u64)(gv > 0 ? gv : 0));
-    } else {
-        out[at] = (int32_t)best;
-    }
-    if (dir_out) dir_out[at] = (uint8_t)best_dir;
+    tg_store(((size_t)blockIdx.z * (size_t)H + (size_t)y) * (size_t)W + (size_t)x, best, best_dir, grad, out, dir_out);
 }
 
 }  // namespace

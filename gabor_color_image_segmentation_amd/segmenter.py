@@ -634,21 +634,29 @@ class HipOps:
             self._texton_masks[key] = self.torch.from_numpy(host.view(np.int32)).to(self.device)
         return self._texton_masks[key]
 
+    def _need_half_disc(self, labels, imgs, grad, out, dir_out, masks, b, h, w, r, n, absent):
+        """The one check of ``texton_gradient`` and ``cue_gradient``: every tensor that is given, then ``absent`` (the caller's
+        message about a tensor that is missing, or None), then the mask table, which is returned (``texton_masks(r, n)`` for None)."""
+        i32 = self.torch.int32
+        for name, t in (("labels", labels), ("grad", grad), ("out", out)):
+            self._need(t, i32, (b, h, w), f"{name} must be a contiguous (B,H,W) int32 tensor")
+        self._need(imgs, self.torch.uint8, (b, h, w, 3), "imgs must be a contiguous (B,H,W,3) uint8 tensor")
+        self._need(dir_out, self.torch.uint8, (b, h, w), "dir_out must be a contiguous (B,H,W) uint8 tensor")
+        if absent:
+            raise ValueError(absent)
+        if masks is None:
+            masks = self.texton_masks(r, n)
+        self._need(masks, i32, (int(n), 2, 2 * int(r) + 1), "masks must be a contiguous (n, 2, 2r+1) int32 tensor")
+        return masks
+
     @_on_device
     def texton_gradient(self, labels, b, h, w, K, r, n, grad, out, dir_out, masks=None):
         """SPEC.md §24: the texton gradient of the (B,H,W) int32 label map ``labels`` (values outside 0 .. K-1 count nowhere) at
         radius ``r`` and ``n`` directions into ``out``, a contiguous (B,H,W) int32 tensor: TG, or floor(sqrt(TG * grad)) with
         ``grad`` a (B,H,W) int32 edge map (None: TG). ``dir_out``: (B,H,W) uint8 or None. ``masks``: a (n, 2, 2r+1) int32 device
         tensor in place of ``texton_masks(r, n)`` (any table is exact). One launch, no workspace (capturable as it is)."""
-        i32 = self.torch.int32
-        for name, t in (("labels", labels), ("grad", grad), ("out", out)):
-            self._need(t, i32, (b, h, w), f"{name} must be a contiguous (B,H,W) int32 tensor")
-        self._need(dir_out, self.torch.uint8, (b, h, w), "dir_out must be a contiguous (B,H,W) uint8 tensor")
-        if labels is None or out is None:
-            raise ValueError("labels and out must be contiguous (B,H,W) int32 tensors")
-        if masks is None:
-            masks = self.texton_masks(r, n)
-        self._need(masks, i32, (int(n), 2, 2 * int(r) + 1), "masks must be a contiguous (n, 2, 2r+1) int32 tensor")
+        absent = "labels and out must be contiguous (B,H,W) int32 tensors" if labels is None or out is None else None
+        masks = self._need_half_disc(labels, None, grad, out, dir_out, masks, b, h, w, r, n, absent)
         _lib.check(self.lib.gcs_texton_gradient(labels.data_ptr(), b, h, w, int(K), int(r), int(n), masks.data_ptr(),
                                                 None if grad is None else grad.data_ptr(), out.data_ptr(),
                                                 None if dir_out is None else dir_out.data_ptr(), self._stream()),
@@ -663,18 +671,13 @@ class HipOps:
         as in ``texton_gradient``. One launch, no workspace (capturable as it is)."""
         if not hasattr(self.lib, "gcs_cue_gradient"):
             raise ValueError("the cue gradient needs ops that have it (this libgcs.so does not export gcs_cue_gradient)")
-        i32, wts = self.torch.int32, _check_cues(bins, weights)[1]
-        for name, t in (("labels", labels), ("grad", grad), ("out", out)):
-            self._need(t, i32, (b, h, w), f"{name} must be a contiguous (B,H,W) int32 tensor")
-        self._need(imgs, self.torch.uint8, (b, h, w, 3), "imgs must be a contiguous (B,H,W,3) uint8 tensor")
-        self._need(dir_out, self.torch.uint8, (b, h, w), "dir_out must be a contiguous (B,H,W) uint8 tensor")
+        wts = _check_cues(bins, weights)[1]
+        absent = None
         if out is None:
-            raise ValueError("out must be a contiguous (B,H,W) int32 tensor")
-        if (wts[0] and labels is None) or (any(wts[1:]) and imgs is None):
-            raise ValueError("a cue of non-zero weight needs its tensor (labels for weights[0], imgs for weights[1:])")
-        if masks is None:
-            masks = self.texton_masks(r, n)
-        self._need(masks, i32, (int(n), 2, 2 * int(r) + 1), "masks must be a contiguous (n, 2, 2r+1) int32 tensor")
+            absent = "out must be a contiguous (B,H,W) int32 tensor"
+        elif (wts[0] and labels is None) or (any(wts[1:]) and imgs is None):
+            absent = "a cue of non-zero weight needs its tensor (labels for weights[0], imgs for weights[1:])"
+        masks = self._need_half_disc(labels, imgs, grad, out, dir_out, masks, b, h, w, r, n, absent)
         ptr = lambda t: None if t is None else t.data_ptr()
         _lib.check(self.lib.gcs_cue_gradient(ptr(labels) if wts[0] else None, ptr(imgs) if any(wts[1:]) else None, b, h, w, int(K),
                                              8 - (int(bins).bit_length() - 1), *wts, int(r), int(n), masks.data_ptr(), ptr(grad),
@@ -1959,13 +1962,25 @@ class Segmenter:
         r, n = _check_texton(radius, n_directions)
         labels = labels.contiguous()
         b, h, w = labels.shape
+        return self._half_disc_map("texton", labels, labels, K, gradient, directions,
+                                   lambda K, g, out, dirs: self.ops.texton_gradient(labels, b, h, w, K, r, n, g, out, dirs))
+
+    def _half_disc_map(self, what, labels, like, K, gradient, directions, launch):
+        """What ``texton_gradient_device`` and ``cue_gradient_device`` share: K (one read of ``labels.max()`` when None; 1 without
+        labels) and its limits, ``out`` and ``dirs`` on the (B,H,W) pixels and the device of ``like``, and
+        ``launch(K, gradient, out, dirs)``."""
+        torch = _torch()
+        shape = tuple(like.shape[:3])
         with self._device():
-            K = int(labels.max()) + 1 if K is None else _as_int(K)
-            if not 1 <= K <= 64:
-                raise ValueError(f"the texton gradient takes 1 <= K <= 64 labels, got {K}")
-            out = torch.empty((b, h, w), dtype=torch.int32, device=labels.device)
-            dirs = torch.empty((b, h, w), dtype=torch.uint8, device=labels.device) if directions else None
-            self.ops.texton_gradient(labels, b, h, w, K, r, n, None if gradient is None else gradient.contiguous(), out, dirs)
+            if labels is None:
+                K = 1
+            else:
+                K = int(labels.max()) + 1 if K is None else _as_int(K)
+            if K is None or not 1 <= K <= 64:
+                raise ValueError(f"the {what} gradient takes 1 <= K <= 64 labels, got {K}")
+            out = torch.empty(shape, dtype=torch.int32, device=like.device)
+            dirs = torch.empty(shape, dtype=torch.uint8, device=like.device) if directions else None
+            launch(K, None if gradient is None else gradient.contiguous(), out, dirs)
         return (out, dirs) if directions else out
 
     def texton_edges_device(self, imgs, radius=8, n_directions=8, mode="per_image", joined=True):
@@ -1975,31 +1990,48 @@ class Segmenter:
         ``joined=False``: TG alone (G is not computed). The labels are the plain k-means map: a plan with ``n_superpixels > 0``,
         ``tree_nodes = "clusters"`` or a post-pass (``connectivity``, ``min_region_size``) is refused, and so are row strips, a
         ``dist_group`` (there is no such argument) and a global codebook over more than one rank."""
-        for name in ("texton_gradient", "feature_gradient"):
-            if not hasattr(self.ops, name):
-                raise ValueError("the texton edge map needs ops that have it")
-        if self.n_superpixels > 0 or self._clusters or self._post_passes:
-            raise ValueError("texton_edges_device needs the plain k-means map (no n_superpixels, tree_nodes or post-pass)")
+        self._need_edge_ops("texton")
+        self._need_plain_map("texton_edges_device")
         r, n = _check_texton(radius, n_directions)
-        self._check_args(imgs, mode, kind="tensor")
-        if mode == "global":
+        return self._edges_chain("texton", imgs, mode, joined, cluster=True,
+                                 launch=lambda ws, imgs, labels, grad, out: self.ops.texton_gradient(labels, *out.shape, self._opt.k,
+                                                                                                     r, n, grad, out, None))
+
+    def _need_edge_ops(self, what):
+        for name in (what + "_gradient", "feature_gradient"):
+            if not hasattr(self.ops, name):
+                raise ValueError(f"the {what} edge map needs ops that have it")
+
+    def _need_plain_map(self, who):
+        if self.n_superpixels > 0 or self._clusters or self._post_passes:
+            raise ValueError(f"{who} needs the plain k-means map (no n_superpixels, tree_nodes or post-pass)")
+
+    def _edges_chain(self, what, imgs, mode, joined, cluster, launch):
+        """The chain behind ``texton_edges_device`` and ``cue_edges_device`` on one feature slab, once the caller has checked its
+        ops, its plan and its parameters: the argument checks, the features, G when ``joined``, the plan's Lloyd loop and its int32
+        label map when ``cluster`` (then ``mode="global"`` runs on one rank), and ``launch(ws, imgs, labels or None, G or None,
+        out)``, the ``what`` gradient."""
+        self._check_args(imgs, mode, kind="tensor", cluster=cluster)
+        if cluster and mode == "global":
             import torch.distributed as td
             if td.is_available() and td.is_initialized() and td.get_world_size() > 1:
-                raise ValueError("texton_edges_device runs on one rank only")
+                raise ValueError(f"{what}_edges_device runs on one rank only")
         torch = _torch()
         imgs = imgs.contiguous()
         b, h, w, _ = imgs.shape
+        new = lambda: torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
         with self._device():
-            ws = self._tail_workspace(b, h, w, mode)
+            ws = self._tail_workspace(b, h, w, mode if cluster else "per_image", slab_only=not cluster)
             _step_features(self.ops, self._opt, ws, imgs, b, h, w)
-            grad = None
+            grad = labels = None
             if joined:
-                grad = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
+                grad = new()
                 self.ops.feature_gradient(ws["feats"], b, h, w, grad)
-            labels = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
-            _step_cluster(self.ops, self._opt, ws, labels, b, h, w, mode, self.debug)
-            out = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
-            self.ops.texton_gradient(labels, b, h, w, self._opt.k, r, n, grad, out, None)
+            if cluster:
+                labels = new()
+                _step_cluster(self.ops, self._opt, ws, labels, b, h, w, mode, self.debug)
+            out = new()
+            launch(ws, imgs, labels, grad, out)
         return out
 
     def cue_gradient_device(self, labels, imgs, K=None, radius=8, n_directions=8, bins=16, weights=(2, 2, 1, 1), gradient=None,
@@ -2023,19 +2055,8 @@ class Segmenter:
         b, h, w = (labels.shape if labels is not None else imgs.shape[:3])
         if labels is not None and imgs is not None and tuple(imgs.shape[:3]) != (b, h, w):
             raise ValueError("labels and imgs must cover the same (B,H,W) pixels")
-        with self._device():
-            if labels is None:
-                K = 1
-            else:
-                K = int(labels.max()) + 1 if K is None else _as_int(K)
-            if K is None or not 1 <= K <= 64:
-                raise ValueError(f"the cue gradient takes 1 <= K <= 64 labels, got {K}")
-            dev = (labels if labels is not None else imgs).device
-            out = torch.empty((b, h, w), dtype=torch.int32, device=dev)
-            dirs = torch.empty((b, h, w), dtype=torch.uint8, device=dev) if directions else None
-            self.ops.cue_gradient(labels, imgs, b, h, w, K, nb, wts, r, n, None if gradient is None else gradient.contiguous(),
-                                  out, dirs)
-        return (out, dirs) if directions else out
+        return self._half_disc_map("cue", labels, labels if labels is not None else imgs, K, gradient, directions,
+                                   lambda K, g, out, dirs: self.ops.cue_gradient(labels, imgs, b, h, w, K, nb, wts, r, n, g, out, dirs))
 
     def cue_edges_device(self, imgs, radius=8, n_directions=8, bins=16, weights=(2, 2, 1, 1), mode="per_image", joined=True):
         """(B,H,W,3) uint8 device tensor -> (B,H,W) int32 boundary map E' = floor(sqrt(PB * G)) of SPEC.md §25, the whole chain on
@@ -2046,37 +2067,16 @@ class Segmenter:
         computed). With ``weights[0] == 0`` NO Lloyd pass is enqueued, and the plan's clustering options play no part; otherwise
         the labels are the plain k-means map and ``texton_edges_device``'s refusals hold. Row strips are refused either way (there
         is no such argument)."""
-        for name in ("cue_gradient", "feature_gradient"):
-            if not hasattr(self.ops, name):
-                raise ValueError("the cue edge map needs ops that have it")
+        self._need_edge_ops("cue")
         r, n = _check_texton(radius, n_directions)
         nb, wts = _check_cues(bins, weights)
-        textons = wts[0] > 0
-        if textons and (self.n_superpixels > 0 or self._clusters or self._post_passes):
-            raise ValueError("cue_edges_device with weights[0] > 0 needs the plain k-means map (no n_superpixels, tree_nodes or "
-                             "post-pass)")
-        self._check_args(imgs, mode, kind="tensor", cluster=textons)
-        if textons and mode == "global":
-            import torch.distributed as td
-            if td.is_available() and td.is_initialized() and td.get_world_size() > 1:
-                raise ValueError("cue_edges_device runs on one rank only")
-        torch = _torch()
-        imgs = imgs.contiguous()
-        b, h, w, _ = imgs.shape
-        with self._device():
-            ws = self._tail_workspace(b, h, w, mode if textons else "per_image", slab_only=not textons)
-            _step_features(self.ops, self._opt, ws, imgs, b, h, w)
-            grad = labels = None
-            if joined:
-                grad = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
-                self.ops.feature_gradient(ws["feats"], b, h, w, grad)
-            if textons:
-                labels = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
-                _step_cluster(self.ops, self._opt, ws, labels, b, h, w, mode, self.debug)
-            out = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
-            self.ops.cue_gradient(labels, ws["colour"] if self._opt.colour else imgs, b, h, w, self._opt.k, nb, wts, r, n, grad,
+        if wts[0] > 0:
+            self._need_plain_map("cue_edges_device with weights[0] > 0")
+
+        def launch(ws, imgs, labels, grad, out):
+            self.ops.cue_gradient(labels, ws["colour"] if self._opt.colour else imgs, *out.shape, self._opt.k, nb, wts, r, n, grad,
                                   out, None)
-        return out
+        return self._edges_chain("cue", imgs, mode, joined, cluster=wts[0] > 0, launch=launch)
 
     # ---- host API: the slot
     def segment_batch(self, imgs: np.ndarray, mode="per_image", out_dtype=np.int32) -> np.ndarray:
@@ -2505,15 +2505,11 @@ def segment_contours(img, **kw) -> np.ndarray:
     """(H,W,3) uint8 -> (H,W) float32 boundary strengths in [0, 1]: the contour map of SPEC.md §15 divided by max(1, alive), so
     that thresholding it at (alive - R) / alive gives the boundaries of the cut at R regions. ``kw``: the plan's options
     (``n_superpixels`` is needed); the plan is cached like ``segment``'s."""
-    torch = _torch()
-    img = np.ascontiguousarray(img)
-    if img.ndim != 3 or img.shape[2] != 3 or img.dtype != np.uint8:
-        raise ValueError("img must be an (H,W,3) uint8 array")
+    img = _one_image(img)
     if not kw.get("n_superpixels") and kw.get("tree_nodes") != "clusters":
         raise ValueError('segment_contours needs n_superpixels=n with n > 0, or tree_nodes="clusters"')
     seg = _plan(kw)
-    dev = torch.from_numpy(img[None]).to(seg.ops.device) if seg.native else torch.from_numpy(img[None])
-    contours, alive = seg.contours_device(dev)
+    contours, alive = seg.contours_device(_batch_of_one(seg, img))
     return (contours[0].cpu().numpy().astype(np.float32) / np.float32(max(1, int(alive[0])))).astype(np.float32)
 
 
@@ -2522,30 +2518,18 @@ def segment_edges(img, **kw) -> np.ndarray:
     (``Segmenter.edges_device``) divided by its largest value, all zeros for a map that is zero everywhere. ``kw``: the plan's
     options (the bank, ``smoothing``, colour and position options shape the map; clustering options play no part); the plan is
     cached like ``segment``'s."""
-    torch = _torch()
     img = _one_image(img)
     seg = _plan(kw)
-    dev = torch.from_numpy(img[None]).to(seg.ops.device) if seg.native else torch.from_numpy(img[None])
-    g = seg.edges_device(dev)[0].cpu().numpy()
-    top = int(g.max())
-    if top == 0:
-        return np.zeros(g.shape, np.float32)
-    return (g.astype(np.float32) / np.float32(top)).astype(np.float32)
+    return _over_largest(seg.edges_device(_batch_of_one(seg, img)))
 
 
 def segment_texton_edges(img, radius=8, n_directions=8, **kw) -> np.ndarray:
     """(H,W,3) uint8 -> (H,W) float32 edge strengths in [0, 1]: the map E of SPEC.md §24 (``Segmenter.texton_edges_device``: the
     texton gradient of the plan's k-means map joined with the texture gradient of §22) divided by its largest value, all zeros
     for a map that is zero everywhere, as ``segment_edges`` normalises. ``kw``: the plan's options, cached like ``segment``'s."""
-    torch = _torch()
     img = _one_image(img)
     seg = _plan(kw)
-    dev = torch.from_numpy(img[None]).to(seg.ops.device) if seg.native else torch.from_numpy(img[None])
-    e = seg.texton_edges_device(dev, radius=radius, n_directions=n_directions)[0].cpu().numpy()
-    top = int(e.max())
-    if top == 0:
-        return np.zeros(e.shape, np.float32)
-    return (e.astype(np.float32) / np.float32(top)).astype(np.float32)
+    return _over_largest(seg.texton_edges_device(_batch_of_one(seg, img), radius=radius, n_directions=n_directions))
 
 
 def segment_cue_edges(img, radius=8, n_directions=8, bins=16, weights=(2, 2, 1, 1), **kw) -> np.ndarray:
@@ -2553,17 +2537,11 @@ def segment_cue_edges(img, radius=8, n_directions=8, bins=16, weights=(2, 2, 1, 
     brightness, colour and texton cues joined per direction, then with the texture gradient of §22) divided by its largest value,
     all zeros for a map that is zero everywhere, as ``segment_edges`` normalises. ``kw``: the plan's options, cached like
     ``segment``'s."""
-    torch = _torch()
     img = _one_image(img)
     r, n = _check_texton(radius, n_directions)
     nb, wts = _check_cues(bins, weights)
     seg = _plan(kw)
-    dev = torch.from_numpy(img[None]).to(seg.ops.device) if seg.native else torch.from_numpy(img[None])
-    e = seg.cue_edges_device(dev, radius=r, n_directions=n, bins=nb, weights=wts)[0].cpu().numpy()
-    top = int(e.max())
-    if top == 0:
-        return np.zeros(e.shape, np.float32)
-    return (e.astype(np.float32) / np.float32(top)).astype(np.float32)
+    return _over_largest(seg.cue_edges_device(_batch_of_one(seg, img), radius=r, n_directions=n, bins=nb, weights=wts))
 
 
 def segment_images(images, batch=64, **kw):
@@ -2586,6 +2564,21 @@ def _one_image(img):
     if img.ndim != 3 or img.shape[2] != 3 or img.dtype != np.uint8:
         raise ValueError("img must be an (H,W,3) uint8 array")
     return img
+
+
+def _batch_of_one(seg, img):
+    """The (H,W,3) image as a (1,H,W,3) tensor where the plan's ops run."""
+    dev = _torch().from_numpy(img[None])
+    return dev.to(seg.ops.device) if seg.native else dev
+
+
+def _over_largest(maps):
+    """The first map of a (B,H,W) int32 tensor as float32, divided by its largest value; zeros for a map that is zero everywhere."""
+    g = maps[0].cpu().numpy()
+    top = int(g.max())
+    if top == 0:
+        return np.zeros(g.shape, np.float32)
+    return (g.astype(np.float32) / np.float32(top)).astype(np.float32)
 
 
 def segment_regions(img, adjacency=False, gradient=False, **kw):

@@ -247,6 +247,27 @@ def test_cue_edges_device_on_a_colour_plan_reads_the_transformed_image(built):
     assert np.array_equal(got[0].numpy(), cg.cue_edges(None, i0, grad, 4, 16, (0, 1, 2, 3), 3, 6))
 
 
+@pytest.mark.parametrize("joined", [True, False])
+def test_cue_edges_device_at_the_texton_weight_alone_is_texton_edges_device(standin, joined):
+    """One chain behind both: the same map, and the same recorded calls up to the last one."""
+    import torch
+    from gabor_color_image_segmentation_amd import Segmenter
+    img, ops, _, _ = standin
+    seg = Segmenter(ops=ops, **PLAN)
+    dev = torch.from_numpy(img[None])
+    got, calls = {}, {}
+    for name, run in (("cue", lambda: seg.cue_edges_device(dev, radius=3, n_directions=6, weights=(1, 0, 0, 0), joined=joined)),
+                      ("texton", lambda: seg.texton_edges_device(dev, radius=3, n_directions=6, joined=joined))):
+        del ops.calls[:]
+        got[name] = run()
+        calls[name] = list(ops.calls)
+    assert got["cue"].dtype == got["texton"].dtype == torch.int32 and torch.equal(got["cue"], got["texton"]) and got["cue"].max() > 0
+    assert calls["cue"][:-1] == calls["texton"][:-1] and len(calls["cue"]) == len(calls["texton"]) > 2
+    assert calls["cue"][-1] == ("cue", 1, 4, 16, (1, 0, 0, 0), 3, 6, True, True, joined, False)
+    assert calls["texton"][-1] == ("texton", 1, 4, 3, 6, joined, False)
+    assert ("gradient" in [c[0] for c in calls["cue"]]) == joined
+
+
 def test_every_host_value_error_comes_before_any_stage(standin):
     import torch
     import gabor_color_image_segmentation_amd as pkg

@@ -156,6 +156,50 @@ def test_weights_and_null_cues(torch_cuda, ops, wts):
             assert np.array_equal(out.cpu().numpy(), got) and np.array_equal(d.cpu().numpy(), dirs)
 
 
+@pytest.mark.parametrize("r", [1, 15])
+@pytest.mark.parametrize("n", [3, 8, 16])
+@pytest.mark.parametrize("shape", [(9, 33), (1, 1)], ids=lambda s: "%dx%d" % s)
+def test_texton_weight_alone_is_the_texton_kernel_byte_for_byte(torch_cuda, ops, shape, n, r):
+    """gcs_cue_gradient at (1, 0, 0, 0) against gcs_texton_gradient on the same K = 64 maps: the map, dir, and the map joined with
+    a G that has negative entries, at every dispatch arm of both kernels (n = 3, 8, 16) and both radius limits; 9 x 33 is two
+    tiles each way, every one partial. The texton side is held to tests/texton_gradient_ref.py, so the two cannot be wrong
+    together."""
+    torch, K = torch_cuda, 64
+    lab = _labels(shape, K, 500 + 10 * n + r)
+    ref = [tg.texton_gradient(lab[i], K, r, n) for i in range(3)]
+    want, wdir = np.stack([t for t, _ in ref]), np.stack([d for _, d in ref])
+    # G: positive values with the sign flipped on a checkerboard, and -1, -5, INT32_MIN where TG > 0 in every map; a negative
+    # entry joins as 0 (a kernel that dropped the clamp, or read G differently from the other, shows at those pixels)
+    grad = np.random.default_rng(n * 31 + r).integers(1, 1 << 20, size=lab.shape).astype(np.int32)
+    y, x = np.mgrid[0:shape[0], 0:shape[1]]
+    grad[:, (y + x) % 2 == 1] *= -1
+    grad[:, 0, 0] = -1 if shape == (1, 1) else (1 << 20) - 1
+    if shape == (9, 33):
+        for i in range(3):
+            at = np.argwhere(want[i] > 0)
+            for (py, px), v in zip(at[[0, len(at) // 2, -1]], (-1, -5, np.iinfo(np.int32).min)):
+                grad[i, py, px] = v
+            assert (want[i][grad[i] < 0] > 0).sum() >= 3 and (want[i][grad[i] > 0] > 0).any()
+    assert (grad < 0).any()
+    dev, masks = torch.from_numpy(lab).cuda(), ops.texton_masks(r, n)
+    for g, expect in ((None, want), (grad, np.stack([tg.joined(want[i], np.maximum(grad[i], 0)) for i in range(3)]))):
+        out = torch.full(lab.shape, -7, dtype=torch.int32, device="cuda")
+        d = torch.full(lab.shape, 77, dtype=torch.uint8, device="cuda")
+        dg = None if g is None else torch.from_numpy(g).cuda()
+        rc = ops.lib.gcs_texton_gradient(dev.data_ptr(), 3, shape[0], shape[1], K, r, n, masks.data_ptr(), ptr(dg), out.data_ptr(),
+                                         d.data_ptr(), _st(torch))
+        assert rc == 0, ops.lib.gcs_last_error()
+        tex, tdir = out.cpu().numpy(), d.cpu().numpy()
+        _same(tex, expect, "the texton kernel against the restatement")
+        _same(tdir, wdir, "the texton kernel's dir against the restatement")
+        got, dirs = _run(torch, ops, lab, None, K, 16, (1, 0, 0, 0), r, n, grad=g)
+        assert got.tobytes() == tex.tobytes() and dirs.tobytes() == tdir.tobytes(), ("joined" if g is not None else "alone")
+        if g is not None:
+            assert not got[g < 0].any() and (shape == (1, 1) or got[g > 0].any())
+    if shape == (9, 33):
+        assert want.max(axis=(1, 2)).min() > 0                # (at 1 x 1 every value is 0: both halves agree)
+
+
 def test_crafted_images(torch_cuda, ops):
     """A constant image and map; a step in one channel only, for each of the three (only that cue answers); two cues stepping at
     right angles (at the crossing the maximum of the sums is half the sum of the maxima); two cues whose edges lie 45 degrees

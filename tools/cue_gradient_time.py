@@ -22,9 +22,10 @@ that are compared take turns, call by call:
   cue_edges_2211_ms, cue_edges_0111_ms, texton_edges_ms
                             (d) Segmenter.cue_edges_device at both weight sets and Segmenter.texton_edges_device, end to end
   step_<what>_ms / parent_<what>_ms
-                            (e) Segmenter.segment_device of the default plan, texton_edges_device and gcs_texton_gradient with this
-                                library and with the PARENT commit's library in this process, taking turns (…_equal: the same
-                                output, …_inside_parent_range: the new median lies in the parent's min - max)
+                            (e) Segmenter.segment_device of the default plan, texton_edges_device, gcs_texton_gradient and
+                                gcs_cue_gradient at (2, 2, 1, 1), joined, with this library and with the PARENT commit's library in
+                                this process, taking turns (…_equal: the same output, …_inside_parent_range: the new median lies in
+                                the parent's min - max; a parent that does not export gcs_cue_gradient has no arm in that call)
 """
 import json
 import os
@@ -115,21 +116,26 @@ def main(out_path, parent):
     # (e) "off means unchanged": the existing steps against the parent commit's library
     plans = dict(parent=(_with_library(parent, lambda: Segmenter()), _with_library(parent, lambda: Segmenter(k=K, **COLOUR))),
                  step=(Segmenter(), seg))
-    assert not hasattr(plans["parent"][0].ops.lib, "gcs_cue_gradient")
     held = {name: new() for name in plans}
 
     def texton_launch(pair, name):
         pair[1].ops.texton_gradient(labels, BATCH, H, W, K, RADIUS, N_DIR, grad, held[name], None)
         return held[name]
+
+    def cue_launch(pair, name):
+        pair[1].ops.cue_gradient(labels, i0, BATCH, H, W, K, BINS, SETS["2211"], RADIUS, N_DIR, grad, held[name], None)
+        return held[name]
     runs = dict(default=lambda pair, name: pair[0].segment_device(imgs), texton_edges=lambda pair, name: pair[1].texton_edges_device(imgs),
-                texton_gradient=texton_launch)
+                texton_gradient=texton_launch, cue_gradient=cue_launch)
     for what, fn in runs.items():
         got = {}
-        times = _turns(torch, {name: (lambda nm: lambda: got.__setitem__(nm, fn(plans[nm], nm)))(name) for name in ("parent", "step")})
+        arms = ("parent", "step") if what != "cue_gradient" or hasattr(plans["parent"][1].ops.lib, "gcs_cue_gradient") else ("step",)
+        times = _turns(torch, {name: (lambda nm: lambda: got.__setitem__(nm, fn(plans[nm], nm)))(name) for name in arms})
         for name, ts in times.items():
             res.update(_stats(f"{name}_{what}", ts))
-        res[what + "_equal"] = bool(torch.equal(got["step"], got["parent"]))
-        res[what + "_inside_parent_range"] = bool(res[f"parent_{what}_ms_min"] <= res[f"step_{what}_ms"] <= res[f"parent_{what}_ms_max"])
+        if "parent" in arms:
+            res[what + "_equal"] = bool(torch.equal(got["step"], got["parent"]))
+            res[what + "_inside_parent_range"] = bool(res[f"parent_{what}_ms_min"] <= res[f"step_{what}_ms"] <= res[f"parent_{what}_ms_max"])
     print(json.dumps(res), flush=True)
     if out_path:
         with open(out_path, "w") as fh:

@@ -19,7 +19,8 @@ that are compared take turns, call by call:
   step_default_ms / parent_default_ms, step_edges_ms / parent_edges_ms
                                 (e) Segmenter.segment_device of the default plan and Segmenter.edges_device, this library's calls
                                     taking turns with the PARENT commit's library in this process (…_equal: the same output,
-                                    …_inside_parent_range: the new median lies in the parent's min - max)
+                                    …_inside_parent_range: the new median lies in the parent's min - max); the parent may itself
+                                    export gcs_texton_gradient: only these two existing calls go through it
 """
 import json
 import os
@@ -125,7 +126,6 @@ def main(out_path, parent, variants):
         print(json.dumps({key: v for key, v in res.items() if key.startswith(f"k{k}_")}), flush=True)
     # "off means unchanged": the existing steps against the parent commit's library
     plans = dict(parent=_with_library(parent, lambda: Segmenter()), step=Segmenter())
-    assert not hasattr(plans["parent"].ops.lib, "gcs_texton_gradient")
     runs = dict(default=lambda s: s.segment_device(imgs), edges=lambda s: s.edges_device(imgs))
     for what, fn in runs.items():
         times, outs = dict(parent=[], step=[]), {}
