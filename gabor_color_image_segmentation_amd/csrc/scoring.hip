@@ -544,7 +544,7 @@ static int region_counts_launch(const int32_t *labels, const TT *truth, const in
 static bool region_shape_ok(int B, int T, int max_annotators, int H, int W, int n_segments, int n_truth_labels, bool u8) {
     return B > 0 && B <= 65535 && T > 0 && max_annotators > 0 && H > 0 && W > 0 && (long long)H * W <= 0x7fffffffLL &&
            n_segments > 0 && n_truth_labels > 0 && !(u8 && n_truth_labels > 256) &&
-           (long long)T * n_segments * n_truth_labels <= 0x3fffffffLL;
+           (long long)T * n_segments * n_truth_labels <= 0x40000000LL;      // 2^30 counters, 4 GiB: the last one ends at byte 2^32
 }
 
 extern "C" int gcs_region_counts(const int32_t *labels, const uint16_t *truth, int A, int H, int W, int n_segments,
@@ -880,7 +880,7 @@ extern "C" int gcs_region_agreement(const uint32_t *hist, const int32_t *img_of,
     if (!hist || !scratch || !sums || !terms) return gcs_fail(GCS_EINVAL, "gcs_region_agreement: NULL pointer");
     if (seg_max && !img_of) return gcs_fail(GCS_EINVAL, "gcs_region_agreement: seg_max_dev needs img_of_dev");
     if (T <= 0 || T > 1000000 || n_segments <= 0 || n_truth_labels <= 0 ||
-        (long long)T * n_segments * n_truth_labels > 0x3fffffffLL)
+        (long long)T * n_segments * n_truth_labels > 0x40000000LL)
         return gcs_fail(GCS_EINVAL, "gcs_region_agreement: bad shape");
     hipLaunchKernelGGL(region_agreement_kernel, dim3(T), dim3(AG_THREADS), 0, stream, hist, img_of, seg_max, n_segments,
                        n_truth_labels, static_cast<unsigned *>(scratch), reinterpret_cast<unsigned long long *>(sums), terms);

@@ -97,7 +97,7 @@ def _need_tree_and_cuts(labels, merges, alive, regions, truth):
     regs, order = _need_cuts(regions)
     _need_two_pixels(*labels.shape[1:])
     k = merges.shape[1] + 1
-    if truth.t * k * truth.stride > 0x3fffffff:
+    if truth.t * k * truth.stride > 1 << 30:
         raise ValueError(f"the leaf tables [{truth.t}][{k}][{truth.stride}] exceed 2^30 counters")
     return labels, merges, alive, regs, order
 

@@ -33,7 +33,9 @@
  * scratch contents are undefined afterwards, and inputs are read only. The exceptions are named where they occur: buffers updated in
  * place (the slab under gcs_smooth_features and gcs_position_features, centroids_dev of gcs_kmeans_finalize and
  * gcs_kmeans_reduce_finalize, leaf_hist_dev of the sweeps), the workspace of gcs_kmeans_pass_fused (the caller zeroes it once), and
- * the slots of a feature slab that hold no pixel (no call writes them: they keep their bytes).
+ * the slots of a feature slab that hold no pixel (no call writes them: they keep their bytes). Arrays larger than 2^31 elements or
+ * 2^32 bytes are inside this contract wherever a function's own bounds admit them: tests/test_gpu_large_maps.py runs the label-map,
+ * image, annotator-stack and canonical-tensor entry points on both sides of those lines (its table names what it does not run).
  */
 #ifndef GCS_H
 #define GCS_H
@@ -326,7 +328,8 @@ int gcs_region_counts(const int32_t *labels_dev, const uint16_t *truth_dev, int 
  * annotator map (first[B] = T), max_annotators = the largest per-image count (it sizes the
  * workgroup-private tables; an image that brings more annotators than stated falls back to global atomics, still exact). hist_dev uint32 [T][n_segments][n_truth_labels],
  * area_dev / perim_dev uint32 [B][n_segments]; the three may hold anything on entry and are zeroed by the call. One launch for the
- * whole batch behind the zeroing. */
+ * whole batch behind the zeroing. Every entry point that takes such a table stack (gcs_region_counts*, gcs_score_batch_resident,
+ * gcs_region_agreement) refuses T * n_segments * n_truth_labels > 2^30 with GCS_EINVAL: a stack is at most 4 GiB. */
 int gcs_region_counts_batch(const int32_t *labels_dev, const uint16_t *truth_dev, const int32_t *first_dev, int B, int T,
                             int max_annotators, int H, int W, int n_segments, int n_truth_labels, uint32_t *hist_dev,
                             uint32_t *area_dev, uint32_t *perim_dev, gcs_stream_t stream);

@@ -12,7 +12,7 @@ A buffer whose entry contents the header prescribes gets them (the zeroed worksp
 centroids of the two finalize calls, the slab under the in-place stages); a buffer the header describes as partly kept is compared
 with its bytes from before. No buffer is ever smaller than the header asks: the tests probe the contract, they provoke nothing.
 
-CONTRACT (below) names, for every symbol of ``_lib.SIGNATURES``, the case that holds it here, the file that already holds it behind
+CONTRACT (below) names, for every symbol of ``_lib.SIGNATURES`` and ``_lib.EXTENSIONS``, the case that holds it here, the file that already holds it behind
 bands, or that it is a host-only function; a CPU test keeps the table complete."""
 import inspect
 import os
@@ -79,6 +79,7 @@ ELSEWHERE = {
     "gcs_region_adjacency_cuts": "test_gpu_region_adjacency.py",
     "gcs_region_tree_edges": "test_gpu_region_tree_edges.py",
     "gcs_label_used": "test_gpu_region_tree_edges.py",
+    "gcs_cue_gradient": "test_gpu_cue_gradient.py",
 }
 # functions that take no device pointer
 HOST_ONLY = {
@@ -107,12 +108,15 @@ def _source_with_helpers(fn, seen=None):
 
 
 def test_every_entry_point_has_a_home():
-    """CPU: the three sets partition ``_lib.SIGNATURES``; every case named is a test of this file that mentions the symbol; every
-    other file named exists, mentions the symbol and poisons or guards its buffers. A new entry point fails here until its contract has a home."""
+    """CPU: the three sets partition ``_lib.SIGNATURES`` and ``_lib.EXTENSIONS`` together; every case named is a test of this file that mentions the symbol; every
+    other file named exists, mentions the symbol and poisons or guards its buffers (or holds them in an arena). A new entry point fails here until its contract has a home."""
     from gabor_color_image_segmentation_amd import _lib
     sets = (set(CONTRACT), set(ELSEWHERE), HOST_ONLY)
     assert not (sets[0] & sets[1]) and not (sets[0] & sets[2]) and not (sets[1] & sets[2])
-    missing, extra = set(_lib.SIGNATURES) - set.union(*sets), set.union(*sets) - set(_lib.SIGNATURES)
+    assert not set(_lib.SIGNATURES) & set(_lib.EXTENSIONS)
+    symbols = set(_lib.SIGNATURES) | set(_lib.EXTENSIONS)
+    assert "gcs_cue_gradient" in symbols
+    missing, extra = symbols - set.union(*sets), set.union(*sets) - symbols
     assert not missing and not extra, (sorted(missing), sorted(extra))
     for sym, case in CONTRACT.items():
         assert case.startswith("test_") and callable(globals().get(case)), (sym, case)
@@ -122,7 +126,8 @@ def test_every_entry_point_has_a_home():
         path = os.path.join(HERE, name)
         assert os.path.isfile(path), (sym, name)
         text = open(path).read()
-        assert sym in text and ("0xAB" in text or "guard" in text.lower()), (sym, name)     # (poisoned or guarded buffers)
+        # (poisoned or guarded buffers, or views of tests/arena.py between its canary bands, as in this file)
+        assert sym in text and ("0xAB" in text or "guard" in text.lower() or ("Arena(" in text and ".check()" in text)), (sym, name)
 
 
 # ------------------------------------------------------------------------------------------------------------ plumbing

@@ -113,14 +113,16 @@ def _takers_of(code):
 
 def test_the_table_names_every_entry_point_that_takes_a_stream():
     """CPU: the table's symbols are exactly the functions of include/*.h that take a gcs_stream_t, which are CONTRACT + ELSEWHERE of
-    tests/test_gpu_buffer_contracts.py + gcs_cue_gradient and the symbols of ``_lib`` whose last argument is a pointer; every case
+    tests/test_gpu_buffer_contracts.py (gcs_cue_gradient of ``_lib.EXTENSIONS`` among them) and the symbols of ``_lib.SIGNATURES`` and
+    ``_lib.EXTENSIONS`` whose last argument is a pointer and that are not host only; every case
     named exists in NAMES; the builder of every case makes the call. A new entry point fails here until it has a case."""
     import test_gpu_buffer_contracts as bc
     from gabor_color_image_segmentation_amd import _lib
     takers = _stream_takers()
-    assert takers == set(bc.CONTRACT) | set(bc.ELSEWHERE) | {"gcs_cue_gradient"}
+    assert takers == set(bc.CONTRACT) | set(bc.ELSEWHERE) and "gcs_cue_gradient" in takers
     both = dict(_lib.SIGNATURES, **_lib.EXTENSIONS)
     assert takers <= set(both) and all(both[s][1][-1] is ctypes.c_void_p for s in takers)
+    assert takers == set(both) - bc.HOST_ONLY                                    # every device entry point of either table
     missing, extra = takers - set(TABLE), set(TABLE) - takers
     assert not missing and not extra, (sorted(missing), sorted(extra))
     text = open(os.path.abspath(__file__)).read()
