@@ -61,6 +61,9 @@ of SPEC.md §24 on the plan's k-means map (default R = 8, K = 8, 8 directions): 
 the maps of SPEC.md §25 (defaults: 16 bins, weights 2,2,1,1 for textons and the three channels, R = 8, K = 8, 8 directions):
 E' = floor(sqrt(PB * G)) (`Segmenter.cue_edges_device`), PB alone (`joined=False`) and, beside them, E of §24; with a first weight of 0 no
 k-means runs. `--cue-edges --n-orient 5 --color-weight 0.125 --chroma-gain 4` prints the default row of `DESIGN.md` §7.
+`--thin` beside `--texton-edges` / `--cue-edges`: the maps thinned along their direction map (SPEC.md §26; G of §22 has none and stays).
+`--match [N]` beside them: two more columns, the ODS / OIS of the one-to-one matching score of §26 (`evaluate.match_scores`, on the
+host, minutes for the 24 images) at N of the 256 thresholds (32 when N is left out).
 """
 import os
 import sys
@@ -287,8 +290,25 @@ def edge_rows(n_orient, cw, g, smoothing, levels=256):
                                                                     best["ODS_regions"], best["OIS"]))
 
 
-def texton_edge_rows(n_orient, cw, g, smoothing, k, radius, levels=256):
-    """`--texton-edges`: E, TG and G (SPEC.md §24, §22) of the 24 val images at `levels` absolute thresholds each."""
+def _match_cells(maps, groups, truth, step, levels, match):
+    """`--match [N]`: " ODS | OIS |" of the one-to-one matching score (SPEC.md §26, `evaluate.match_scores`, on the host) at N of
+    the `levels` thresholds of the sweep; nothing when `match` is 0."""
+    if not match:
+        return ""
+    from gabor_color_image_segmentation_amd.evaluate import match_scores, ods_ois
+    taus = [(2 * j + 1) * levels // (2 * match) for j in range(match)]
+    th = [step * (tau + 1) - 1 for tau in taus]
+    table = []
+    for group, m in zip(groups, maps):
+        host = m.cpu().numpy()
+        table += [match_scores(host[j], truth[i], th)["fmeasure"].tolist() for j, i in enumerate(group)]
+    best = ods_ois(table, th)
+    return " %.4f | %.4f |" % (best["ODS"], best["OIS"])
+
+
+def texton_edge_rows(n_orient, cw, g, smoothing, k, radius, levels=256, thin=False, match=0):
+    """`--texton-edges`: E, TG and G (SPEC.md §24, §22) of the 24 val images at `levels` absolute thresholds each. `thin`: E and TG
+    thinned along their direction map (§26; G has none)."""
     import numpy as np
     import torch
     from gabor_color_image_segmentation_amd import Segmenter
@@ -302,10 +322,11 @@ def texton_edge_rows(n_orient, cw, g, smoothing, k, radius, levels=256):
     seg = Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, smoothing=smoothing, k=k)
     groups = [[i for i in ids if pack["img_" + i].shape[:2] == shape] for shape in sorted({pack["img_" + i].shape[:2] for i in ids})]
     batches = [torch.from_numpy(np.stack([pack["img_" + i] for i in group])).cuda() for group in groups]
-    print("| map | n_orient | w | g | K | k | radius | levels | step | ODS | threshold | OIS |")
-    print("|---|---|---|---|---|---|---|---|---|---|---|---|")
-    for name, make in (("E", lambda d: seg.texton_edges_device(d, radius=radius)),
-                       ("TG", lambda d: seg.texton_edges_device(d, radius=radius, joined=False)),
+    print("| map | n_orient | w | g | K | k | radius | levels | step | ODS | threshold | OIS |" + (" match ODS | match OIS |" if match else ""))
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|" + ("---|---|" if match else ""))
+    mark = " thin" if thin else ""
+    for name, make in (("E" + mark, lambda d: seg.texton_edges_device(d, radius=radius, thin=thin)),
+                       ("TG" + mark, lambda d: seg.texton_edges_device(d, radius=radius, joined=False, thin=thin)),
                        ("G", lambda d: seg.edges_device(d))):
         maps = [make(d) for d in batches]
         step = -(-(max(int(m.max()) for m in maps) + 1) // levels)          # one step for the set: the thresholds are absolute
@@ -314,11 +335,13 @@ def texton_edge_rows(n_orient, cw, g, smoothing, k, radius, levels=256):
             table += edge_sweep_resident(m, truth.to_device(group), levels=levels, step=step)[2].tolist()
         best = ods_ois(table, [step * (tau + 1) - 1 for tau in range(levels)])
         print("| %s | %d | %g | %d | %g | %d | %d | %d | %d | %.4f | %s > %d | %.4f |" % (
-            name, n_orient, cw, g, smoothing, k, radius, levels, step, best["ODS"], name, best["ODS_regions"], best["OIS"]))
+            name, n_orient, cw, g, smoothing, k, radius, levels, step, best["ODS"], name, best["ODS_regions"], best["OIS"])
+            + _match_cells(maps, groups, truth, step, levels, match))
 
 
-def cue_edge_rows(n_orient, cw, g, k, radius, bins, weights, levels=256):
-    """`--cue-edges`: E' and PB (SPEC.md §25) and E (§24) of the 24 val images at `levels` absolute thresholds each."""
+def cue_edge_rows(n_orient, cw, g, k, radius, bins, weights, levels=256, thin=False, match=0):
+    """`--cue-edges`: E' and PB (SPEC.md §25) and E (§24) of the 24 val images at `levels` absolute thresholds each. `thin`: every
+    map thinned along its direction map (§26)."""
     import numpy as np
     import torch
     from gabor_color_image_segmentation_amd import Segmenter
@@ -332,11 +355,13 @@ def cue_edge_rows(n_orient, cw, g, k, radius, bins, weights, levels=256):
     seg = Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, k=k)
     groups = [[i for i in ids if pack["img_" + i].shape[:2] == shape] for shape in sorted({pack["img_" + i].shape[:2] for i in ids})]
     batches = [torch.from_numpy(np.stack([pack["img_" + i] for i in group])).cuda() for group in groups]
-    print("| map | n_orient | w | g | k | radius | bins | weights | levels | step | ODS | threshold | OIS |")
-    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|")
-    cue = dict(radius=radius, bins=bins, weights=weights)
-    for name, make in (("E'", lambda d: seg.cue_edges_device(d, **cue)), ("PB", lambda d: seg.cue_edges_device(d, joined=False, **cue)),
-                       ("E", lambda d: seg.texton_edges_device(d, radius=radius))):
+    print("| map | n_orient | w | g | k | radius | bins | weights | levels | step | ODS | threshold | OIS |" + (" match ODS | match OIS |" if match else ""))
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|" + ("---|---|" if match else ""))
+    cue = dict(radius=radius, bins=bins, weights=weights, thin=thin)
+    mark = " thin" if thin else ""
+    for name, cues, make in (("E'" + mark, True, lambda d: seg.cue_edges_device(d, **cue)),
+                             ("PB" + mark, True, lambda d: seg.cue_edges_device(d, joined=False, **cue)),
+                             ("E" + mark, False, lambda d: seg.texton_edges_device(d, radius=radius, thin=thin))):
         maps = [make(d) for d in batches]
         step = -(-(max(int(m.max()) for m in maps) + 1) // levels)          # one step for the set: the thresholds are absolute
         table = []
@@ -344,8 +369,16 @@ def cue_edge_rows(n_orient, cw, g, k, radius, bins, weights, levels=256):
             table += edge_sweep_resident(m, truth.to_device(group), levels=levels, step=step)[2].tolist()
         best = ods_ois(table, [step * (tau + 1) - 1 for tau in range(levels)])
         print("| %s | %d | %g | %d | %d | %d | %s | %s | %d | %d | %.4f | %s > %d | %.4f |" % (
-            name, n_orient, cw, g, k, radius, "-" if name == "E" else bins, "-" if name == "E" else ",".join(str(v) for v in weights),
-            levels, step, best["ODS"], name, best["ODS_regions"], best["OIS"]))
+            name, n_orient, cw, g, k, radius, bins if cues else "-", ",".join(str(v) for v in weights) if cues else "-",
+            levels, step, best["ODS"], name, best["ODS_regions"], best["OIS"]) + _match_cells(maps, groups, truth, step, levels, match))
+
+
+def _match_levels():
+    """`--match [N]`: N thresholds (32 when N is left out), 0 without the option."""
+    if "--match" not in sys.argv:
+        return 0
+    at = sys.argv.index("--match") + 1
+    return int(sys.argv[at]) if at < len(sys.argv) and sys.argv[at].isdigit() else 32
 
 
 if __name__ == '__main__':
@@ -354,13 +387,15 @@ if __name__ == '__main__':
             return conv(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
         cue_edge_rows(opt("--n-orient", int, 6), opt("--color-weight", float, 0.0), opt("--chroma-gain", int, 0), opt("--k", int, 8),
                       opt("--radius", int, 8), opt("--bins", int, 16),
-                      tuple(int(v) for v in opt("--weights", str, "2,2,1,1").split(",")))
+                      tuple(int(v) for v in opt("--weights", str, "2,2,1,1").split(",")), thin="--thin" in sys.argv,
+                      match=_match_levels())
         sys.exit(0)
     if "--texton-edges" in sys.argv:
         def opt(name, conv, default):
             return conv(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
         texton_edge_rows(opt("--n-orient", int, 6), opt("--color-weight", float, 0.0), opt("--chroma-gain", int, 0),
-                         opt("--smoothing", float, 0.0), opt("--k", int, 8), opt("--radius", int, 8))
+                         opt("--smoothing", float, 0.0), opt("--k", int, 8), opt("--radius", int, 8), thin="--thin" in sys.argv,
+                         match=_match_levels())
         sys.exit(0)
     if "--edges" in sys.argv:
         def opt(name, conv, default):

@@ -110,6 +110,12 @@ EXTENSIONS = {
     "gcs_cue_gradient": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes): every symbol include/gcs_thin.h declares (SPEC.md §26), optional in the same way.
+THIN_EXTENSIONS = {
+    "gcs_thin_steps": (_i, [_i, _vp]),
+    "gcs_edge_thin": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+}
+
 
 class GcsError(RuntimeError):
     pass
@@ -138,7 +144,7 @@ def load():
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)      # AttributeError here = header/library mismatch
         fn.restype, fn.argtypes = res, args
-    for name, (res, args) in EXTENSIONS.items():
+    for name, (res, args) in list(EXTENSIONS.items()) + list(THIN_EXTENSIONS.items()):
         fn = getattr(lib, name, None)    # optional: an older library of the same ABI lacks it
         if fn is not None:
             fn.restype, fn.argtypes = res, args

@@ -197,6 +197,95 @@ def edge_scores(edges, segments_truth, thresholds) -> dict:
     return out
 
 
+# ---- one-to-one matching scores of an edge-strength map (SPEC.md §26): the metric that charges a thick map for its width
+
+def thin_boundaries(s) -> np.ndarray:
+    """One-pixel contours of a label map: pixel (y, x) is a boundary pixel iff its right or its lower neighbour (where the image
+    has one) carries another label - the pair ownership of ``gcs_region_adjacency`` (SPEC.md §20). (H,W) bool."""
+    s = np.asarray(s)
+    if s.ndim != 2:
+        raise ValueError("a label map must be an (H,W) array")
+    out = np.zeros(s.shape, bool)
+    out[:, :-1] |= s[:, :-1] != s[:, 1:]
+    out[:-1, :] |= s[:-1, :] != s[1:, :]
+    return out
+
+
+def match_distance2(height, width) -> int:
+    """SPEC.md §26: the largest squared distance of an allowed pair, (0.0075 x the diagonal)^2 in integers; 18 for 481 x 321."""
+    return (9 * (int(height) ** 2 + int(width) ** 2)) // 160000
+
+
+def match_count(p_mask, q_mask, d2) -> int:
+    """The cardinality of a maximum matching between the pixels of two (H,W) bool masks, a pair being allowed iff its squared
+    distance is at most ``d2``. The pairs are built offset by offset; the matching is scipy's Hopcroft-Karp."""
+    from scipy.sparse import csr_matrix
+    from scipy.sparse.csgraph import maximum_bipartite_matching
+    p_mask, q_mask = np.asarray(p_mask, bool), np.asarray(q_mask, bool)
+    h, w = p_mask.shape
+    n_p, n_q = int(p_mask.sum()), int(q_mask.sum())
+    if n_p == 0 or n_q == 0:
+        return 0
+    p_id = np.full((h, w), -1, np.int64)
+    q_id = np.full((h, w), -1, np.int64)
+    p_id[p_mask] = np.arange(n_p)
+    q_id[q_mask] = np.arange(n_q)
+    reach = int(np.sqrt(d2))
+    while (reach + 1) ** 2 <= d2:
+        reach += 1
+    while reach ** 2 > d2:
+        reach -= 1
+    rows, cols = [], []
+    for dy in range(-reach, reach + 1):
+        for dx in range(-reach, reach + 1):
+            if dy * dy + dx * dx > d2 or abs(dy) >= h or abs(dx) >= w:
+                continue
+            # q = p + (dy, dx): the two windows of the image that the offset maps onto each other
+            ps = p_id[max(0, -dy):h - max(0, dy), max(0, -dx):w - max(0, dx)]
+            qs = q_id[max(0, dy):h - max(0, -dy), max(0, dx):w - max(0, -dx)]
+            both = (ps >= 0) & (qs >= 0)
+            rows.append(ps[both])
+            cols.append(qs[both])
+    rows, cols = np.concatenate(rows), np.concatenate(cols)
+    if rows.size == 0:
+        return 0
+    graph = csr_matrix((np.ones(rows.size, np.int8), (rows, cols)), shape=(n_p, n_q))
+    return int(np.sum(maximum_bipartite_matching(graph, perm_type="column") >= 0))
+
+
+def match_scores(edges, segments_truth, thresholds, max_dist2=None) -> dict:
+    """One-to-one matching recall / precision / F of an (H,W) integer edge-strength map at every threshold (SPEC.md §26). For a
+    threshold theta, P = {edges > theta}; per annotator t, Q_t = ``thin_boundaries(s_t)`` and M_t = the cardinality of a maximum
+    matching between P and Q_t with a pair allowed iff dy^2 + dx^2 <= D2 = ``match_distance2(H, W)`` (``max_dist2`` overrides
+    it). recall = mean_t M_t / |Q_t| (ZeroDivisionError for an annotator without a boundary), precision = mean_t M_t / |P|, F and
+    the zero rule (|P| = 0) as in ``edge_scores``, whose dict shape is returned. A map pixel is used at most once per annotator,
+    so a ribbon k pixels wide has precision 1 / k where ``edge_scores`` gives it 1."""
+    edges = np.asarray(edges)
+    if edges.ndim != 2 or edges.dtype.kind not in "iu":
+        raise ValueError("edges must be an (H,W) integer array")
+    if len(segments_truth) == 0:
+        raise ZeroDivisionError("no annotator maps")
+    d2 = match_distance2(*edges.shape) if max_dist2 is None else int(max_dist2)
+    if d2 < 0:
+        raise ValueError("max_dist2 must be >= 0")
+    truths = [thin_boundaries(s) for s in segments_truth]
+    for t in truths:
+        if t.shape != edges.shape:
+            raise ValueError("every annotator map must have the shape of edges")
+    th = np.asarray(thresholds).astype(np.int64).ravel()
+    out = {"recall": np.zeros(len(th)), "precision": np.zeros(len(th)), "fmeasure": np.zeros(len(th))}
+    for j, theta in enumerate(th):
+        p_mask = edges > theta
+        ann = []
+        for t in truths:
+            m = float(match_count(p_mask, t, d2)) if p_mask.any() else 0.0
+            ann += [m, float(t.sum()), m]
+        sc = edge_scores_from_counts(float(p_mask.sum()), ann)
+        for key in out:
+            out[key][j] = sc[key]
+    return out
+
+
 # ---- region agreement: PRI, VoI, segmentation covering (SPEC.md §8; not part of the reference's ``metrics``)
 
 def agreement_sums(labels, truth):

@@ -218,6 +218,7 @@ class HipOps:
         self.bias = torch.from_numpy(bias).to(self.device)
         self._gabor_ws = None
         self._texton_masks = {}                  # SPEC.md §24: the half-disc tables on the device, per (r, n)
+        self._thin_steps = {}                    # SPEC.md §26: the step tables on the device, per n
         self.chroma_gain = _check_chroma_gain(chroma_gain)        # SPEC.md §11 (0: colour_opponent is never called)
         # SPEC.md §10: the smoothing taps of every scale on the device (K = 0: none, and smooth_features is never called)
         self.smoothing = _check_smoothing(smoothing, bank)
@@ -682,6 +683,39 @@ class HipOps:
         _lib.check(self.lib.gcs_cue_gradient(ptr(labels) if wts[0] else None, ptr(imgs) if any(wts[1:]) else None, b, h, w, int(K),
                                              8 - (int(bins).bit_length() - 1), *wts, int(r), int(n), masks.data_ptr(), ptr(grad),
                                              out.data_ptr(), ptr(dir_out), self._stream()), "gcs_cue_gradient")
+
+    def thin_steps(self, n):
+        """SPEC.md §26: the step table of ``n`` directions, a (n, 8) int32 device tensor holding the rows of gcs_thin_steps; made
+        on the host once per ``n`` and kept (a captured step must find it made)."""
+        if not hasattr(self.lib, "gcs_thin_steps"):
+            raise ValueError("thin edges need ops that have them (this libgcs.so does not export gcs_thin_steps)")
+        key = int(n)
+        if key not in self._thin_steps:
+            if not 1 <= key <= 16:
+                raise ValueError("thin edges take 1..16 directions")
+            host = np.zeros((key, 8), np.int32)
+            _lib.check(self.lib.gcs_thin_steps(key, host.ctypes.data), "gcs_thin_steps")
+            self._thin_steps[key] = self.torch.from_numpy(host).to(self.device)
+        return self._thin_steps[key]
+
+    @_on_device
+    def edge_thin(self, edges, dirs, b, h, w, n, out, steps=None):
+        """SPEC.md §26: the (B,H,W) int32 map ``edges`` thinned along its (B,H,W) uint8 direction map ``dirs`` of ``n`` directions
+        into ``out``, a contiguous (B,H,W) int32 tensor: a pixel keeps max(E, 0) when it is the maximum along its direction's
+        normal (strict on the minus side, weak on the plus side) and is 0 otherwise. ``steps``: a (n, 8) int32 device tensor in
+        place of ``thin_steps(n)`` (any table is exact). One launch, no workspace (capturable as it is)."""
+        if not hasattr(self.lib, "gcs_edge_thin"):
+            raise ValueError("thin edges need ops that have them (this libgcs.so does not export gcs_edge_thin)")
+        if edges is None or dirs is None or out is None:
+            raise ValueError("edges and out must be contiguous (B,H,W) int32 tensors and dirs a contiguous (B,H,W) uint8 tensor")
+        for name, t in (("edges", edges), ("out", out)):
+            self._need(t, self.torch.int32, (b, h, w), f"{name} must be a contiguous (B,H,W) int32 tensor")
+        self._need(dirs, self.torch.uint8, (b, h, w), "dirs must be a contiguous (B,H,W) uint8 tensor")
+        if steps is None:
+            steps = self.thin_steps(n)
+        self._need(steps, self.torch.int32, (int(n), 8), "steps must be a contiguous (n, 8) int32 tensor")
+        _lib.check(self.lib.gcs_edge_thin(edges.data_ptr(), dirs.data_ptr(), b, h, w, int(n), steps.data_ptr(), out.data_ptr(),
+                                          self._stream()), "gcs_edge_thin")
 
     def region_tree_edges_buffers(self, b, h, w, K, capacity=EDGES_MAX):
         """What SPEC.md §23 needs for one (batch, shape, K): ``(stage, merges (B, K-1, 2) int32, costs (B, K-1) int64, alive (B,)
@@ -1947,15 +1981,17 @@ class Segmenter:
             self.ops.feature_gradient(ws["feats"], b, h, w, out)
         return out
 
-    def texton_gradient_device(self, labels, K=None, radius=8, n_directions=8, gradient=None, directions=False):
+    def texton_gradient_device(self, labels, K=None, radius=8, n_directions=8, gradient=None, directions=False, thin=False):
         """(B,H,W) int32 device label map -> (B,H,W) int32 texton gradient of SPEC.md §24: the largest chi-square distance, over
         ``n_directions`` directions, between the label histograms of the two halves of a disc of ``radius`` pixels (mirrored at
         the border). ``K``: the number of labels (None: one read of ``labels.max()`` from the device; at most 64; values outside
         0 .. K-1 count in no bin). ``gradient``: a (B,H,W) int32 edge map G >= 0 (``edges_device``): the result is then
         floor(sqrt(TG * G)). ``directions=True``: returns ``(map, dir)``, dir (B,H,W) uint8 = the lowest direction of the
-        maximum, 0 where TG = 0."""
+        maximum, 0 where TG = 0. ``thin=True``: the map is thinned along ``dir`` (SPEC.md §26, ``thin_edges_device``) by one more
+        launch on the same stream, and the thinned map is what is returned."""
         if not hasattr(self.ops, "texton_gradient"):
             raise ValueError("the texton gradient needs ops that have it")
+        self._need_thin_ops(thin)
         torch = _torch()
         if getattr(labels, "ndim", 0) != 3 or labels.dtype != torch.int32:
             raise ValueError("labels must be a (B,H,W) int32 device tensor")
@@ -1963,12 +1999,18 @@ class Segmenter:
         labels = labels.contiguous()
         b, h, w = labels.shape
         return self._half_disc_map("texton", labels, labels, K, gradient, directions,
-                                   lambda K, g, out, dirs: self.ops.texton_gradient(labels, b, h, w, K, r, n, g, out, dirs))
+                                   lambda K, g, out, dirs: self.ops.texton_gradient(labels, b, h, w, K, r, n, g, out, dirs),
+                                   thin=n if thin else 0)
 
-    def _half_disc_map(self, what, labels, like, K, gradient, directions, launch):
+    def _need_thin_ops(self, thin):
+        if thin and not hasattr(self.ops, "edge_thin"):
+            raise ValueError("thin edges need ops that have them")
+
+    def _half_disc_map(self, what, labels, like, K, gradient, directions, launch, thin=0):
         """What ``texton_gradient_device`` and ``cue_gradient_device`` share: K (one read of ``labels.max()`` when None; 1 without
         labels) and its limits, ``out`` and ``dirs`` on the (B,H,W) pixels and the device of ``like``, and
-        ``launch(K, gradient, out, dirs)``."""
+        ``launch(K, gradient, out, dirs)``. ``thin`` = n > 0: ``dirs`` is made either way and the map is thinned behind the launch
+        (SPEC.md §26)."""
         torch = _torch()
         shape = tuple(like.shape[:3])
         with self._device():
@@ -1979,23 +2021,29 @@ class Segmenter:
             if K is None or not 1 <= K <= 64:
                 raise ValueError(f"the {what} gradient takes 1 <= K <= 64 labels, got {K}")
             out = torch.empty(shape, dtype=torch.int32, device=like.device)
-            dirs = torch.empty(shape, dtype=torch.uint8, device=like.device) if directions else None
+            dirs = torch.empty(shape, dtype=torch.uint8, device=like.device) if directions or thin else None
             launch(K, None if gradient is None else gradient.contiguous(), out, dirs)
+            if thin:
+                thick, out = out, torch.empty_like(out)
+                self.ops.edge_thin(thick, dirs, *shape, thin, out)
         return (out, dirs) if directions else out
 
-    def texton_edges_device(self, imgs, radius=8, n_directions=8, mode="per_image", joined=True):
+    def texton_edges_device(self, imgs, radius=8, n_directions=8, mode="per_image", joined=True, thin=False):
         """(B,H,W,3) uint8 device tensor -> (B,H,W) int32 edge map E = floor(sqrt(TG * G)) of SPEC.md §24, the whole chain on one
         feature slab: the features, G = the texture gradient of §22 (``edges_device``), the plan's Lloyd loop (``mode`` as in
         ``segment_device``), its int32 label map, and the texton gradient TG of that map at ``radius`` and ``n_directions``.
         ``joined=False``: TG alone (G is not computed). The labels are the plain k-means map: a plan with ``n_superpixels > 0``,
         ``tree_nodes = "clusters"`` or a post-pass (``connectivity``, ``min_region_size``) is refused, and so are row strips, a
-        ``dist_group`` (there is no such argument) and a global codebook over more than one rank."""
+        ``dist_group`` (there is no such argument) and a global codebook over more than one rank. ``thin=True``: the kernel also
+        writes its direction map and the thin launch of SPEC.md §26 runs behind it on the same stream; the thinned map is returned.
+        ``thin=False`` enqueues exactly the launches it always did."""
         self._need_edge_ops("texton")
+        self._need_thin_ops(thin)
         self._need_plain_map("texton_edges_device")
         r, n = _check_texton(radius, n_directions)
-        return self._edges_chain("texton", imgs, mode, joined, cluster=True,
-                                 launch=lambda ws, imgs, labels, grad, out: self.ops.texton_gradient(labels, *out.shape, self._opt.k,
-                                                                                                     r, n, grad, out, None))
+        return self._edges_chain("texton", imgs, mode, joined, cluster=True, thin=n if thin else 0,
+                                 launch=lambda ws, imgs, labels, grad, out, dirs: self.ops.texton_gradient(
+                                     labels, *out.shape, self._opt.k, r, n, grad, out, dirs))
 
     def _need_edge_ops(self, what):
         for name in (what + "_gradient", "feature_gradient"):
@@ -2006,11 +2054,12 @@ class Segmenter:
         if self.n_superpixels > 0 or self._clusters or self._post_passes:
             raise ValueError(f"{who} needs the plain k-means map (no n_superpixels, tree_nodes or post-pass)")
 
-    def _edges_chain(self, what, imgs, mode, joined, cluster, launch):
+    def _edges_chain(self, what, imgs, mode, joined, cluster, launch, thin=0):
         """The chain behind ``texton_edges_device`` and ``cue_edges_device`` on one feature slab, once the caller has checked its
         ops, its plan and its parameters: the argument checks, the features, G when ``joined``, the plan's Lloyd loop and its int32
         label map when ``cluster`` (then ``mode="global"`` runs on one rank), and ``launch(ws, imgs, labels or None, G or None,
-        out)``, the ``what`` gradient."""
+        out, dirs or None)``, the ``what`` gradient. ``thin`` = n > 0: the gradient writes ``dirs`` too and the map is thinned behind
+        it (SPEC.md §26); 0: ``dirs`` is None and nothing is added."""
         self._check_args(imgs, mode, kind="tensor", cluster=cluster)
         if cluster and mode == "global":
             import torch.distributed as td
@@ -2031,18 +2080,23 @@ class Segmenter:
                 labels = new()
                 _step_cluster(self.ops, self._opt, ws, labels, b, h, w, mode, self.debug)
             out = new()
-            launch(ws, imgs, labels, grad, out)
+            dirs = torch.empty((b, h, w), dtype=torch.uint8, device=imgs.device) if thin else None
+            launch(ws, imgs, labels, grad, out, dirs)
+            if thin:
+                thick, out = out, new()
+                self.ops.edge_thin(thick, dirs, b, h, w, thin, out)
         return out
 
     def cue_gradient_device(self, labels, imgs, K=None, radius=8, n_directions=8, bins=16, weights=(2, 2, 1, 1), gradient=None,
-                            directions=False):
+                            directions=False, thin=False):
         """The boundary map PB of SPEC.md §25 of any (B,H,W) int32 device label map and any (B,H,W,3) uint8 device image: the
         chi-square distances of the label histograms (weight ``weights[0]``) and of the histograms of the three channels quantised
         to ``bins`` bins (``weights[1:]``), added per direction before the maximum over ``n_directions`` is taken. ``labels`` /
         ``imgs`` may be None when their weights are 0. ``K``, ``radius``, ``gradient``, ``directions``: as in
-        ``texton_gradient_device`` (``K`` plays no part when ``weights[0]`` is 0)."""
+        ``texton_gradient_device`` (``K`` plays no part when ``weights[0]`` is 0). ``thin``: as in ``texton_gradient_device``."""
         if not hasattr(self.ops, "cue_gradient"):
             raise ValueError("the cue gradient needs ops that have it")
+        self._need_thin_ops(thin)
         torch = _torch()
         r, n = _check_texton(radius, n_directions)
         nb, wts = _check_cues(bins, weights)
@@ -2056,9 +2110,11 @@ class Segmenter:
         if labels is not None and imgs is not None and tuple(imgs.shape[:3]) != (b, h, w):
             raise ValueError("labels and imgs must cover the same (B,H,W) pixels")
         return self._half_disc_map("cue", labels, labels if labels is not None else imgs, K, gradient, directions,
-                                   lambda K, g, out, dirs: self.ops.cue_gradient(labels, imgs, b, h, w, K, nb, wts, r, n, g, out, dirs))
+                                   lambda K, g, out, dirs: self.ops.cue_gradient(labels, imgs, b, h, w, K, nb, wts, r, n, g, out, dirs),
+                                   thin=n if thin else 0)
 
-    def cue_edges_device(self, imgs, radius=8, n_directions=8, bins=16, weights=(2, 2, 1, 1), mode="per_image", joined=True):
+    def cue_edges_device(self, imgs, radius=8, n_directions=8, bins=16, weights=(2, 2, 1, 1), mode="per_image", joined=True,
+                         thin=False):
         """(B,H,W,3) uint8 device tensor -> (B,H,W) int32 boundary map E' = floor(sqrt(PB * G)) of SPEC.md §25, the whole chain on
         one feature slab: the features, G = the texture gradient of §22, the plan's Lloyd loop and its int32 label map (``mode`` as
         in ``segment_device``), then ONE launch that adds, per direction, the chi-square distances of the label histograms and of
@@ -2066,17 +2122,39 @@ class Segmenter:
         quantised to ``bins`` bins, with the integer ``weights`` (textons, channel 0, 1, 2). ``joined=False``: PB alone (G is not
         computed). With ``weights[0] == 0`` NO Lloyd pass is enqueued, and the plan's clustering options play no part; otherwise
         the labels are the plain k-means map and ``texton_edges_device``'s refusals hold. Row strips are refused either way (there
-        is no such argument)."""
+        is no such argument). ``thin``: as in ``texton_edges_device``."""
         self._need_edge_ops("cue")
+        self._need_thin_ops(thin)
         r, n = _check_texton(radius, n_directions)
         nb, wts = _check_cues(bins, weights)
         if wts[0] > 0:
             self._need_plain_map("cue_edges_device with weights[0] > 0")
 
-        def launch(ws, imgs, labels, grad, out):
+        def launch(ws, imgs, labels, grad, out, dirs):
             self.ops.cue_gradient(labels, ws["colour"] if self._opt.colour else imgs, *out.shape, self._opt.k, nb, wts, r, n, grad,
-                                  out, None)
-        return self._edges_chain("cue", imgs, mode, joined, cluster=wts[0] > 0, launch=launch)
+                                  out, dirs)
+        return self._edges_chain("cue", imgs, mode, joined, cluster=wts[0] > 0, launch=launch, thin=n if thin else 0)
+
+    def thin_edges_device(self, edges, dirs, n_directions=8):
+        """(B,H,W) int32 device edge map and its (B,H,W) uint8 direction map -> (B,H,W) int32 thin map T of SPEC.md §26: a pixel
+        keeps max(E, 0) when no larger value lies along the normal of its direction (of ``n_directions``, SPEC.md §24's) among its
+        eight neighbours, linearly interpolated, and is 0 otherwise; strict on one side and weak on the other, so one pixel of a
+        two-pixel plateau survives. A direction >= ``n_directions`` gives 0. One launch; the maps are those of
+        ``texton_gradient_device`` / ``cue_gradient_device`` with ``directions=True``, or any others."""
+        self._need_thin_ops(True)
+        torch = _torch()
+        if getattr(edges, "ndim", 0) != 3 or edges.dtype != torch.int32:
+            raise ValueError("edges must be a (B,H,W) int32 device tensor")
+        if getattr(dirs, "ndim", 0) != 3 or dirs.dtype != torch.uint8 or tuple(dirs.shape) != tuple(edges.shape):
+            raise ValueError("dirs must be a (B,H,W) uint8 device tensor covering the same pixels as edges")
+        n = _as_int(n_directions)
+        if n is None or not 1 <= n <= 16:
+            raise ValueError(f"n_directions must be in 1..16, got {n_directions!r}")
+        edges, dirs = edges.contiguous(), dirs.contiguous()
+        with self._device():
+            out = torch.empty_like(edges)
+            self.ops.edge_thin(edges, dirs, *edges.shape, n, out)
+        return out
 
     # ---- host API: the slot
     def segment_batch(self, imgs: np.ndarray, mode="per_image", out_dtype=np.int32) -> np.ndarray:
@@ -2523,25 +2601,27 @@ def segment_edges(img, **kw) -> np.ndarray:
     return _over_largest(seg.edges_device(_batch_of_one(seg, img)))
 
 
-def segment_texton_edges(img, radius=8, n_directions=8, **kw) -> np.ndarray:
+def segment_texton_edges(img, radius=8, n_directions=8, thin=False, **kw) -> np.ndarray:
     """(H,W,3) uint8 -> (H,W) float32 edge strengths in [0, 1]: the map E of SPEC.md §24 (``Segmenter.texton_edges_device``: the
     texton gradient of the plan's k-means map joined with the texture gradient of §22) divided by its largest value, all zeros
-    for a map that is zero everywhere, as ``segment_edges`` normalises. ``kw``: the plan's options, cached like ``segment``'s."""
+    for a map that is zero everywhere, as ``segment_edges`` normalises. ``thin=True``: the thin map T of SPEC.md §26, normalised
+    the same way. ``kw``: the plan's options, cached like ``segment``'s."""
     img = _one_image(img)
     seg = _plan(kw)
-    return _over_largest(seg.texton_edges_device(_batch_of_one(seg, img), radius=radius, n_directions=n_directions))
+    return _over_largest(seg.texton_edges_device(_batch_of_one(seg, img), radius=radius, n_directions=n_directions, thin=bool(thin)))
 
 
-def segment_cue_edges(img, radius=8, n_directions=8, bins=16, weights=(2, 2, 1, 1), **kw) -> np.ndarray:
+def segment_cue_edges(img, radius=8, n_directions=8, bins=16, weights=(2, 2, 1, 1), thin=False, **kw) -> np.ndarray:
     """(H,W,3) uint8 -> (H,W) float32 edge strengths in [0, 1]: the map E' of SPEC.md §25 (``Segmenter.cue_edges_device``: the
     brightness, colour and texton cues joined per direction, then with the texture gradient of §22) divided by its largest value,
-    all zeros for a map that is zero everywhere, as ``segment_edges`` normalises. ``kw``: the plan's options, cached like
-    ``segment``'s."""
+    all zeros for a map that is zero everywhere, as ``segment_edges`` normalises. ``thin=True``: the thin map T of SPEC.md §26,
+    normalised the same way. ``kw``: the plan's options, cached like ``segment``'s."""
     img = _one_image(img)
     r, n = _check_texton(radius, n_directions)
     nb, wts = _check_cues(bins, weights)
     seg = _plan(kw)
-    return _over_largest(seg.cue_edges_device(_batch_of_one(seg, img), radius=r, n_directions=n, bins=nb, weights=wts))
+    return _over_largest(seg.cue_edges_device(_batch_of_one(seg, img), radius=r, n_directions=n, bins=nb, weights=wts,
+                                              thin=bool(thin)))
 
 
 def segment_images(images, batch=64, **kw):
