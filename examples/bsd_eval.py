@@ -64,6 +64,9 @@ k-means runs. `--cue-edges --n-orient 5 --color-weight 0.125 --chroma-gain 4` pr
 `--thin` beside `--texton-edges` / `--cue-edges`: the maps thinned along their direction map (SPEC.md §26; G of §22 has none and stays).
 `--match [N]` beside them: two more columns, the ODS / OIS of the one-to-one matching score of §26 (`evaluate.match_scores`, on the
 host, minutes for the 24 images) at N of the 256 thresholds (32 when N is left out).
+`--match-device` beside them: two more columns, the ODS / OIS of the same score at ALL 256 thresholds from the device matcher (SPEC.md
+§27: `evaluate_gpu.edge_match_resident`, seconds); with `--match N` as well, a line per map says whether the two paths give the same
+floats at the N thresholds.
 """
 import os
 import sys
@@ -290,23 +293,40 @@ def edge_rows(n_orient, cw, g, smoothing, levels=256):
                                                                     best["ODS_regions"], best["OIS"]))
 
 
-def _match_cells(maps, groups, truth, step, levels, match):
+def _match_cells(maps, groups, truth, step, levels, match, device=False):
     """`--match [N]`: " ODS | OIS |" of the one-to-one matching score (SPEC.md §26, `evaluate.match_scores`, on the host) at N of
-    the `levels` thresholds of the sweep; nothing when `match` is 0."""
-    if not match:
-        return ""
+    the `levels` thresholds of the sweep; nothing when `match` is 0. `--match-device`: " ODS | OIS |" of the same score at all
+    `levels` thresholds from the device (§27, `evaluate_gpu.edge_match_resident`), and with both a second line: whether the host's
+    floats are the device's at the N thresholds."""
     from gabor_color_image_segmentation_amd.evaluate import match_scores, ods_ois
-    taus = [(2 * j + 1) * levels // (2 * match) for j in range(match)]
-    th = [step * (tau + 1) - 1 for tau in taus]
-    table = []
-    for group, m in zip(groups, maps):
-        host = m.cpu().numpy()
-        table += [match_scores(host[j], truth[i], th)["fmeasure"].tolist() for j, i in enumerate(group)]
-    best = ods_ois(table, th)
-    return " %.4f | %.4f |" % (best["ODS"], best["OIS"])
+    cells, taus, table = "", [], []
+    if match:
+        taus = [(2 * j + 1) * levels // (2 * match) for j in range(match)]
+        th = [step * (tau + 1) - 1 for tau in taus]
+        for group, m in zip(groups, maps):
+            host = m.cpu().numpy()
+            table += [match_scores(host[j], truth[i], th)["fmeasure"].tolist() for j, i in enumerate(group)]
+        best = ods_ois(table, th)
+        cells += " %.4f | %.4f |" % (best["ODS"], best["OIS"])
+    if device:
+        from gabor_color_image_segmentation_amd.evaluate_gpu import edge_match_resident
+        dev = []
+        for group, m in zip(groups, maps):
+            dev += edge_match_resident(m, truth.to_device(group), levels=levels, step=step)[2].tolist()
+        best = ods_ois(dev, [step * (tau + 1) - 1 for tau in range(levels)])
+        cells += " %.4f | %.4f |" % (best["ODS"], best["OIS"])
+        if match:
+            same = all(row[tau] == want for row, wants in zip(dev, table) for tau, want in zip(taus, wants))
+            cells += "\n  host and device F at tau = %s: %s" % (",".join(str(t) for t in taus), "the same floats" if same else "DIFFERENT")
+    return cells
 
 
-def texton_edge_rows(n_orient, cw, g, smoothing, k, radius, levels=256, thin=False, match=0):
+def _match_header(match, device):
+    return (" match ODS | match OIS |" if match else "") + (" device match ODS | device match OIS |" if device else ""), \
+        ("---|---|" if match else "") + ("---|---|" if device else "")
+
+
+def texton_edge_rows(n_orient, cw, g, smoothing, k, radius, levels=256, thin=False, match=0, match_device=False):
     """`--texton-edges`: E, TG and G (SPEC.md §24, §22) of the 24 val images at `levels` absolute thresholds each. `thin`: E and TG
     thinned along their direction map (§26; G has none)."""
     import numpy as np
@@ -322,8 +342,8 @@ def texton_edge_rows(n_orient, cw, g, smoothing, k, radius, levels=256, thin=Fal
     seg = Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, smoothing=smoothing, k=k)
     groups = [[i for i in ids if pack["img_" + i].shape[:2] == shape] for shape in sorted({pack["img_" + i].shape[:2] for i in ids})]
     batches = [torch.from_numpy(np.stack([pack["img_" + i] for i in group])).cuda() for group in groups]
-    print("| map | n_orient | w | g | K | k | radius | levels | step | ODS | threshold | OIS |" + (" match ODS | match OIS |" if match else ""))
-    print("|---|---|---|---|---|---|---|---|---|---|---|---|" + ("---|---|" if match else ""))
+    print("| map | n_orient | w | g | K | k | radius | levels | step | ODS | threshold | OIS |" + _match_header(match, match_device)[0])
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|" + _match_header(match, match_device)[1])
     mark = " thin" if thin else ""
     for name, make in (("E" + mark, lambda d: seg.texton_edges_device(d, radius=radius, thin=thin)),
                        ("TG" + mark, lambda d: seg.texton_edges_device(d, radius=radius, joined=False, thin=thin)),
@@ -336,10 +356,10 @@ def texton_edge_rows(n_orient, cw, g, smoothing, k, radius, levels=256, thin=Fal
         best = ods_ois(table, [step * (tau + 1) - 1 for tau in range(levels)])
         print("| %s | %d | %g | %d | %g | %d | %d | %d | %d | %.4f | %s > %d | %.4f |" % (
             name, n_orient, cw, g, smoothing, k, radius, levels, step, best["ODS"], name, best["ODS_regions"], best["OIS"])
-            + _match_cells(maps, groups, truth, step, levels, match))
+            + _match_cells(maps, groups, truth, step, levels, match, match_device))
 
 
-def cue_edge_rows(n_orient, cw, g, k, radius, bins, weights, levels=256, thin=False, match=0):
+def cue_edge_rows(n_orient, cw, g, k, radius, bins, weights, levels=256, thin=False, match=0, match_device=False):
     """`--cue-edges`: E' and PB (SPEC.md §25) and E (§24) of the 24 val images at `levels` absolute thresholds each. `thin`: every
     map thinned along its direction map (§26)."""
     import numpy as np
@@ -355,8 +375,8 @@ def cue_edge_rows(n_orient, cw, g, k, radius, bins, weights, levels=256, thin=Fa
     seg = Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, k=k)
     groups = [[i for i in ids if pack["img_" + i].shape[:2] == shape] for shape in sorted({pack["img_" + i].shape[:2] for i in ids})]
     batches = [torch.from_numpy(np.stack([pack["img_" + i] for i in group])).cuda() for group in groups]
-    print("| map | n_orient | w | g | k | radius | bins | weights | levels | step | ODS | threshold | OIS |" + (" match ODS | match OIS |" if match else ""))
-    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|" + ("---|---|" if match else ""))
+    print("| map | n_orient | w | g | k | radius | bins | weights | levels | step | ODS | threshold | OIS |" + _match_header(match, match_device)[0])
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|" + _match_header(match, match_device)[1])
     cue = dict(radius=radius, bins=bins, weights=weights, thin=thin)
     mark = " thin" if thin else ""
     for name, cues, make in (("E'" + mark, True, lambda d: seg.cue_edges_device(d, **cue)),
@@ -370,7 +390,7 @@ def cue_edge_rows(n_orient, cw, g, k, radius, bins, weights, levels=256, thin=Fa
         best = ods_ois(table, [step * (tau + 1) - 1 for tau in range(levels)])
         print("| %s | %d | %g | %d | %d | %d | %s | %s | %d | %d | %.4f | %s > %d | %.4f |" % (
             name, n_orient, cw, g, k, radius, bins if cues else "-", ",".join(str(v) for v in weights) if cues else "-",
-            levels, step, best["ODS"], name, best["ODS_regions"], best["OIS"]) + _match_cells(maps, groups, truth, step, levels, match))
+            levels, step, best["ODS"], name, best["ODS_regions"], best["OIS"]) + _match_cells(maps, groups, truth, step, levels, match, match_device))
 
 
 def _match_levels():
@@ -388,14 +408,14 @@ if __name__ == '__main__':
         cue_edge_rows(opt("--n-orient", int, 6), opt("--color-weight", float, 0.0), opt("--chroma-gain", int, 0), opt("--k", int, 8),
                       opt("--radius", int, 8), opt("--bins", int, 16),
                       tuple(int(v) for v in opt("--weights", str, "2,2,1,1").split(",")), thin="--thin" in sys.argv,
-                      match=_match_levels())
+                      match=_match_levels(), match_device="--match-device" in sys.argv)
         sys.exit(0)
     if "--texton-edges" in sys.argv:
         def opt(name, conv, default):
             return conv(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
         texton_edge_rows(opt("--n-orient", int, 6), opt("--color-weight", float, 0.0), opt("--chroma-gain", int, 0),
                          opt("--smoothing", float, 0.0), opt("--k", int, 8), opt("--radius", int, 8), thin="--thin" in sys.argv,
-                         match=_match_levels())
+                         match=_match_levels(), match_device="--match-device" in sys.argv)
         sys.exit(0)
     if "--edges" in sys.argv:
         def opt(name, conv, default):

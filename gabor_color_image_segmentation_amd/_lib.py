@@ -116,6 +116,14 @@ THIN_EXTENSIONS = {
     "gcs_edge_thin": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes): every symbol include/gcs_match.h declares (SPEC.md §27), optional in the same way.
+MATCH_EXTENSIONS = {
+    "gcs_match_offsets": (_i, [_i, _vp, _vp]),
+    "gcs_truth_thin": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "gcs_edge_match_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "gcs_edge_match": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+}
+
 
 class GcsError(RuntimeError):
     pass
@@ -144,7 +152,7 @@ def load():
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)      # AttributeError here = header/library mismatch
         fn.restype, fn.argtypes = res, args
-    for name, (res, args) in list(EXTENSIONS.items()) + list(THIN_EXTENSIONS.items()):
+    for name, (res, args) in list(EXTENSIONS.items()) + list(THIN_EXTENSIONS.items()) + list(MATCH_EXTENSIONS.items()):
         fn = getattr(lib, name, None)    # optional: an older library of the same ABI lacks it
         if fn is not None:
             fn.restype, fn.argtypes = res, args

@@ -13,6 +13,8 @@ Four layers, each with the C entry points it calls:
    ``sweep_counts`` / ``sweep_scores``; ``region_sweep_resident`` (gcs_region_counts_batch[_u8], gcs_region_sweep) with
    ``sweep_agreement``; ``under_sweep_resident`` (gcs_region_counts_batch[_u8], gcs_region_sweep_under) and ``cut_shapes_device``
    (gcs_cut_shapes) with ``sweep_reference_scores``; ``metrics_sweep_resident`` chains them all (SPEC.md §15 - §17).
+   ``edge_match_counts_resident`` / ``edge_match_resident`` (gcs_truth_thin, gcs_match_offsets, gcs_edge_match): the one-to-one
+   matching score of an edge map at every threshold at once (SPEC.md §27).
 
 The host arithmetic exists once: ``_boundary_scores``, ``_region_scores_batch`` and ``evaluate.agreement_from_sums``.
 """
@@ -29,6 +31,8 @@ from .evaluate import agreement_from_sums
 
 SWEEP_LEVELS = 4096                                              # the most labels a region tree has (SPEC.md §14)
 SWEEP_CUTS = 64                                                  # the most cuts one gcs_region_sweep call takes
+MATCH_LEVELS = 256                                               # the most levels gcs_edge_match takes (SPEC.md §27)
+MATCH_DIST2_MAX = 160                                            # the largest D2 gcs_match_offsets makes a table for
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -419,6 +423,24 @@ class DeviceTruth:
         self._out = None                                       # the _ResultBlock
         self._scratch = None
         self._pending = None                                   # weak reference to the submission that owns the result block
+        self._thin = None                                      # SPEC.md §27: (thin planes, |Q_t| on the device, |Q_t| on the host)
+
+    def thin_planes(self):
+        """SPEC.md §27: ``(thin, counts, n_thin)`` - the contours Q_t = ``evaluate.thin_boundaries(s_t)`` as a (T,H,W) uint8
+        device tensor, |Q_t| as a (T,) int32 device tensor and as a host int64 array. Made by gcs_truth_thin on first use and
+        kept; nothing else of the truth changes."""
+        import torch
+        if self._thin is None:
+            lib = _match_lib()
+            if self.h > 4096 or self.w > 4096:
+                raise ValueError("the matcher takes images of at most 4096 x 4096 pixels")
+            with torch.cuda.device(self.device):
+                thin = torch.empty((self.t, self.h, self.w), dtype=torch.uint8, device=self.device)
+                counts = torch.empty(self.t, dtype=torch.int32, device=self.device)
+                _lib.check(lib.gcs_truth_thin(self.maps.data_ptr(), self.t, self.h, self.w, int(self.u8), thin.data_ptr(),
+                                              counts.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream), "gcs_truth_thin")
+                self._thin = (thin, counts, counts.cpu().numpy().astype(np.int64))
+        return self._thin
 
     def _uncollected(self):
         """The submission whose numbers still sit in this truth's ONE result block, or None (collected, or dropped)."""
@@ -666,6 +688,106 @@ def edge_sweep_resident(edges, truth: DeviceTruth, levels=256, step=None):
     for tau, c in enumerate(counts):
         for i in range(b):
             sc = edge_scores_from_counts(c[i], c[b + 3 * first[i]:b + 3 * first[i + 1]])
+            out[0, i, tau], out[1, i, tau], out[2, i, tau] = sc["recall"], sc["precision"], sc["fmeasure"]
+    return out[0], out[1], out[2], step
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# 4a'. One-to-one matching counts of a level map at every level at once (SPEC.md §27): the levels are nested, so one incremental
+# maximum matching per annotator map serves them all; one 64-lane workgroup per map, all maps of the batch side by side.
+
+def _match_lib():
+    lib = _lib.load()
+    for name in _lib.MATCH_EXTENSIONS:
+        if not hasattr(lib, name):
+            raise ValueError(f"the device matcher needs a library that has it (this libgcs.so does not export {name})")
+    return lib
+
+
+def _match_offsets(lib, d2):
+    table, n = np.zeros((512, 2), np.int32), np.zeros(1, np.int32)
+    _lib.check(lib.gcs_match_offsets(int(d2), table.ctypes.data, n.ctypes.data), "gcs_match_offsets")
+    return table[:int(n[0])].copy()
+
+
+def _match_arguments(shape, device, truth, levels, max_dist2):
+    """Every check of the match calls, before anything runs -> (levels, D2)."""
+    from .evaluate import match_distance2
+    b, h, w = shape
+    _need_match((b, h, w), device, truth, "level map")
+    levels = int(levels)
+    if not 1 <= levels <= MATCH_LEVELS:
+        raise ValueError(f"levels must be in 1 .. {MATCH_LEVELS}")
+    if h > 4096 or w > 4096:
+        raise ValueError("the matcher takes images of at most 4096 x 4096 pixels")
+    d2 = match_distance2(h, w) if max_dist2 is None else int(max_dist2)
+    if not 0 <= d2 <= MATCH_DIST2_MAX:
+        raise ValueError(f"max_dist2 must be in 0 .. {MATCH_DIST2_MAX}, got {d2}")
+    return levels, d2
+
+
+def edge_match_counts_resident(q, truth: DeviceTruth, levels, max_dist2=None, stats=False):
+    """SPEC.md §27. q: (B,H,W) int32 device tensor of levels, read as clamp(q, 0, levels); truth: the resident ground truth of the
+    same images. Returns host int64 arrays ``(matched [T][levels], above [B][levels], n_thin [T])``: matched[t][tau] = the
+    cardinality of a maximum matching between {q_b > tau} (b = img_of[t]) and Q_t = ``evaluate.thin_boundaries(s_t)`` with a pair
+    allowed iff dy^2 + dx^2 <= ``max_dist2`` (None: ``evaluate.match_distance2(H, W)``; at most 160), above[b][tau] = #{q_b > tau},
+    n_thin[t] = |Q_t|: what ``evaluate.match_count`` gives level by level. ``stats=True`` appends the kernel's uint32 [T][4]
+    counters per map: search steps, 64-lane probes, deepest stack, failed searches. Buffers of its own."""
+    import torch
+    _need_labels(q, 3, "q")
+    levels, d2 = _match_arguments(q.shape, q.device, truth, levels, max_dist2)
+    lib = _match_lib()
+    b, h, w = q.shape
+    q = q.contiguous()
+    with torch.cuda.device(truth.device):
+        thin, _, n_thin = truth.thin_planes()
+        offsets = torch.from_numpy(_match_offsets(lib, d2)).to(truth.device)
+        cap = int(n_thin.max()) + 1
+        ws = torch.empty(lib.gcs_edge_match_bytes(b, truth.t, h, w, cap), dtype=torch.uint8, device=truth.device)
+        out = torch.empty((truth.t + b, levels), dtype=torch.int32, device=truth.device)
+        _lib.check(lib.gcs_edge_match(q.data_ptr(), thin.data_ptr(), truth.img_of_d.data_ptr(), b, truth.t, h, w, levels,
+                                      offsets.data_ptr(), len(offsets), cap, ws.data_ptr(), out.data_ptr(),
+                                      out[truth.t:].data_ptr(), torch.cuda.current_stream(truth.device).cuda_stream),
+                   "gcs_edge_match")
+        raw = out.cpu().numpy().astype(np.int64)
+        counters = ws[:16 * truth.t].cpu().numpy().view(np.uint32).reshape(truth.t, 4) if stats else None
+    if (raw[:truth.t] < 0).any():
+        raise _lib.GcsError("gcs_edge_match: a map's search stack overflowed")       # cap = max |Q_t| + 1: cannot happen
+    res = (raw[:truth.t].copy(), raw[truth.t:].copy(), n_thin.copy())
+    return res + (counters,) if stats else res
+
+
+def edge_match_resident(edges, truth: DeviceTruth, levels=256, step=None, max_dist2=None):
+    """One-to-one matching scores of an edge-strength map at ``levels`` thresholds at once (SPEC.md §27, the metric of §26).
+    edges: (B,H,W) int32 device tensor of non-negative strengths; truth: the resident ground truth of the same images. The map is
+    quantised exactly as in ``edge_sweep_resident`` (q = min(levels, edges // step), ``step`` defaulting to
+    ceil((batch max + 1) / levels)); level tau is the boundary map edges >= step (tau + 1). Returns ``(recall, precision,
+    fmeasure, step)``, float64 host arrays [B][levels]: row i holds, float for float, ``evaluate.match_scores(edges[i], truths_i,
+    [step * (tau + 1) - 1 for tau in range(levels)], max_dist2)`` - the same integers through ``evaluate.edge_scores_from_counts``
+    - zeros where a level leaves an image without a boundary pixel, ZeroDivisionError for an annotator map without a contour."""
+    import torch
+    from .evaluate import edge_scores_from_counts
+    _need_labels(edges, 3, "edges")
+    levels, d2 = _match_arguments(edges.shape, edges.device, truth, levels, max_dist2)
+    _match_lib()
+    b = edges.shape[0]
+    with torch.cuda.device(truth.device):
+        if step is None:
+            step = -(-(int(edges.max().item()) + 1) // levels)
+        step = int(step)
+        if step < 1:
+            raise ValueError("step must be at least 1")
+        q = torch.clamp(torch.div(edges, step, rounding_mode="floor"), max=levels).to(torch.int32).contiguous()
+    matched, above, n_thin = edge_match_counts_resident(q, truth, levels, d2)
+    m, g, n = matched.astype(np.float64).tolist(), above.astype(np.float64).tolist(), n_thin.astype(np.float64).tolist()
+    first = truth.first.tolist()
+    out = np.zeros((3, b, levels))
+    for i in range(b):
+        for tau in range(levels):
+            ann = []
+            for t in range(first[i], first[i + 1]):
+                ann += [m[t][tau], n[t], m[t][tau]]
+            sc = edge_scores_from_counts(g[i][tau], ann)
             out[0, i, tau], out[1, i, tau], out[2, i, tau] = sc["recall"], sc["precision"], sc["fmeasure"]
     return out[0], out[1], out[2], step
 
