@@ -124,6 +124,11 @@ MATCH_EXTENSIONS = {
     "gcs_edge_match": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes): every symbol include/gcs_model.h declares (SPEC.md §28), optional in the same way.
+MODEL_EXTENSIONS = {
+    "gcs_kmeans_evaluate": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+}
+
 
 class GcsError(RuntimeError):
     pass
@@ -152,7 +157,8 @@ def load():
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)      # AttributeError here = header/library mismatch
         fn.restype, fn.argtypes = res, args
-    for name, (res, args) in list(EXTENSIONS.items()) + list(THIN_EXTENSIONS.items()) + list(MATCH_EXTENSIONS.items()):
+    for name, (res, args) in list(EXTENSIONS.items()) + list(THIN_EXTENSIONS.items()) + list(MATCH_EXTENSIONS.items()) \
+            + list(MODEL_EXTENSIONS.items()):
         fn = getattr(lib, name, None)    # optional: an older library of the same ABI lacks it
         if fn is not None:
             fn.restype, fn.argtypes = res, args

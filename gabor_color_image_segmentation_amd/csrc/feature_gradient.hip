@@ -5,7 +5,7 @@
 //               whole (8 >> L) x (32 >> L) rectangle). First the level >= 1 terms of that rectangle, ONE thread per level pixel
 //               (threads 0..63: level 1, 64..79: level 2, 80..83: level 3), into LDS; then a thread per full-resolution pixel adds
 //               its level-0 term and the terms of its parents and takes the exact square root. Every thread locates its four clamped
-//               neighbours once (gcs_locate) and then steps through the level's planes at a constant stride, as rt_slab_walk does.
+//               neighbours once (slab_tap) and then steps through the level's planes at a constant stride, as rt_slab_walk does.
 //               (-DGCS_FG_PER_PIXEL: every pixel recomputes the terms of its parents itself, for same-box A/B runs: DESIGN.md §4.20.)
 // No workspace, no allocation, no host synchronisation: one launch (capturable).
 #include "slab_slots.h"
@@ -17,56 +17,17 @@ typedef unsigned long long u64;
 constexpr int FG_TW = 32, FG_TH = 8, FG_THREADS = FG_TW * FG_TH;
 constexpr int FG_HW_MAX = 4096, FG_D_MAX = 207;
 
-// One neighbour of a level pixel: where its value of the level's first plane sits in the slab of its image.
-struct FgTap {
-    const unsigned char *p;           // wide slab: the value's address
-    unsigned slot, nb;                // split slab: slot (LO byte index) and nibble byte (relative to MID / TOP)
-    int sh;                           // split slab: the nibble's shift
-    bool top;                         // split slab: the tile's level flag (some TOP nibble of the level is non-zero)
-};
-
-__device__ __forceinline__ FgTap fg_tap(const GcsLayout &lo, const unsigned char *img, int L, int yl, int xl) {
-    int blk, iy, ix;
-    gcs_locate(lo, yl << L, xl << L, blk, iy, ix);      // any full-resolution pixel of the level pixel's block holds its value
-    const unsigned tile = (unsigned)(blk >> 2), q = (unsigned)(blk & 3), side = 8u >> L;
-    const unsigned sy = (unsigned)iy >> L, sx = (unsigned)ix >> L;
-    FgTap t{};
-    if (lo.split) {
-        t.slot = tile * (unsigned)lo.S + (unsigned)lo.sl0[L] + sy * 4u * side + q * side + sx;
-        sm_nibble(L, t.slot, t.nb, t.sh);
-        t.top = img[lo.flag_off + 4u * tile + (unsigned)L] != 0;
-    } else {
-        t.p = img + (size_t)tile * lo.tile_bytes + lo.off[L] + (size_t)(q * side * side + sy * side + sx) * 2;
-    }
-    return t;
-}
-
-// The tap's value of the plane it stands on (plain uint16), then one plane on.
-template <bool SPLIT>
-__device__ __forceinline__ int fg_next(const GcsLayout &lo, const unsigned char *img, FgTap &t, unsigned npl) {
-    unsigned v;
-    if (SPLIT) {
-        v = (img[t.slot] ^ 0x80u) | (((unsigned)img[lo.mid_off + t.nb] >> t.sh & 15u) << 8);
-        if (t.top) v |= ((unsigned)img[lo.top_off + t.nb] >> t.sh & 15u) << 12;
-        t.slot += npl, t.nb += npl >> 1;              // (a plane is a multiple of the nibble group: same shift)
-    } else {
-        v = (unsigned)*reinterpret_cast<const uint16_t *>(t.p) ^ 0x8080u;
-        t.p += 2 * npl;
-    }
-    return (int)v;
-}
-
 // (DX_L >> 2L) + (DY_L >> 2L) of SPEC.md §22 at level pixel (yl, xl), which lies inside the level image.
 template <bool SPLIT>
 __device__ __forceinline__ u64 fg_level(const GcsLayout &lo, const unsigned char *img, int L, int yl, int xl) {
     const int HL = lo.HL[L], WL = lo.WL[L];
-    FgTap xm = fg_tap(lo, img, L, yl, max(xl - 1, 0)), xp = fg_tap(lo, img, L, yl, min(xl + 1, WL - 1));
-    FgTap ym = fg_tap(lo, img, L, max(yl - 1, 0), xl), yp = fg_tap(lo, img, L, min(yl + 1, HL - 1), xl);
+    SlabTap xm = slab_tap(lo, img, L, yl, max(xl - 1, 0)), xp = slab_tap(lo, img, L, yl, min(xl + 1, WL - 1));
+    SlabTap ym = slab_tap(lo, img, L, max(yl - 1, 0), xl), yp = slab_tap(lo, img, L, min(yl + 1, HL - 1), xl);
     const unsigned npl = (unsigned)KP_TP >> (2 * L);
     u64 dx = 0, dy = 0;
     for (int d = lo.DL[L]; d > 0; --d) {
-        const int a = fg_next<SPLIT>(lo, img, xp, npl) - fg_next<SPLIT>(lo, img, xm, npl);
-        const int c = fg_next<SPLIT>(lo, img, yp, npl) - fg_next<SPLIT>(lo, img, ym, npl);
+        const int a = slab_next<SPLIT>(lo, img, xp, npl) - slab_next<SPLIT>(lo, img, xm, npl);
+        const int c = slab_next<SPLIT>(lo, img, yp, npl) - slab_next<SPLIT>(lo, img, ym, npl);
         dx += (u64)((unsigned)a * (unsigned)a);       // |a| <= 65535: a^2 < 2^32
         dy += (u64)((unsigned)c * (unsigned)c);
     }

@@ -1,5 +1,6 @@
 // slab_slots.h — the slab seen slot by slot at a level's own resolution: what the kernels that rewrite planes of a filled slab in
-// place share (smooth.hip: SPEC.md §10, position.hip: SPEC.md §12). Layout and names: common.h.
+// place share (smooth.hip: SPEC.md §10, position.hip: SPEC.md §12), and the plane-after-plane reader of the kernels that only read
+// it (SlabTap below). Layout and names: common.h.
 #pragma once
 #include "common.h"
 
@@ -31,6 +32,47 @@ __device__ __forceinline__ unsigned sm_decode(const GcsLayout &lo, const unsigne
     unsigned v = (img[slot] ^ 0x80u) | (((unsigned)img[lo.mid_off + nb] >> sh & 15u) << 8);
     if (img[lo.flag_off + 4u * tile + (unsigned)L]) v |= ((unsigned)img[lo.top_off + nb] >> sh & 15u) << 12;
     return v;
+}
+
+// ---- a level pixel read plane after plane (feature_gradient.hip: SPEC.md §22, kmeans_model.hip: SPEC.md §28): the pixel is located
+// once, then every plane of its level is one constant stride on.
+// Where the pixel's value of the level's first plane sits in the slab of its image.
+struct SlabTap {
+    const unsigned char *p;           // wide slab: the value's address
+    unsigned slot, nb;                // split slab: slot (LO byte index) and nibble byte (relative to MID / TOP)
+    int sh;                           // split slab: the nibble's shift
+    bool top;                         // split slab: the tile's level flag (some TOP nibble of the level is non-zero)
+};
+
+__device__ __forceinline__ SlabTap slab_tap(const GcsLayout &lo, const unsigned char *img, int L, int yl, int xl) {
+    int blk, iy, ix;
+    gcs_locate(lo, yl << L, xl << L, blk, iy, ix);      // any full-resolution pixel of the level pixel's block holds its value
+    const unsigned tile = (unsigned)(blk >> 2), q = (unsigned)(blk & 3), side = 8u >> L;
+    const unsigned sy = (unsigned)iy >> L, sx = (unsigned)ix >> L;
+    SlabTap t{};
+    if (lo.split) {
+        t.slot = tile * (unsigned)lo.S + (unsigned)lo.sl0[L] + sy * 4u * side + q * side + sx;
+        sm_nibble(L, t.slot, t.nb, t.sh);
+        t.top = img[lo.flag_off + 4u * tile + (unsigned)L] != 0;
+    } else {
+        t.p = img + (size_t)tile * lo.tile_bytes + lo.off[L] + (size_t)(q * side * side + sy * side + sx) * 2;
+    }
+    return t;
+}
+
+// The tap's value of the plane it stands on (plain uint16), then one plane on.
+template <bool SPLIT>
+__device__ __forceinline__ int slab_next(const GcsLayout &lo, const unsigned char *img, SlabTap &t, unsigned npl) {
+    unsigned v;
+    if (SPLIT) {
+        v = (img[t.slot] ^ 0x80u) | (((unsigned)img[lo.mid_off + t.nb] >> t.sh & 15u) << 8);
+        if (t.top) v |= ((unsigned)img[lo.top_off + t.nb] >> t.sh & 15u) << 12;
+        t.slot += npl, t.nb += npl >> 1;              // (a plane is a multiple of the nibble group: same shift)
+    } else {
+        v = (unsigned)*reinterpret_cast<const uint16_t *>(t.p) ^ 0x8080u;
+        t.p += 2 * npl;
+    }
+    return (int)v;
 }
 
 // Slot (sy, sx) of level L in block blk -> the level pixel it holds; false: the slot holds no pixel.

@@ -24,6 +24,7 @@ import numpy as np
 
 from . import _lib
 from .bank import GaborBank, check_color_weight, check_position_range, check_position_weight, make_bank, smoothing_taps
+from .kmeans_model import KMeansModel, confidence_of
 
 # Feature-slab bytes per group of a per-image batch. Large on purpose: measured in round 4 with the current kernels
 # (tools/cache_resident_pass.py, profiles/r4_notes.md "Infinity-Cache-resident groups"): a pass that re-reads a slab small enough
@@ -622,6 +623,29 @@ class HipOps:
             raise ValueError("out must be a contiguous (B,H,W) int32 tensor")
         _lib.check(self.lib.gcs_feature_gradient(feats.data_ptr(), b, h, w, *self._bk, out.data_ptr(), self._stream()),
                    "gcs_feature_gradient")
+
+    @_on_device
+    def kmeans_evaluate(self, feats, cent, b, h, w, k, n_sets, labels=None, best=None, second=None, stats=None):
+        """SPEC.md §28: the slab ``feats`` measured against the codebooks ``cent``, a contiguous (n_sets, k, D) int16 tensor holding
+        the uint16 centroids (what ``kmeans_init`` and the Lloyd loop leave in it), ``n_sets`` 1 or B. Outputs, each optional and
+        at least one given: ``labels`` (B,H,W) int32, ``best`` and ``second`` (B,H,W) int64 - the squared distance to the nearest
+        and to the second nearest centroid -, ``stats`` (n_sets, k, 2) int64 = (count, inertia) per cluster, zeroed by the call
+        itself. One launch (two with ``stats``), no workspace (capturable as it is)."""
+        if not hasattr(self.lib, "gcs_kmeans_evaluate"):
+            raise _lib.GcsError("the k-means model needs a library that has it (this libgcs.so does not export gcs_kmeans_evaluate)")
+        torch = self.torch
+        if cent is None or (labels is None and best is None and second is None and stats is None):
+            raise ValueError("kmeans_evaluate needs the centroids and at least one of labels, best, second and stats")
+        self._need(cent, (torch.int16, torch.uint16), (int(n_sets), int(k), self.bank.n_features),
+                   "cent must be a contiguous (n_sets, k, D) int16 tensor")
+        self._need(labels, torch.int32, (b, h, w), "labels must be a contiguous (B,H,W) int32 tensor")
+        self._need(best, torch.int64, (b, h, w), "best must be a contiguous (B,H,W) int64 tensor")
+        self._need(second, torch.int64, (b, h, w), "second must be a contiguous (B,H,W) int64 tensor")
+        self._need(stats, torch.int64, (int(n_sets), int(k), 2), "stats must be a contiguous (n_sets, k, 2) int64 tensor")
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(self.lib.gcs_kmeans_evaluate(feats.data_ptr(), cent.data_ptr(), b, h, w, *self._bk, int(k), int(n_sets),
+                                                ptr(labels), ptr(best), ptr(second), ptr(stats), self._stream()),
+                   "gcs_kmeans_evaluate")
 
     def texton_masks(self, r, n):
         """SPEC.md §24: the half-disc table of radius ``r`` and ``n`` directions, a (n, 2, 2r+1) int32 device tensor holding the
@@ -1253,6 +1277,11 @@ class Segmenter:
         self.position_weight = check_position_weight(position_weight)   # SPEC.md §12: a coordinate slot behind every scale's filters
         self.bank = make_bank(n_scales, n_orient, ksize, f_max, ratio, bandwidth, self.color_weight, self.position_weight)
         self.smoothing = _check_smoothing(smoothing, self.bank)     # SPEC.md §10, between the Gabor stage and k-means
+        # SPEC.md §28: what a k-means model must share with the plan that takes it - the feature space and k
+        self.model_signature = dict(n_scales=int(n_scales), n_orient=int(n_orient), ksize=int(ksize), f_max=float(f_max),
+                                    ratio=float(ratio), bandwidth=float(bandwidth), color_weight=float(self.color_weight),
+                                    chroma_gain=int(self.chroma_gain), smoothing=float(self.smoothing),
+                                    position_weight=int(self.position_weight), k=self.k)
         self.n_superpixels, self.spatial_weight = _check_superpixels(n_superpixels, spatial_weight)   # SPEC.md §13 (0: §4's Lloyd stage)
         if self.n_superpixels > 0 and self.bank.n_features > _SP_D_MAX:
             raise ValueError(f"n_superpixels needs a bank of at most {_SP_D_MAX} features, this one has {self.bank.n_features}")
@@ -1499,12 +1528,18 @@ class Segmenter:
         return max(1, min(b, _SLAB_BUDGET // max(1, per_image)))
 
     # ---- device-resident API (used by bench.py: inputs already in HBM)
-    def segment_device(self, imgs, mode="per_image", out=None, dist_group=None, group=None):
-        """imgs: (B,H,W,3) uint8 device tensor -> (B,H,W) int32 device tensor."""
+    def segment_device(self, imgs, mode="per_image", out=None, dist_group=None, group=None, codebook=None, refine=0):
+        """imgs: (B,H,W,3) uint8 device tensor -> (B,H,W) int32 device tensor. ``codebook``: a ``KMeansModel`` (SPEC.md §28) in
+        place of the centroids the Lloyd stage would make for itself - ``refine = 0``: frozen, the stage is one assign pass;
+        ``refine = m``: m update passes from it first. See ``predict_device``."""
         torch = _torch()
         self._check_args(imgs, mode, dist_group=dist_group, kind="tensor")
         imgs = imgs.contiguous()
         b, h, w, _ = imgs.shape
+        opt = self._opt
+        if codebook is not None:
+            codebook, refine = self._codebook_check(codebook, b, mode, refine, dist_group)
+            opt = opt._replace(n_iter=refine + 1)
         if self.native and imgs.device != self.ops.device:
             raise ValueError(f"imgs live on {imgs.device}, this Segmenter on {self.ops.device}")
         if out is None:
@@ -1518,7 +1553,8 @@ class Segmenter:
                 n = min(g, b - g0)
                 ws = self._workspace(n, h, w, mode) if n == g else self._tail_workspace(n, h, w, mode)
                 _step_features(self.ops, self._opt, ws, imgs[g0:g0 + n], n, h, w)
-                _step_cluster(self.ops, self._opt, ws, out[g0:g0 + n], n, h, w, mode, self.debug, dist_group)
+                _step_cluster(self.ops, opt, ws, out[g0:g0 + n], n, h, w, mode, self.debug, dist_group,
+                              **({} if codebook is None else {"init": self._codebook_init(codebook, g0, n)}))
                 self._note_plane(ws)
             if not self._post_passes:                      # (SPEC.md §18: the step's map is connected and numbered as §7 numbers)
                 return out
@@ -1531,6 +1567,137 @@ class Segmenter:
                 self.ops.connected_regions(out, regions)
                 out.copy_(regions)
         return out
+
+    # ---- the k-means model (SPEC.md §28)
+    def _codebook_check(self, model, b, mode, refine=0, dist_group=None):
+        """The argument rules of a call that takes a codebook, before anything is launched -> (the model on the plan's device,
+        ``refine`` as an int)."""
+        if not isinstance(model, KMeansModel):
+            raise ValueError(f"codebook must be a KMeansModel, got {type(model).__name__}")
+        if self.n_superpixels > 0:
+            raise ValueError("a codebook takes the place of the Lloyd stage's centroids: it needs n_superpixels = 0")
+        if dist_group is not None:
+            raise ValueError("a codebook does not run over a dist_group")
+        m = _as_int(refine)
+        if m is None or m < 0:
+            raise ValueError(f"refine must be an integer >= 0, got {refine!r}")
+        if model.signature != self.model_signature:
+            diff = sorted(n for n in set(model.signature) | set(self.model_signature)
+                          if model.signature.get(n) != self.model_signature.get(n))
+            raise ValueError(f"the model was fitted in another feature space than this plan's: {', '.join(diff)} differ")
+        if model.n_features != self.bank.n_features:
+            raise ValueError(f"the model has {model.n_features} features, this plan's bank {self.bank.n_features}")
+        if model.n_sets != 1 and (model.n_sets != b or mode != "per_image"):
+            raise ValueError(f"a model of {model.n_sets} codebooks labels a batch of {model.n_sets} images in mode 'per_image', "
+                             f"got {b} images in mode {mode!r}")
+        return model.to(self.ops.device), m
+
+    @staticmethod
+    def _codebook_init(model, g0, n):
+        """``lloyd``'s ``init`` for images [g0, g0 + n) of a batch: the model's centroids copied into the step's own (one codebook
+        is broadcast over the sets), which the update passes of a warm start then change - the model never is."""
+        i16 = _torch().int16
+        src = model.centroids.view(i16)
+
+        def init(cent):
+            cent.copy_(src if model.n_sets == 1 else src[g0:g0 + n])
+        return init
+
+    def _model_steps(self, imgs, mode, codebook, opt, out):
+        """The step on every group of a (B,H,W,3) uint8 device tensor, checked by the caller: yields (g0, n, workspace) with the
+        group's slab filled and, where ``opt`` is given, its Lloyd stage run at ``opt`` into ``out`` (from ``codebook``, or from
+        the init of SPEC.md §4), the final centroids in the workspace's ``cent``."""
+        b, h, w, _ = imgs.shape
+        g = self.group_size(b, h, w, mode)
+        for g0 in range(0, b, g):
+            n = min(g, b - g0)
+            ws = self._workspace(n, h, w, mode) if n == g else self._tail_workspace(n, h, w, mode)
+            _step_features(self.ops, self._opt, ws, imgs[g0:g0 + n], n, h, w)
+            if opt is not None:
+                _step_cluster(self.ops, opt, ws, out[g0:g0 + n], n, h, w, mode, self.debug,
+                              **({} if codebook is None else {"init": self._codebook_init(codebook, g0, n)}))
+            yield g0, n, ws
+
+    def _model_args(self, imgs, mode, model, refine=0):
+        """What the entry points of the model share in front of their first launch -> (imgs, model, refine)."""
+        self._check_args(imgs, mode, kind="tensor")
+        if self.n_superpixels > 0:
+            raise ValueError("the k-means model is the Lloyd stage's: it needs n_superpixels = 0")
+        if not hasattr(self.ops, "kmeans_evaluate"):
+            raise ValueError("the k-means model needs ops that have kmeans_evaluate")
+        if self.native and imgs.device != self.ops.device:
+            raise ValueError(f"imgs live on {imgs.device}, this Segmenter on {self.ops.device}")
+        if model is not None:
+            model, refine = self._codebook_check(model, imgs.shape[0], mode, refine)
+        return imgs.contiguous(), model, refine
+
+    def fit_device(self, imgs, mode="global", init=None):
+        """(B,H,W,3) uint8 device tensor -> the ``KMeansModel`` of the plan's own step on it (SPEC.md §28): the centroids the Lloyd
+        loop ends on - one codebook in mode "global", B in "per_image" - with the count and the inertia of every cluster under
+        them, from one evaluate launch on the slab the step left in its workspace. ``init``: a model to start the loop from in
+        place of the init of SPEC.md §4 (the plan's ``n_iter`` passes either way)."""
+        torch = _torch()
+        imgs, init, _ = self._model_args(imgs, mode, init)
+        b, h, w, _ = imgs.shape
+        n_sets = b if mode == "per_image" else 1
+        with self._device():
+            labels = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
+            cent = torch.empty((n_sets, self.k, self.bank.n_features), dtype=torch.int16, device=imgs.device)
+            stats = torch.empty((n_sets, self.k, 2), dtype=torch.int64, device=imgs.device)
+            for g0, n, ws in self._model_steps(imgs, mode, init, self._opt, labels):
+                ns = n if mode == "per_image" else 1
+                cent[g0:g0 + ns].copy_(ws["cent"])
+                self.ops.kmeans_evaluate(ws["feats"], ws["cent"], n, h, w, self.k, ns, stats=stats[g0:g0 + ns])
+        return KMeansModel(cent, stats[..., 0].contiguous(), stats[..., 1].contiguous(), self.model_signature)
+
+    def predict_device(self, imgs, model, refine=0, mode="per_image", out=None):
+        """(B,H,W,3) uint8 device tensor -> (B,H,W) int32 labels under ``model`` (SPEC.md §28): the feature stages, then the Lloyd
+        stage started from a copy of the model's centroids with ``n_iter = refine + 1`` - ``refine = 0`` is ONE assign pass with
+        the codebook as it is, so cluster ids mean the same from call to call. A one-codebook model is shared by every image;
+        ``refine = m > 0`` with ``mode = "per_image"`` lets every image refine its own copy, with "global" one copy is refined over
+        the batch. A model of B codebooks labels image i of a batch of B with codebook i. The plan's post-passes and
+        ``tree_nodes = "clusters"`` run as they do without a codebook. ValueError: ``n_superpixels > 0``, a model whose signature
+        is not the plan's, a B-codebook model on a batch of another size or in mode "global"."""
+        return self.segment_device(imgs, mode, out, codebook=model, refine=refine)
+
+    def evaluate_device(self, imgs, model=None, mode="per_image", labels=True, best=False, second=False, stats=True):
+        """(B,H,W,3) uint8 device tensor -> dict of the outputs of SPEC.md §28 that were asked for: ``labels`` (B,H,W) int32,
+        ``best`` and ``second`` (B,H,W) int64, ``stats`` (n_sets, k, 2) int64 = (count, inertia), measured against ``model``'s
+        codebooks as they are, or, without one, against the centroids the plan's own Lloyd loop ends on in ``mode``."""
+        torch = _torch()
+        if not (labels or best or second or stats):
+            raise ValueError("evaluate_device needs at least one of labels, best, second and stats")
+        imgs, model, _ = self._model_args(imgs, mode, model)
+        b, h, w, _ = imgs.shape
+        n_sets = model.n_sets if model is not None else (b if mode == "per_image" else 1)
+        res = {}
+        with self._device():
+            new = lambda dt: torch.empty((b, h, w), dtype=dt, device=imgs.device)
+            for name, on, dt in (("labels", labels, torch.int32), ("best", best, torch.int64), ("second", second, torch.int64)):
+                if on:
+                    res[name] = new(dt)
+            if stats:
+                res["stats"] = torch.zeros((n_sets, self.k, 2), dtype=torch.int64, device=imgs.device)
+            own = new(torch.int32) if model is None else None
+            for g0, n, ws in self._model_steps(imgs, mode, None, self._opt if model is None else None, own):
+                if model is None:
+                    cent, ns = ws["cent"], n if mode == "per_image" else 1
+                else:
+                    ns = 1 if n_sets == 1 else n
+                    cent = model.centroids.view(torch.int16)[0 if n_sets == 1 else g0:][:ns]
+                part = torch.empty((ns, self.k, 2), dtype=torch.int64, device=imgs.device) if stats else None
+                self.ops.kmeans_evaluate(ws["feats"], cent, n, h, w, self.k, ns, stats=part,
+                                         **{name: res[name][g0:g0 + n] for name in ("labels", "best", "second") if name in res})
+                if stats:                                  # (one codebook over several groups: the groups' tables add up)
+                    res["stats"][0 if n_sets == 1 else g0:][:ns] += part
+        return res
+
+    def confidence_device(self, imgs, model=None, mode="per_image"):
+        """(B,H,W,3) uint8 device tensor -> (labels (B,H,W) int32, confidence (B,H,W) float32 in [0, 1]) of SPEC.md §28:
+        (second - best) / second in float64, 0 where second = 0 - 0 for a pixel as close to another centroid as to its own, 1 for a
+        pixel on its centroid. ``model``, ``mode``: as in ``evaluate_device``."""
+        res = self.evaluate_device(imgs, model, mode, labels=True, best=True, second=True, stats=False)
+        return res["labels"], confidence_of(res["best"], res["second"])
 
     def _superpixel_check(self, h, w, mode="per_image", out_dtype=None, dist_group=None):
         """The argument rules of SPEC.md §13 for one image shape (``h`` None: only those that need no shape), before anything is
@@ -1848,7 +2015,7 @@ class Segmenter:
         """``shard_rows`` for THIS plan's bank (its pyramid depth and kernel size decide alignment and halo)."""
         return shard_rows(height, world, rank, self.bank.n_levels, self.bank.ksize)
 
-    def segment_rows_sharded_device(self, strip, r0, r1, s0, height, dist_group=None, out=None):
+    def segment_rows_sharded_device(self, strip, r0, r1, s0, height, dist_group=None, out=None, codebook=None):
         """Row-sharded images with one global codebook (BASELINE config 5).
 
         ``strip``: (B, s1-s0, W, 3) uint8 device tensor = global rows [s0, s1) of B images of
@@ -1860,6 +2027,8 @@ class Segmenter:
         """
         torch = _torch()
         self._check_strips()
+        if codebook is not None:
+            raise ValueError("a codebook is not supported on row strips (the strips' init is the exchange of SPEC.md §4's pixels)")
         strip = strip.contiguous()
         b, hs, w, _ = strip.shape
         if hs < 8 or w < 8:
@@ -1903,7 +2072,7 @@ class Segmenter:
             return out
         return res.contiguous()
 
-    def segment_owned_rows_device(self, owned, height, dist_group=None):
+    def segment_owned_rows_device(self, owned, height, dist_group=None, codebook=None):
         """Row-sharded images where every rank holds ONLY its own rows on its device (BASELINE config 5, option (ii) of
         SURVEY §8e): the halo rows the Gabor stage needs are fetched from the neighbouring ranks device to device
         (``torch.distributed`` point-to-point: RCCL send / recv over xGMI on a multi-GPU node; gloo in the tests), then
@@ -1914,6 +2083,8 @@ class Segmenter:
         (``halo_rows(n_levels, ksize)`` rows), so that a halo comes from ONE neighbour. Returns the (B, r1-r0, W) int32 labels."""
         torch = _torch()
         self._check_strips()
+        if codebook is not None:
+            raise ValueError("a codebook is not supported on row strips (the strips' init is the exchange of SPEC.md §4's pixels)")
         import torch.distributed as td
         if not (td.is_available() and td.is_initialized()):
             raise RuntimeError("segment_owned_rows_device needs torch.distributed (one rank per row strip)")
@@ -2157,14 +2328,15 @@ class Segmenter:
         return out
 
     # ---- host API: the slot
-    def segment_batch(self, imgs: np.ndarray, mode="per_image", out_dtype=np.int32) -> np.ndarray:
+    def segment_batch(self, imgs: np.ndarray, mode="per_image", out_dtype=np.int32, codebook=None, refine=0) -> np.ndarray:
         """(B,H,W,3) uint8 host array -> fresh (B,H,W) host label array (the calling convention of script.py:25,30).
 
         ``out_dtype``: np.int32 (default, SPEC.md §1) or np.uint8 (a quarter of the bytes; metrics.py:43 casts the map
         with ``.astype('int')`` anyway; not with ``connectivity=True`` or ``min_region_size > 0``, whose region ids exceed 255).
         The image upload goes through a cached pinned staging buffer, cut into chunks so that the copy of chunk n+1
         (its own stream) overlaps the Gabor stage of chunk n; the labels are copied straight into a fresh pinned
-        buffer that the returned array owns."""
+        buffer that the returned array owns. ``codebook``, ``refine``: a ``KMeansModel`` in place of the stage's own centroids
+        (``predict_device``), on the plain path: upload, step, download."""
         torch = _torch()
         if isinstance(imgs, (list, tuple)):                        # B equally shaped (H,W,3) images: staged one by one
             imgs = _ImageList(imgs)
@@ -2172,6 +2344,9 @@ class Segmenter:
             imgs = np.ascontiguousarray(imgs)
         out_dtype = self._check_args(imgs, mode, out_dtype)
         b, h, w, _ = imgs.shape
+        if codebook is not None:                                   # (SPEC.md §28: the plain path)
+            dev = torch.from_numpy(np.asarray(imgs)).to(self.ops.device)
+            return self.segment_device(dev, mode, codebook=codebook, refine=refine).cpu().numpy().astype(out_dtype, copy=False)
         path = self._host_path(b, h, w, mode)
         if path == "plain":                                        # (test stand-ins, post-passes, collectives, large §13 calls)
             dev = torch.from_numpy(np.asarray(imgs)).to(self.ops.device)
@@ -2214,7 +2389,7 @@ class Segmenter:
             cur.synchronize()
         return res.numpy()
 
-    def segment_stream(self, batches, mode="per_image", out_dtype=np.int32, depth=2):
+    def segment_stream(self, batches, mode="per_image", out_dtype=np.int32, depth=2, codebook=None, refine=0):
         """Pipelined host API: a generator over the label arrays of an iterable of equally shaped (B,H,W,3) uint8 host
         batches, in order - ``for labels in seg.segment_stream(loader): ...`` instead of calling ``segment_batch`` per batch
         (the loop of script.py:22-38 over a data set). Results equal ``segment_batch(batch, mode, out_dtype)``.
@@ -2222,8 +2397,13 @@ class Segmenter:
         Three streams work on ``depth + 1`` buffer slots: while batch n runs through the Gabor stage and the Lloyd passes,
         batch n+1 is copied into pinned memory and uploaded and the labels of batch n-1 are downloaded into a fresh pinned
         array that the caller owns, both by the copy engines (gcs_download: see there). A result is handed out ``depth``
-        batches after its input was taken (sooner when the input ends)."""
+        batches after its input was taken (sooner when the input ends). With a ``codebook`` every batch takes
+        ``segment_batch``'s plain path."""
         out_dtype = self._check_args(None, mode, out_dtype)
+        if codebook is not None:
+            for imgs in batches:
+                yield self.segment_batch(imgs, mode, out_dtype, codebook=codebook, refine=refine)
+            return
         if not self._may_pipeline(mode):
             for imgs in batches:                                   # no pipeline for post-passes / collectives / stand-ins / §13
                 yield self.segment_batch(imgs, mode, out_dtype)
@@ -2322,13 +2502,15 @@ class Segmenter:
             self._host[key] = st
         return st
 
-    def __call__(self, img: np.ndarray) -> np.ndarray:
+    def __call__(self, img: np.ndarray, codebook=None, refine=0) -> np.ndarray:
         img = np.asarray(img)
         if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
             raise ValueError("img must be an (H,W,3) uint8 array (skimage.io.imread of an RGB file)")
+        if codebook is not None:
+            return self.segment_batch(img[None], codebook=codebook, refine=refine)[0]
         return self.segment_batch(img[None])[0]
 
-    def segment_images(self, images, batch=64, out_dtype=np.int32):
+    def segment_images(self, images, batch=64, out_dtype=np.int32, codebook=None, refine=0):
         """The loop of script.py:22-38 as a generator: ``for labels in seg.segment_images(loader): ...`` yields, in input
         order, exactly what ``segment(img)`` returns for every (H,W,3) uint8 image of an iterable - any mix of shapes (BSD500
         holds 481x321 and 321x481 images). Images wait in per-shape groups of up to ``batch`` and go through the device
@@ -2337,14 +2519,18 @@ class Segmenter:
         downloading), the partial group of every shape, and at most ``2 * batch`` finished label maps that wait for an
         EARLIER image of another shape - when that many have piled up, the group (or the pipeline) that holds the oldest
         outstanding image is flushed early as a partial batch, so a rare shape at the start of a long or endless loader
-        neither stalls the output nor grows the pinned result memory without bound."""
+        neither stalls the output nor grows the pinned result memory without bound. ``codebook``: a one-codebook ``KMeansModel``
+        for every image (``predict_device``; every group then takes ``segment_batch``'s plain path)."""
         batch = int(batch)
         if batch < 1:
             raise ValueError("batch must be >= 1")
         out_dtype = self._check_args(None, "per_image", out_dtype)
+        if codebook is not None and getattr(codebook, "n_sets", 1) != 1:
+            raise ValueError("segment_images groups the images itself: it takes a model of one codebook")
+        with_model = {} if codebook is None else dict(codebook=codebook, refine=refine)
         groups, ready, nxt = {}, {}, 0
         pipes, tags = {}, {}                   # per shape: the pipeline of its FULL batches and the image indices in flight
-        piped = self._may_pipeline("per_image")
+        piped = self._may_pipeline("per_image") and codebook is None
 
         def emit(idx, labels):
             for i, lab in zip(idx, labels):
@@ -2363,7 +2549,7 @@ class Segmenter:
                 for labels in pipes[shape].push(_ImageList(imgs)):
                     emit(tags[shape].pop(0), labels)
             else:
-                emit(idx, self.segment_batch(list(imgs), "per_image", out_dtype))
+                emit(idx, self.segment_batch(list(imgs), "per_image", out_dtype, **with_model))
 
         try:
             for n, img in enumerate(images):
@@ -2573,10 +2759,37 @@ def _plan(kw) -> Segmenter:
     return _default[key]
 
 
+def _with_model(kw):
+    """``codebook`` and ``refine`` taken out of a one-shot call's keywords (plans are cached by what is left) -> the keywords of the
+    host paths: none without a codebook."""
+    codebook, refine = kw.pop("codebook", None), kw.pop("refine", 0)
+    return {} if codebook is None else dict(codebook=codebook, refine=refine)
+
+
 def segment(img, **kw) -> np.ndarray:
-    """Drop-in for ``slic(img, ...)`` at script.py:30: (H,W,3) uint8 -> (H,W) int32 labels 0..k-1."""
+    """Drop-in for ``slic(img, ...)`` at script.py:30: (H,W,3) uint8 -> (H,W) int32 labels 0..k-1. ``codebook=model, refine=m``:
+    under a ``KMeansModel`` of ``fit_codebook`` (``Segmenter.predict_device``) instead of the image's own centroids."""
+    model = _with_model(kw)
     _need_cut(kw)
-    return _plan(kw)(img)
+    return _plan(kw)(img, **model)
+
+
+def fit_codebook(imgs, mode="global", **kw) -> KMeansModel:
+    """(B,H,W,3) uint8 host array (or B equally shaped images) -> the ``KMeansModel`` of ``Segmenter.fit_device`` on them, on
+    the host: one codebook for the batch in mode "global". ``kw``: the plan's options, cached like ``segment``'s."""
+    seg = _plan(kw)
+    dev = _torch().from_numpy(np.ascontiguousarray(np.asarray(imgs)))
+    return seg.fit_device(dev.to(seg.ops.device) if seg.native else dev, mode).cpu()
+
+
+def segment_confidence(img, codebook=None, **kw):
+    """(H,W,3) uint8 -> ((H,W) int32 labels, (H,W) float32 confidence in [0, 1]) of SPEC.md §28
+    (``Segmenter.confidence_device``): how much nearer a pixel is to its centroid than to the next one. ``codebook``: a
+    ``KMeansModel``; without one, the image's own centroids. ``kw``: the plan's options, cached like ``segment``'s."""
+    img = _one_image(img)
+    seg = _plan(kw)
+    labels, conf = seg.confidence_device(_batch_of_one(seg, img), codebook)
+    return labels[0].cpu().numpy(), conf[0].cpu().numpy()
 
 
 def segment_contours(img, **kw) -> np.ndarray:
@@ -2628,15 +2841,17 @@ def segment_images(images, batch=64, **kw):
     """Generator form of the loop at script.py:22-38: yields ``segment(img)`` for every image of an iterable, in order, with
     the images batched per shape behind the scenes (``Segmenter.segment_images``)."""
     out_dtype = kw.pop("out_dtype", np.int32)
+    model = _with_model(kw)
     _need_cut(kw)
-    return _plan(kw).segment_images(images, batch=batch, out_dtype=out_dtype)
+    return _plan(kw).segment_images(images, batch=batch, out_dtype=out_dtype, **model)
 
 
 def segment_batch(imgs, mode="per_image", **kw) -> np.ndarray:
     """(B,H,W,3) uint8 -> (B,H,W) int32; equals stack([segment(i) for i in imgs]) in per_image mode."""
     out_dtype = kw.pop("out_dtype", np.int32)
+    model = _with_model(kw)
     _need_cut(kw)
-    return _plan(kw).segment_batch(imgs, mode, out_dtype=out_dtype)
+    return _plan(kw).segment_batch(imgs, mode, out_dtype=out_dtype, **model)
 
 
 def _one_image(img):
