@@ -38,7 +38,7 @@ from slab_layout import flag_bytes, tile_geometry
 KEEP_BYTES = 256 << 20             # csrc/lloyd_pass.h: KP_MALL_KEEP_DEFAULT
 N_DRAWN = 100000
 
-# id (starts with the name gcs_selftest_pass_kernel gives; banks as in PASS_CASES of tests/test_gpu_value_range.py),
+# id (starts with the name gcs_selftest_pass_kernel gives; banks as in PASS_CASES of tests/pass_cases.py),
 # (n_scales, n_orient, ksize, shift, k), (B, H, W), G = workgroups of the launch with ONE global codebook - split<..>: parts * B
 # (lloyd_mfma_launch: grid (parts, B), all working); native<NL,MINB,N0>: parts_eff * B (launch_native: 256 * MINB / B working
 # workgroups per image) -, what the case runs: "pass" one pass through gcs_kmeans_assign_accumulate, "per_image" that and a pass with

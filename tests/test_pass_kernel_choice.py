@@ -70,8 +70,8 @@ def test_refused_shapes_banks_and_k_give_null(lib):
 
 
 def test_value_range_case_ids_name_the_kernel_their_bank_takes(lib):
-    """The ids of PASS_CASES (tests/test_gpu_value_range.py) are claims: each starts with the hook's answer for its bank and k."""
-    from test_gpu_value_range import PASS_CASES
+    """The ids of PASS_CASES (tests/pass_cases.py) are claims: each starts with the hook's answer for its bank and k."""
+    from pass_cases import PASS_CASES
     assert len(PASS_CASES) >= 28
     for (ns, no, _ks, _shift, k), case_id in PASS_CASES:
         name = _name(lib, 41, 74, ns, no, k)
@@ -164,7 +164,7 @@ def test_nt_limit_equals_the_restated_one(lib):
     """Every bank of PASS_CASES and the default 4x6 and 8x8 banks, n_sets 1 and B, B and shapes as listed; both arms and every
     family occur."""
     from slab_layout import tile_geometry
-    from test_gpu_value_range import PASS_CASES
+    from pass_cases import PASS_CASES
     banks = sorted({(ns, no, k) for (ns, no, _ks, _shift, k), _ in PASS_CASES} | {(4, 6, 8), (8, 8, 8)})
     seen = {}
     for ns, no, k in banks:
