@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """One codebook for a stream of images: cluster ids that mean the same thing from call to call (SPEC.md §28).
 
-    python examples/codebook_stream.py [--fit 8] [--k 8] [--refine 0] [--save model.npz]
+    python examples/codebook_stream.py [--fit 8] [--k 8] [--refine 0] [--init spec|kmeans++] [--n-init 1] [--seed 0] [--save model.npz]
 
 Fits ONE k-means codebook on the first ``--fit`` portrait val fixture images (tests/golden/bsd_val_images.npz, colour bank), then
 labels the remaining ones with it, one call per image as a camera loop would: the Gabor stage and a single assign pass instead of
 the ten passes of a per-image codebook. Prints the model's per-cluster counts and its mean squared error, and per image the share
 of every cluster under the shared codebook, the error of the shared codebook on that image against the error of the image's own
 codebook, and the mean confidence of its pixels. ``--save`` keeps the model as an ``.npz`` that ``KMeansModel.load`` reads back.
+``--init kmeans++`` seeds every Lloyd loop by k-means++ (SPEC.md §29) instead of evenly spaced raster pixels, and ``--n-init n``
+then fits the codebook n times from the seeds ``--seed``, ``--seed + 1``, ... and keeps the fit with the least inertia.
 Needs a GPU."""
 import argparse
 import os
@@ -25,15 +27,18 @@ def main():
     ap.add_argument("--fit", type=int, default=8, help="images the codebook is fitted on")
     ap.add_argument("--k", type=int, default=8)
     ap.add_argument("--refine", type=int, default=0, help="update passes per image from the shared codebook (0: frozen)")
+    ap.add_argument("--init", default="spec", choices=["spec", "kmeans++"], help="how every Lloyd loop starts (SPEC.md §4 / §29)")
+    ap.add_argument("--n-init", type=int, default=1, help="restarts of the fit (with --init kmeans++): the least inertia is kept")
+    ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--save", default=None)
     args = ap.parse_args()
     import torch
     from gabor_color_image_segmentation_amd import KMeansModel, Segmenter
     val = np.load(os.path.join(ROOT, "tests", "golden", "bsd_val_images.npz"))
     ids = [str(i) for i in val["ids"] if val["img_" + str(i)].shape[:2] == (481, 321)]
-    seg = Segmenter(k=args.k, **BANK)
+    seg = Segmenter(k=args.k, init=args.init, seed=args.seed, **BANK)
     dev = lambda names: torch.from_numpy(np.stack([val["img_" + i] for i in names])).to(seg.ops.device)
-    model = seg.fit_device(dev(ids[:args.fit]), "global")
+    model = seg.fit_device(dev(ids[:args.fit]), "global", n_init=args.n_init)
     if args.save:
         model.save(args.save)
         model = KMeansModel.load(args.save)

@@ -129,6 +129,11 @@ MODEL_EXTENSIONS = {
     "gcs_kmeans_evaluate": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes): every symbol include/gcs_seed.h declares (SPEC.md §29), optional in the same way.
+SEED_EXTENSIONS = {
+    "gcs_kmeans_seed": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_uint64, _vp, _vp, _vp, _vp]),
+}
+
 
 class GcsError(RuntimeError):
     pass
@@ -158,7 +163,7 @@ def load():
         fn = getattr(lib, name)      # AttributeError here = header/library mismatch
         fn.restype, fn.argtypes = res, args
     for name, (res, args) in list(EXTENSIONS.items()) + list(THIN_EXTENSIONS.items()) + list(MATCH_EXTENSIONS.items()) \
-            + list(MODEL_EXTENSIONS.items()):
+            + list(MODEL_EXTENSIONS.items()) + list(SEED_EXTENSIONS.items()):
         fn = getattr(lib, name, None)    # optional: an older library of the same ABI lacks it
         if fn is not None:
             fn.restype, fn.argtypes = res, args

@@ -647,6 +647,27 @@ class HipOps:
                                                 ptr(labels), ptr(best), ptr(second), ptr(stats), self._stream()),
                    "gcs_kmeans_evaluate")
 
+    @_on_device
+    def kmeans_seed(self, feats, b, h, w, k, n_sets, cent, stride, trials=4, seed=0, picks=None, potential=None):
+        """SPEC.md §29: k k-means++ seeds per codebook set, drawn among the candidates of the slab ``feats`` at ``stride`` (a power
+        of two; at most 4096 candidates per set), into ``cent``, a contiguous (n_sets, k, D) int16 tensor (the uint16 values
+        ``kmeans_init`` would write), ``n_sets`` 1 or B. Optional: ``picks`` (n_sets, k) int32, the candidate indices, and
+        ``potential`` (n_sets,) int64, the candidates' summed squared distance to their nearest seed. One launch, no workspace
+        (capturable as it is)."""
+        if not hasattr(self.lib, "gcs_kmeans_seed"):
+            raise _lib.GcsError("k-means++ seeding needs a library that has it (this libgcs.so does not export gcs_kmeans_seed)")
+        torch = self.torch
+        if cent is None:
+            raise ValueError("kmeans_seed needs the centroid tensor")
+        self._need(cent, (torch.int16, torch.uint16), (int(n_sets), int(k), self.bank.n_features),
+                   "cent must be a contiguous (n_sets, k, D) int16 tensor")
+        self._need(picks, torch.int32, (int(n_sets), int(k)), "picks must be a contiguous (n_sets, k) int32 tensor")
+        self._need(potential, torch.int64, (int(n_sets),), "potential must be a contiguous (n_sets,) int64 tensor")
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(self.lib.gcs_kmeans_seed(feats.data_ptr(), b, h, w, *self._bk, int(k), int(n_sets), int(stride), int(trials),
+                                            int(seed) & _U64, cent.data_ptr(), ptr(picks), ptr(potential), self._stream()),
+                   "gcs_kmeans_seed")
+
     def texton_masks(self, r, n):
         """SPEC.md §24: the half-disc table of radius ``r`` and ``n`` directions, a (n, 2, 2r+1) int32 device tensor holding the
         uint32 rows of gcs_texton_masks; made on the host once per (r, n) and kept (a captured step must find it made)."""
@@ -974,6 +995,42 @@ def _check_tree_nodes(tree_nodes, n_superpixels):
     return tree_nodes == "components"
 
 
+_U64 = (1 << 64) - 1
+SEED_CANDIDATES_MAX = 4096
+
+
+def seed_stride(b_set, height, width):
+    """SPEC.md §29, the host's stride rule: the smallest power of two >= 8 at which a codebook set of ``b_set`` images of
+    (height, width) pixels has at most 4096 candidates - 8 for one 481x321 image (61 x 41 = 2501 candidates), 64 for a global
+    codebook over 64 of them (3072)."""
+    s = 8
+    while s <= 4096:
+        if b_set * -(-height // s) * -(-width // s) <= SEED_CANDIDATES_MAX:
+            return s
+        s *= 2
+    raise ValueError(f"k-means++ seeding takes at most {SEED_CANDIDATES_MAX} images in one codebook set, got {b_set}")
+
+
+def _check_seeding(init, seed, seed_trials):
+    """The plan's seeding options -> None for the init of SPEC.md §4, (seed, trials) for SPEC.md §29."""
+    if init not in ("spec", "kmeans++"):
+        raise ValueError(f'init must be "spec" or "kmeans++", got {init!r}')
+    s, t = _as_int(seed), _as_int(seed_trials)
+    if s is None or not 0 <= s <= _U64:
+        raise ValueError(f"seed must be an integer in 0..2^64-1, got {seed!r}")
+    if t is None or not 1 <= t <= 8:
+        raise ValueError(f"seed_trials must be an integer in 1..8, got {seed_trials!r}")
+    return (s, t) if init == "kmeans++" else None
+
+
+def _seed_init(ops, feats, b, h, w, k, n_sets, seed, trials, stride=None):
+    """``lloyd``'s ``init`` for SPEC.md §29: one seed launch into the step's centroids, on the step's stream, at the stride of the
+    slab it sees (``seed_stride``) unless one is given."""
+    def init(cent):
+        ops.kmeans_seed(feats, b, h, w, k, n_sets, cent, stride or seed_stride(b if n_sets == 1 else 1, h, w), trials, seed)
+    return init
+
+
 def lloyd(ops, feats, b, h, w, k, n_iter, mode, labels, partials, cent, sums, dist_group=None,
           rows=None, init=None, raster=None, debug=_ENV_DEBUG, fold=None):
     """SPEC.md §4 schedule on one feature slab. ``mode``: 'per_image' or 'global'.
@@ -1037,9 +1094,10 @@ def lloyd(ops, feats, b, h, w, k, n_iter, mode, labels, partials, cent, sums, di
 # stage on). The two pieces of the step take it, the ops, a workspace and the debug switches as arguments and never the
 # Segmenter: a graph entry holds them, and an entry that held its plan would be a reference cycle (see _segment_small).
 # ``components``: SPEC.md §18 is on (then ``min_size`` = the plan's min_region_size, the m of the node map); ``clusters``: SPEC.md §21
-# is on (the same m). ``boundary``: the tree is SPEC.md §23's (merge_cost = "boundary").
+# is on (the same m). ``boundary``: the tree is SPEC.md §23's (merge_cost = "boundary"). ``seed``: None = the init of SPEC.md §4,
+# (seed, trials) = the Lloyd loop starts from the seeds of SPEC.md §29.
 _StepOptions = collections.namedtuple("_StepOptions", "k n_iter colour smooth position n_superpixels spatial_weight n_regions "
-                                                      "components min_size clusters boundary", defaults=(False, False))
+                                                      "components min_size clusters boundary seed", defaults=(False, False, None))
 
 
 def _opponent(ops, imgs, colour):
@@ -1155,7 +1213,8 @@ def _step_cluster(ops, opt, ws, out, b, h, w, mode, debug, dist_group=None, rows
     and tree and cut run on that, the tree at K_cap; ``nodes=False`` leaves the §13 map as it is. A uint8 ``out`` is narrowed from
     the int32 map of the workspace (a graph entry). With ``tree_nodes = "clusters"`` (SPEC.md §21) the Lloyd loop writes its int32
     map to the node stage's own buffer, its node map goes to the output, and the tree reads its statistics from the slab
-    (``region_tree_slab``: no canonical tensor), at K_cap; ``tree`` as above."""
+    (``region_tree_slab``: no canonical tensor), at K_cap; ``tree`` as above. ``opt.seed`` (SPEC.md §29): without an ``init`` the
+    Lloyd loop starts from the seed launch on this slab instead of the init of SPEC.md §4."""
     if opt.n_superpixels == 0:
         ndws = raw = n_nodes = None
         if opt.clusters:
@@ -1167,6 +1226,8 @@ def _step_cluster(ops, opt, ws, out, b, h, w, mode, debug, dist_group=None, rows
             out32 = ws["out32"]
         km = raw if opt.clusters else out
         raster = km if rows is None and hasattr(ops, "assign_raster") else None       # the last pass writes the raster map itself
+        if init is None and opt.seed is not None:                                     # SPEC.md §29 (given centroids win)
+            init = _seed_init(ops, ws["feats"], b, h, w, opt.k, b if mode == "per_image" else 1, *opt.seed)
         lloyd(ops, ws["feats"], b, h, w, opt.k, opt.n_iter, mode, ws["labels"], ws["partials"], ws["cent"], ws["sums"],
               dist_group, rows=rows, init=init, raster=raster, debug=debug, fold=ws.get("fold"))
         if raster is None:
@@ -1235,8 +1296,15 @@ class Segmenter:
                  ratio=math.sqrt(2.0), bandwidth=1.0, connectivity=False, device="cuda:0", ops=None,
                  slab_candidates=1, min_region_size=0, smoothing=0.0, color_weight=0.0, chroma_gain=0,
                  position_weight=0, n_superpixels=0, spatial_weight=576, n_regions=0, tree_nodes="superpixels",
-                 merge_cost="features"):
-        """``n_superpixels = n`` (SPEC.md §13; 0 = off, 2..4096): grid-local k-means instead of the Lloyd stage - about n compact
+                 merge_cost="features", init="spec", seed=0, seed_trials=4):
+        """``init = "kmeans++"`` (SPEC.md §29; needs ``n_superpixels = 0``): every Lloyd loop of the plan starts from k seeds drawn
+        by k-means++ with ``seed_trials`` greedy trials (1..8) among a grid of at most 4096 candidate pixels of its codebook set
+        (``seed_stride``), one launch in front of the passes, instead of the k evenly spaced raster pixels of SPEC.md §4
+        (``"spec"``, the default: every path enqueues what it always did). The draws depend on ``seed`` (0..2^64-1) alone, not on
+        the image: a single image's result is its row of the batch's. A ``codebook=`` wins: no seeding runs. Restarts:
+        ``fit_device(n_init=n)``. Not over a ``dist_group``, and not on the row-strip entry points.
+
+        ``n_superpixels = n`` (SPEC.md §13; 0 = off, 2..4096): grid-local k-means instead of the Lloyd stage - about n compact
         superpixels per image (K = ny * nx of ``superpixel_grid``) on the same features; ``k`` and ``mode`` are then unused (centres
         are per image). ``spatial_weight`` = lambda (1..65535, default 576) weighs the squared pixel distance to a centre against
         the squared feature distance: larger = more compact. Recommended pairing: ``min_region_size = S * S // 4`` with S of
@@ -1283,6 +1351,10 @@ class Segmenter:
                                     chroma_gain=int(self.chroma_gain), smoothing=float(self.smoothing),
                                     position_weight=int(self.position_weight), k=self.k)
         self.n_superpixels, self.spatial_weight = _check_superpixels(n_superpixels, spatial_weight)   # SPEC.md §13 (0: §4's Lloyd stage)
+        self._seeding = _check_seeding(init, seed, seed_trials)                  # SPEC.md §29 (None: the init of §4)
+        self.init, self.seed, self.seed_trials = init, int(seed), int(seed_trials)
+        if self._seeding and self.n_superpixels > 0:
+            raise ValueError('init = "kmeans++" seeds the Lloyd stage: it needs n_superpixels = 0')
         if self.n_superpixels > 0 and self.bank.n_features > _SP_D_MAX:
             raise ValueError(f"n_superpixels needs a bank of at most {_SP_D_MAX} features, this one has {self.bank.n_features}")
         self._boundary = _check_merge_cost(merge_cost)                          # SPEC.md §23
@@ -1292,6 +1364,8 @@ class Segmenter:
         self.ops = ops if ops is not None else HipOps(self.bank, device, self.smoothing, self.chroma_gain)
         if self.n_superpixels > 0 and not hasattr(self.ops, "superpixels"):
             raise ValueError("Segmenter(n_superpixels=n, ops=...) needs ops that have the superpixel stage")
+        if self._seeding and not hasattr(self.ops, "kmeans_seed"):
+            raise ValueError('Segmenter(init="kmeans++", ops=...) needs ops that have kmeans_seed')
         self._components = _check_tree_nodes(tree_nodes, self.n_superpixels)    # SPEC.md §18
         self._clusters = tree_nodes == "clusters"                               # SPEC.md §21 (checked: n_superpixels = 0)
         self.tree_nodes = tree_nodes
@@ -1326,7 +1400,7 @@ class Segmenter:
         self.slab_placement_ms = None
         self._opt = _StepOptions(self.k, int(n_iter), self.chroma_gain > 0, self.smoothing > 0, self.position_weight > 0,
                                  self.n_superpixels, self.spatial_weight, self.n_regions, self._components,
-                                 self.min_region_size, self._clusters, self._boundary)
+                                 self.min_region_size, self._clusters, self._boundary, self._seeding)
         self._ws = {}
         self._host = {}
         self._stream = {}
@@ -1397,6 +1471,15 @@ class Segmenter:
             if h < 8 or w < 8:
                 raise ValueError("images must be at least 8x8")
             check_position_range(self.position_weight, h, w)
+        if self._seeding and cluster:
+            if dist_group is not None:
+                raise ValueError('init = "kmeans++" does not run over a dist_group')
+            if mode == "global":
+                import torch.distributed as td
+                if td.is_available() and td.is_initialized() and td.get_world_size() > 1:
+                    raise ValueError('init = "kmeans++" does not run over more than one rank (every rank would draw its own seeds)')
+                if imgs is not None:
+                    seed_stride(imgs.shape[0], h, w)       # (ValueError: more than 4096 images in the one set)
         if self.n_superpixels > 0 and cluster:
             self._superpixel_check(h, w, mode, out_dtype, dist_group)
         if self._clusters and cluster:
@@ -1631,12 +1714,20 @@ class Segmenter:
             model, refine = self._codebook_check(model, imgs.shape[0], mode, refine)
         return imgs.contiguous(), model, refine
 
-    def fit_device(self, imgs, mode="global", init=None):
+    def fit_device(self, imgs, mode="global", init=None, n_init=1):
         """(B,H,W,3) uint8 device tensor -> the ``KMeansModel`` of the plan's own step on it (SPEC.md §28): the centroids the Lloyd
         loop ends on - one codebook in mode "global", B in "per_image" - with the count and the inertia of every cluster under
         them, from one evaluate launch on the slab the step left in its workspace. ``init``: a model to start the loop from in
-        place of the init of SPEC.md §4 (the plan's ``n_iter`` passes either way)."""
+        place of the plan's own start (the plan's ``n_iter`` passes either way). ``n_init = n > 1`` (SPEC.md §29; a plan with
+        ``init = "kmeans++"``, no ``init`` model): n loops on the same slab from the seeds of ``seed``, ``seed + 1``, ...; every set
+        keeps the loop whose inertias sum to the least (ties: the lowest restart), chosen on the device, and
+        ``predict_device(imgs, model)`` delivers that loop's labels."""
         torch = _torch()
+        n_init = _as_int(n_init)
+        if n_init is None or n_init < 1:
+            raise ValueError("n_init must be an integer >= 1")
+        if n_init > 1 and (init is not None or not self._seeding):
+            raise ValueError('n_init > 1 restarts the seeding: it needs a plan with init = "kmeans++" and no init model')
         imgs, init, _ = self._model_args(imgs, mode, init)
         b, h, w, _ = imgs.shape
         n_sets = b if mode == "per_image" else 1
@@ -1646,6 +1737,40 @@ class Segmenter:
             stats = torch.empty((n_sets, self.k, 2), dtype=torch.int64, device=imgs.device)
             for g0, n, ws in self._model_steps(imgs, mode, init, self._opt, labels):
                 ns = n if mode == "per_image" else 1
+                cent[g0:g0 + ns].copy_(ws["cent"])
+                self.ops.kmeans_evaluate(ws["feats"], ws["cent"], n, h, w, self.k, ns, stats=stats[g0:g0 + ns])
+                for i in range(1, n_init):                 # the restarts, on the slab the first loop filled
+                    again = torch.empty((ns, self.k, 2), dtype=torch.int64, device=imgs.device)
+                    opt = self._opt._replace(seed=((self.seed + i) & _U64, self.seed_trials))
+                    _step_cluster(self.ops, opt, ws, labels[g0:g0 + n], n, h, w, mode, self.debug)
+                    self.ops.kmeans_evaluate(ws["feats"], ws["cent"], n, h, w, self.k, ns, stats=again)
+                    better = again[:, :, 1].sum(dim=1) < stats[g0:g0 + ns, :, 1].sum(dim=1)      # strictly: ties keep the earlier
+                    cent[g0:g0 + ns] = torch.where(better[:, None, None], ws["cent"], cent[g0:g0 + ns])
+                    stats[g0:g0 + ns] = torch.where(better[:, None, None], again, stats[g0:g0 + ns])
+        return KMeansModel(cent, stats[..., 0].contiguous(), stats[..., 1].contiguous(), self.model_signature)
+
+    def seed_device(self, imgs, mode="per_image", seed=None, trials=None, stride=None):
+        """(B,H,W,3) uint8 device tensor -> the ``KMeansModel`` of the k-means++ seeds of SPEC.md §29 themselves, before any Lloyd
+        pass: one codebook per image, or one for the batch in mode "global", with the counts and inertias of one evaluate launch.
+        ``seed``, ``trials``: the plan's ``seed`` and ``seed_trials`` unless given; ``stride``: ``seed_stride`` of each group unless
+        given. Works on any plan with ``n_superpixels = 0``, whatever its ``init``."""
+        torch = _torch()
+        seed, trials = _check_seeding("kmeans++", self.seed if seed is None else seed, self.seed_trials if trials is None else trials)
+        if stride is not None and (_as_int(stride) is None or not 1 <= stride <= 4096 or stride & (stride - 1)):
+            raise ValueError(f"stride must be a power of two in 1..4096, got {stride!r}")
+        imgs, _, _ = self._model_args(imgs, mode, None)
+        if not hasattr(self.ops, "kmeans_seed"):
+            raise ValueError("seed_device needs ops that have kmeans_seed")
+        b, h, w, _ = imgs.shape
+        n_sets = b if mode == "per_image" else 1
+        if stride is None:
+            seed_stride(b if mode == "global" else 1, h, w)            # (ValueError before any launch)
+        with self._device():
+            cent = torch.empty((n_sets, self.k, self.bank.n_features), dtype=torch.int16, device=imgs.device)
+            stats = torch.empty((n_sets, self.k, 2), dtype=torch.int64, device=imgs.device)
+            for g0, n, ws in self._model_steps(imgs, mode, None, None, None):
+                ns = n if mode == "per_image" else 1
+                _seed_init(self.ops, ws["feats"], n, h, w, self.k, ns, seed, trials, stride)(ws["cent"])
                 cent[g0:g0 + ns].copy_(ws["cent"])
                 self.ops.kmeans_evaluate(ws["feats"], ws["cent"], n, h, w, self.k, ns, stats=stats[g0:g0 + ns])
         return KMeansModel(cent, stats[..., 0].contiguous(), stats[..., 1].contiguous(), self.model_signature)
@@ -2002,6 +2127,8 @@ class Segmenter:
 
     def _check_strips(self):
         """The options the two row-strip entry points refuse."""
+        if self._seeding:
+            raise ValueError('init = "kmeans++" is not supported on row strips (the candidates would be one strip\'s)')
         if self.n_superpixels > 0:
             raise ValueError("n_superpixels > 0 is not supported on row strips")
         if self._clusters:
@@ -2774,12 +2901,13 @@ def segment(img, **kw) -> np.ndarray:
     return _plan(kw)(img, **model)
 
 
-def fit_codebook(imgs, mode="global", **kw) -> KMeansModel:
+def fit_codebook(imgs, mode="global", n_init=1, **kw) -> KMeansModel:
     """(B,H,W,3) uint8 host array (or B equally shaped images) -> the ``KMeansModel`` of ``Segmenter.fit_device`` on them, on
-    the host: one codebook for the batch in mode "global". ``kw``: the plan's options, cached like ``segment``'s."""
+    the host: one codebook for the batch in mode "global". ``n_init``: restarts (with ``init="kmeans++"``; SPEC.md §29).
+    ``kw``: the plan's options, cached like ``segment``'s."""
     seg = _plan(kw)
     dev = _torch().from_numpy(np.ascontiguousarray(np.asarray(imgs)))
-    return seg.fit_device(dev.to(seg.ops.device) if seg.native else dev, mode).cpu()
+    return seg.fit_device(dev.to(seg.ops.device) if seg.native else dev, mode, n_init=n_init).cpu()
 
 
 def segment_confidence(img, codebook=None, **kw):
