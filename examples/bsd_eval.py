@@ -67,12 +67,23 @@ host, minutes for the 24 images) at N of the 256 thresholds (32 when N is left o
 `--match-device` beside them: two more columns, the ODS / OIS of the same score at ALL 256 thresholds from the device matcher (SPEC.md
 §27: `evaluate_gpu.edge_match_resident`, seconds); with `--match N` as well, a line per map says whether the two paths give the same
 floats at the N thresholds.
+`--regularize LAMBDA [--regularize-sweeps N --regularize-neighbours 4|8]` beside the label tables (`--min-region-size`, `--smoothing`,
+the colour and position options) and beside `--regions ... --tree-nodes clusters`: the same rows through
+Segmenter(regularize=LAMBDA, ...) (SPEC.md §30: ICM sweeps of a Potts prior on the k-means map, in front of every later stage).
 """
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def _regularize_kw():
+    """The plan options of SPEC.md §30 from the command line: none without `--regularize`."""
+    arg = lambda name, kind: {name.strip("-").replace("-", "_"): kind(sys.argv[sys.argv.index(name) + 1])} if name in sys.argv else {}
+    if "--regularize" not in sys.argv:
+        return {}
+    return dict(**arg("--regularize", float), **arg("--regularize-sweeps", int), **arg("--regularize-neighbours", int))
 
 from gabor_color_image_segmentation_amd import segment                      # noqa: E402  (script.py:11)
 from gabor_color_image_segmentation_amd.evaluate import metrics             # noqa: E402  (script.py:14)
@@ -139,7 +150,8 @@ def merge_table(sizes, smoothings=(0.0,), weights=(0.0,), gains=(0,), n_orient=N
     print(("| n_orient | w | g " if colour else "") + ("| mu " if position else "") + "| K | m | R | P | F | PRI | VoI | covering | regions / image |")
     print(("|---|---|---" if colour else "") + ("|---" if position else "") + "|---|---|---|---|---|---|---|---|---|")
     for cw, g, mu, K, m in [(cw, g, mu, K, m) for cw in weights for g in gains for mu in positions for K in smoothings for m in sizes]:
-        seg = Segmenter(n_orient=n_orient, min_region_size=m, smoothing=K, color_weight=cw, chroma_gain=g, position_weight=mu)
+        seg = Segmenter(n_orient=n_orient, min_region_size=m, smoothing=K, color_weight=cw, chroma_gain=g, position_weight=mu,
+                        **_regularize_kw())
         rows = []
         for group in groups:
             labels = seg.segment_device(torch.from_numpy(np.stack([pack["img_" + i] for i in group])).cuda())
@@ -180,7 +192,7 @@ def region_plan(n, lam, n_orient, cw, g, tree_nodes, k, m=0):
     cost = sys.argv[sys.argv.index("--merge-cost") + 1] if "--merge-cost" in sys.argv else "features"    # SPEC.md §23
     if tree_nodes == "clusters":
         return Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, k=k, tree_nodes=tree_nodes, min_region_size=m,
-                         merge_cost=cost)
+                         merge_cost=cost, **_regularize_kw())
     return Segmenter(n_orient=n_orient, color_weight=cw, chroma_gain=g, n_superpixels=n, spatial_weight=lam, tree_nodes=tree_nodes,
                      min_region_size=m, merge_cost=cost)
 
@@ -447,7 +459,8 @@ if __name__ == '__main__':
         superpixel_row(one("--superpixels", int, 300), one("--spatial-weight", int, 576), one("--n-orient", int, 6),
                        one("--color-weight", float, 0.0), one("--chroma-gain", int, 0), one("--min-region-size", str, "0"))
         sys.exit(0)
-    if any(o in sys.argv for o in ("--min-region-size", "--smoothing", "--color-weight", "--chroma-gain", "--n-orient", "--position-weight")):
+    if any(o in sys.argv for o in ("--min-region-size", "--smoothing", "--color-weight", "--chroma-gain", "--n-orient", "--position-weight",
+                                   "--regularize")):
         def arg(name, conv, default):
             return [conv(v) for v in sys.argv[sys.argv.index(name) + 1].split(",")] if name in sys.argv else default
         merge_table(arg("--min-region-size", int, [0]), arg("--smoothing", float, [0.0]), arg("--color-weight", float, [0.0]),

@@ -134,6 +134,12 @@ SEED_EXTENSIONS = {
     "gcs_kmeans_seed": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_uint64, _vp, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes): every symbol include/gcs_relax.h declares (SPEC.md §30), optional in the same way.
+RELAX_EXTENSIONS = {
+    "gcs_kmeans_costs": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "gcs_label_relax": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
 
 class GcsError(RuntimeError):
     pass
@@ -163,7 +169,7 @@ def load():
         fn = getattr(lib, name)      # AttributeError here = header/library mismatch
         fn.restype, fn.argtypes = res, args
     for name, (res, args) in list(EXTENSIONS.items()) + list(THIN_EXTENSIONS.items()) + list(MATCH_EXTENSIONS.items()) \
-            + list(MODEL_EXTENSIONS.items()) + list(SEED_EXTENSIONS.items()):
+            + list(MODEL_EXTENSIONS.items()) + list(SEED_EXTENSIONS.items()) + list(RELAX_EXTENSIONS.items()):
         fn = getattr(lib, name, None)    # optional: an older library of the same ABI lacks it
         if fn is not None:
             fn.restype, fn.argtypes = res, args

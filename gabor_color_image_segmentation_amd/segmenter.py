@@ -668,6 +668,48 @@ class HipOps:
                                             int(seed) & _U64, cent.data_ptr(), ptr(picks), ptr(potential), self._stream()),
                    "gcs_kmeans_seed")
 
+    @_on_device
+    def kmeans_costs(self, feats, cent, b, h, w, k, n_sets, costs):
+        """SPEC.md §30: the cost volume of the slab ``feats`` under the codebooks ``cent`` (as ``kmeans_evaluate`` takes them) into
+        ``costs``, a contiguous (B, k, H, W) int64 tensor: the distances d_j(p) of SPEC.md §28. One launch, no workspace."""
+        if not hasattr(self.lib, "gcs_kmeans_costs"):
+            raise _lib.GcsError("the cost volume needs a library that has it (this libgcs.so does not export gcs_kmeans_costs)")
+        torch = self.torch
+        if cent is None or costs is None:
+            raise ValueError("kmeans_costs needs the centroids and the cost tensor")
+        self._need(cent, (torch.int16, torch.uint16), (int(n_sets), int(k), self.bank.n_features),
+                   "cent must be a contiguous (n_sets, k, D) int16 tensor")
+        self._need(costs, torch.int64, (b, int(k), h, w), "costs must be a contiguous (B, k, H, W) int64 tensor")
+        self._check_dev(cent, costs)
+        _lib.check(self.lib.gcs_kmeans_costs(feats.data_ptr(), cent.data_ptr(), b, h, w, *self._bk, int(k), int(n_sets),
+                                             costs.data_ptr(), self._stream()), "gcs_kmeans_costs")
+
+    @_on_device
+    def label_relax(self, costs, beta, b, h, w, k, neighbours, sweeps, labels_in, labels_out, workspace=None, changed=None,
+                    energy=None):
+        """SPEC.md §30: ``sweeps`` ICM sweeps of the Potts energy of the (B, k, H, W) int64 volume ``costs`` at the weights ``beta``
+        ((B,) int64), from the (B,H,W) int32 map ``labels_in`` into ``labels_out`` (another tensor). ``workspace``: at least
+        B*H*W*4 bytes, needed for ``sweeps >= 2``. Optional: ``changed`` (B, sweeps) int32, the labels every sweep changed, and
+        ``energy`` (B, 2) int64 = (unary, pairs) of the delivered map; both are zeroed by the call itself (capturable as it is)."""
+        if not hasattr(self.lib, "gcs_label_relax"):
+            raise _lib.GcsError("the label relaxation needs a library that has it (this libgcs.so does not export gcs_label_relax)")
+        torch = self.torch
+        if costs is None or beta is None or labels_in is None or labels_out is None:
+            raise ValueError("label_relax needs costs, beta, labels_in and labels_out")
+        self._need(costs, torch.int64, (b, int(k), h, w), "costs must be a contiguous (B, k, H, W) int64 tensor")
+        self._need(beta, torch.int64, (b,), "beta must be a contiguous (B,) int64 tensor")
+        self._need(labels_in, torch.int32, (b, h, w), "labels_in must be a contiguous (B,H,W) int32 tensor")
+        self._need(labels_out, torch.int32, (b, h, w), "labels_out must be a contiguous (B,H,W) int32 tensor")
+        self._need(changed, torch.int32, (b, int(sweeps)), "changed must be a contiguous (B, sweeps) int32 tensor")
+        self._need(energy, torch.int64, (b, 2), "energy must be a contiguous (B, 2) int64 tensor")
+        if workspace is not None and (workspace.numel() * workspace.element_size() < b * h * w * 4 or not workspace.is_contiguous()):
+            raise ValueError("workspace must hold at least B*H*W*4 bytes")
+        self._check_dev(*(t for t in (costs, beta, labels_in, labels_out, workspace, changed, energy) if t is not None))
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(self.lib.gcs_label_relax(costs.data_ptr(), beta.data_ptr(), b, h, w, int(k), int(neighbours), int(sweeps),
+                                            labels_in.data_ptr(), labels_out.data_ptr(), ptr(workspace), ptr(changed), ptr(energy),
+                                            self._stream()), "gcs_label_relax")
+
     def texton_masks(self, r, n):
         """SPEC.md §24: the half-disc table of radius ``r`` and ``n`` directions, a (n, 2, 2r+1) int32 device tensor holding the
         uint32 rows of gcs_texton_masks; made on the host once per (r, n) and kept (a captured step must find it made)."""
@@ -1023,6 +1065,49 @@ def _check_seeding(init, seed, seed_trials):
     return (s, t) if init == "kmeans++" else None
 
 
+def _check_regularize(regularize, sweeps, neighbours):
+    """The plan's options of SPEC.md §30 -> None when ``regularize`` is 0, else (q, sweeps, neighbours), q = round(256 lambda)."""
+    try:
+        lam = float(regularize)
+    except (TypeError, ValueError):
+        lam = float("nan")
+    if isinstance(regularize, (bool, str, bytes)) or not math.isfinite(lam) or lam < 0:
+        raise ValueError(f"regularize must be a finite number >= 0, got {regularize!r}")
+    s, n = _as_int(sweeps), _as_int(neighbours)
+    if s is None or not 1 <= s <= 64:
+        raise ValueError(f"regularize_sweeps must be an integer in 1..64, got {sweeps!r}")
+    if n not in (4, 8):
+        raise ValueError(f"regularize_neighbours must be 4 or 8, got {neighbours!r}")
+    if lam == 0:
+        return None
+    q = int(math.floor(256.0 * lam + 0.5))
+    if not 1 <= q <= 65535:
+        raise ValueError(f"regularize: round(256 * lambda) must be in 1..65535, got lambda = {regularize!r}")
+    return q, s, n
+
+
+def relax_beta(stats, q):
+    """SPEC.md §30, the weight of a codebook set from the table of SPEC.md §28: ``stats`` (n_sets, k, 2) int64 = (count, inertia)
+    -> (n_sets,) int64: beta = (q * m) >> 8 with m = floor(sum_j inertia_j / sum_j count_j). Integer torch operations on the
+    tensor's device: no kernel of the library's, no host read."""
+    m = stats[:, :, 1].sum(dim=1) // stats[:, :, 0].sum(dim=1)
+    return (m * int(q)) >> 8
+
+
+def _step_relax(ops, opt, ws, km, b, h, w, mode):
+    """SPEC.md §30 behind the Lloyd loop, on the slab and the centroids it ended on: the stats table of SPEC.md §28 (for beta
+    alone), the cost volume, and ``opt.relax``'s sweeps from a copy of the int32 map ``km`` back into ``km``."""
+    q, sweeps, neighbours = opt.relax
+    n_sets = b if mode == "per_image" else 1
+    rx = _stage_buffers(ops, opt, ws, "rx", b, h, w, n_sets=n_sets, like=km)
+    ops.kmeans_evaluate(ws["feats"], ws["cent"], b, h, w, opt.k, n_sets, stats=rx["stats"])
+    beta = relax_beta(rx["stats"], q)
+    rx["beta"].copy_(beta if n_sets == b else beta.expand(b))             # (global mode: every image gets the set's beta)
+    ops.kmeans_costs(ws["feats"], ws["cent"], b, h, w, opt.k, n_sets, rx["costs"])
+    rx["start"].copy_(km)
+    ops.label_relax(rx["costs"], rx["beta"], b, h, w, opt.k, neighbours, sweeps, rx["start"], km, workspace=rx["work"])
+
+
 def _seed_init(ops, feats, b, h, w, k, n_sets, seed, trials, stride=None):
     """``lloyd``'s ``init`` for SPEC.md §29: one seed launch into the step's centroids, on the step's stream, at the stride of the
     slab it sees (``seed_stride``) unless one is given."""
@@ -1095,9 +1180,11 @@ def lloyd(ops, feats, b, h, w, k, n_iter, mode, labels, partials, cent, sums, di
 # Segmenter: a graph entry holds them, and an entry that held its plan would be a reference cycle (see _segment_small).
 # ``components``: SPEC.md §18 is on (then ``min_size`` = the plan's min_region_size, the m of the node map); ``clusters``: SPEC.md §21
 # is on (the same m). ``boundary``: the tree is SPEC.md §23's (merge_cost = "boundary"). ``seed``: None = the init of SPEC.md §4,
-# (seed, trials) = the Lloyd loop starts from the seeds of SPEC.md §29.
+# (seed, trials) = the Lloyd loop starts from the seeds of SPEC.md §29. ``relax``: None = the map as the Lloyd loop leaves it,
+# (q, sweeps, neighbours) = the regulariser of SPEC.md §30 behind it, q = round(256 lambda).
 _StepOptions = collections.namedtuple("_StepOptions", "k n_iter colour smooth position n_superpixels spatial_weight n_regions "
-                                                      "components min_size clusters boundary seed", defaults=(False, False, None))
+                                                      "components min_size clusters boundary seed relax",
+                                      defaults=(False, False, None, None))
 
 
 def _opponent(ops, imgs, colour):
@@ -1134,14 +1221,22 @@ def _step_features(ops, opt, ws, imgs, b, h, w, y0=0, chunk=None):
         ops.position_features(ws["feats"], b, h, w, y0=y0)
 
 
-def _stage_buffers(ops, opt, ws, key, b, h, w):
+def _stage_buffers(ops, opt, ws, key, b, h, w, n_sets=None, like=None):
     """The one place where the buffers of SPEC.md §13 (``key`` "sp": canonical tensor, workspace), §18 ("nd": scratch, second label
-    map, node counts) and §14 ("rt": workspace, merges, costs, alive; for K = ny * nx, or K_cap = 4096 on the nodes of §18: about
-    5 MB of workspace per image at D = 72, 0.32 GB for a batch of 64) join a workspace: at a stage's first use, or up front for a
-    graph entry. Returns them. A stage that is off leaves no key."""
+    map, node counts), §14 ("rt": workspace, merges, costs, alive; for K = ny * nx, or K_cap = 4096 on the nodes of §18: about
+    5 MB of workspace per image at D = 72, 0.32 GB for a batch of 64) and §30 ("rx": cost volume - B * k * H * W * 8 bytes, 0.63 GB
+    for 64 images of 481 x 321 at k = 8 -, stats table, beta, start map and workspace, on the device of ``like``) join a workspace:
+    at a stage's first use, or up front for a graph entry. Returns them. A stage that is off leaves no key."""
     if key not in ws:
         _, ny, nx = superpixel_grid(h, w, opt.n_superpixels) if opt.n_superpixels else (0, 0, 0)
-        if key == "sp":
+        if key == "rx":
+            torch, dev = _torch(), like.device
+            ws[key] = dict(costs=torch.empty((b, opt.k, h, w), dtype=torch.int64, device=dev),
+                           stats=torch.empty((n_sets, opt.k, 2), dtype=torch.int64, device=dev),
+                           beta=torch.empty((b,), dtype=torch.int64, device=dev),
+                           start=torch.empty((b, h, w), dtype=torch.int32, device=dev),
+                           work=torch.empty((b, h, w), dtype=torch.int32, device=dev))
+        elif key == "sp":
             ws[key] = ops.superpixel_buffers(b, h, w, opt.n_superpixels)
         elif key == "nd":
             ws[key] = ops.region_nodes_buffers(b, h, w)
@@ -1151,6 +1246,7 @@ def _stage_buffers(ops, opt, ws, key, b, h, w):
     return ws[key]
 
 
+_RELAX_OPS = ("kmeans_evaluate", "kmeans_costs", "label_relax")
 _BOUNDARY_OPS = ("region_tree_edges_buffers", "feature_gradient", "label_used", "region_adjacency", "region_tree_edges")
 
 
@@ -1214,7 +1310,9 @@ def _step_cluster(ops, opt, ws, out, b, h, w, mode, debug, dist_group=None, rows
     the int32 map of the workspace (a graph entry). With ``tree_nodes = "clusters"`` (SPEC.md §21) the Lloyd loop writes its int32
     map to the node stage's own buffer, its node map goes to the output, and the tree reads its statistics from the slab
     (``region_tree_slab``: no canonical tensor), at K_cap; ``tree`` as above. ``opt.seed`` (SPEC.md §29): without an ``init`` the
-    Lloyd loop starts from the seed launch on this slab instead of the init of SPEC.md §4."""
+    Lloyd loop starts from the seed launch on this slab instead of the init of SPEC.md §4. ``opt.relax`` (SPEC.md §30): the int32
+    k-means map is regularised in place behind the loop (``_step_relax``), in front of the node map; the entry points that
+    deliver uint8 maps straight from the loop never run with it."""
     if opt.n_superpixels == 0:
         ndws = raw = n_nodes = None
         if opt.clusters:
@@ -1232,6 +1330,8 @@ def _step_cluster(ops, opt, ws, out, b, h, w, mode, debug, dist_group=None, rows
               dist_group, rows=rows, init=init, raster=raster, debug=debug, fold=ws.get("fold"))
         if raster is None:
             ops.labels_widen(ws["labels"], b, h, w, km)
+        if opt.relax is not None:                                                     # SPEC.md §30: every later stage sees its map
+            _step_relax(ops, opt, ws, km, b, h, w, mode)
         if not opt.clusters:
             return
         ops.region_nodes(raw, opt.min_size, out32, n_nodes, scratch=ndws)
@@ -1296,8 +1396,17 @@ class Segmenter:
                  ratio=math.sqrt(2.0), bandwidth=1.0, connectivity=False, device="cuda:0", ops=None,
                  slab_candidates=1, min_region_size=0, smoothing=0.0, color_weight=0.0, chroma_gain=0,
                  position_weight=0, n_superpixels=0, spatial_weight=576, n_regions=0, tree_nodes="superpixels",
-                 merge_cost="features", init="spec", seed=0, seed_trials=4):
-        """``init = "kmeans++"`` (SPEC.md §29; needs ``n_superpixels = 0``): every Lloyd loop of the plan starts from k seeds drawn
+                 merge_cost="features", init="spec", seed=0, seed_trials=4, regularize=0.0, regularize_sweeps=4,
+                 regularize_neighbours=8):
+        """``regularize = lambda > 0`` (SPEC.md §30; needs ``n_superpixels = 0``; 0, the default: every path enqueues what it always
+        did): a Potts prior on the k-means map, minimised by ``regularize_sweeps`` (1..64) sweeps of iterated conditional modes over
+        ``regularize_neighbours`` (4 or 8) neighbours, behind the Lloyd loop (and behind ``codebook=`` / ``refine=``) and in front
+        of ``connectivity``, ``min_region_size`` and the node map of ``tree_nodes = "clusters"``. The weight of a differing
+        neighbour is beta = (round(256 lambda) * m) >> 8 with m the mean squared distance of a pixel to its centroid, so lambda
+        is in units of the map's own mean cost. Host batches take the plain path. Not with row strips, a ``dist_group``, more than
+        one rank or the texton / cue edge chains.
+
+        ``init = "kmeans++"`` (SPEC.md §29; needs ``n_superpixels = 0``): every Lloyd loop of the plan starts from k seeds drawn
         by k-means++ with ``seed_trials`` greedy trials (1..8) among a grid of at most 4096 candidate pixels of its codebook set
         (``seed_stride``), one launch in front of the passes, instead of the k evenly spaced raster pixels of SPEC.md §4
         (``"spec"``, the default: every path enqueues what it always did). The draws depend on ``seed`` (0..2^64-1) alone, not on
@@ -1355,6 +1464,11 @@ class Segmenter:
         self.init, self.seed, self.seed_trials = init, int(seed), int(seed_trials)
         if self._seeding and self.n_superpixels > 0:
             raise ValueError('init = "kmeans++" seeds the Lloyd stage: it needs n_superpixels = 0')
+        self._relax = _check_regularize(regularize, regularize_sweeps, regularize_neighbours)   # SPEC.md §30 (None: off)
+        self.regularize, self.regularize_sweeps = float(regularize), int(regularize_sweeps)
+        self.regularize_neighbours = int(regularize_neighbours)
+        if self._relax and self.n_superpixels > 0:
+            raise ValueError("regularize > 0 relaxes the k-means map: it needs n_superpixels = 0")
         if self.n_superpixels > 0 and self.bank.n_features > _SP_D_MAX:
             raise ValueError(f"n_superpixels needs a bank of at most {_SP_D_MAX} features, this one has {self.bank.n_features}")
         self._boundary = _check_merge_cost(merge_cost)                          # SPEC.md §23
@@ -1366,6 +1480,8 @@ class Segmenter:
             raise ValueError("Segmenter(n_superpixels=n, ops=...) needs ops that have the superpixel stage")
         if self._seeding and not hasattr(self.ops, "kmeans_seed"):
             raise ValueError('Segmenter(init="kmeans++", ops=...) needs ops that have kmeans_seed')
+        if self._relax and not all(hasattr(self.ops, m) for m in _RELAX_OPS):
+            raise ValueError("Segmenter(regularize=lambda, ops=...) needs ops that have kmeans_evaluate, kmeans_costs and label_relax")
         self._components = _check_tree_nodes(tree_nodes, self.n_superpixels)    # SPEC.md §18
         self._clusters = tree_nodes == "clusters"                               # SPEC.md §21 (checked: n_superpixels = 0)
         self.tree_nodes = tree_nodes
@@ -1400,7 +1516,7 @@ class Segmenter:
         self.slab_placement_ms = None
         self._opt = _StepOptions(self.k, int(n_iter), self.chroma_gain > 0, self.smoothing > 0, self.position_weight > 0,
                                  self.n_superpixels, self.spatial_weight, self.n_regions, self._components,
-                                 self.min_region_size, self._clusters, self._boundary, self._seeding)
+                                 self.min_region_size, self._clusters, self._boundary, self._seeding, self._relax)
         self._ws = {}
         self._host = {}
         self._stream = {}
@@ -1437,6 +1553,12 @@ class Segmenter:
     @n_iter.setter
     def n_iter(self, n):             # (the one option that is changed on a live plan, by tests: the step's record follows)
         self._opt = self._opt._replace(n_iter=int(n))
+
+    @property
+    def _model_opt(self):
+        """The step of the entry points that describe the k-means model (SPEC.md §28): the plan's, without the regulariser of
+        SPEC.md §30, which changes the map and not the model."""
+        return self._opt._replace(relax=None)
 
     def _device(self):
         """Launches go through ctypes on the current stream of ``self.ops.device``: the context that makes that device current
@@ -1480,6 +1602,13 @@ class Segmenter:
                     raise ValueError('init = "kmeans++" does not run over more than one rank (every rank would draw its own seeds)')
                 if imgs is not None:
                     seed_stride(imgs.shape[0], h, w)       # (ValueError: more than 4096 images in the one set)
+        if self._relax and cluster:
+            if dist_group is not None:
+                raise ValueError("regularize > 0 does not run over a dist_group")
+            if mode == "global":
+                import torch.distributed as td
+                if td.is_available() and td.is_initialized() and td.get_world_size() > 1:
+                    raise ValueError("regularize > 0 does not run over more than one rank (beta would be one rank's)")
         if self.n_superpixels > 0 and cluster:
             self._superpixel_check(h, w, mode, out_dtype, dist_group)
         if self._clusters and cluster:
@@ -1488,13 +1617,13 @@ class Segmenter:
 
     def _may_pipeline(self, mode, superpixels=False):
         """May host batches of this plan leave the plain path (``segment_device`` between two blocking copies)? Not the test
-        stand-ins, the post-passes and the collectives; SPEC.md §13 only where the caller says so (``superpixels``: a small call
+        stand-ins, the post-passes, the regulariser of SPEC.md §30 and the collectives; SPEC.md §13 only where the caller says so (``superpixels``: a small call
         replays its graph like any other, but there is no chunked upload and no three-stream pipeline for it)."""
         dist_on = False
         if mode == "global":
             import torch.distributed as td
             dist_on = td.is_available() and td.is_initialized()
-        return self.native and not self._post_passes and not dist_on \
+        return self.native and not self._post_passes and not dist_on and self._relax is None \
             and not self.debug.force_collectives and (superpixels or self.n_superpixels == 0)
 
     def _host_path(self, b, h, w, mode):
@@ -1735,13 +1864,13 @@ class Segmenter:
             labels = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
             cent = torch.empty((n_sets, self.k, self.bank.n_features), dtype=torch.int16, device=imgs.device)
             stats = torch.empty((n_sets, self.k, 2), dtype=torch.int64, device=imgs.device)
-            for g0, n, ws in self._model_steps(imgs, mode, init, self._opt, labels):
+            for g0, n, ws in self._model_steps(imgs, mode, init, self._model_opt, labels):
                 ns = n if mode == "per_image" else 1
                 cent[g0:g0 + ns].copy_(ws["cent"])
                 self.ops.kmeans_evaluate(ws["feats"], ws["cent"], n, h, w, self.k, ns, stats=stats[g0:g0 + ns])
                 for i in range(1, n_init):                 # the restarts, on the slab the first loop filled
                     again = torch.empty((ns, self.k, 2), dtype=torch.int64, device=imgs.device)
-                    opt = self._opt._replace(seed=((self.seed + i) & _U64, self.seed_trials))
+                    opt = self._model_opt._replace(seed=((self.seed + i) & _U64, self.seed_trials))
                     _step_cluster(self.ops, opt, ws, labels[g0:g0 + n], n, h, w, mode, self.debug)
                     self.ops.kmeans_evaluate(ws["feats"], ws["cent"], n, h, w, self.k, ns, stats=again)
                     better = again[:, :, 1].sum(dim=1) < stats[g0:g0 + ns, :, 1].sum(dim=1)      # strictly: ties keep the earlier
@@ -1804,7 +1933,7 @@ class Segmenter:
             if stats:
                 res["stats"] = torch.zeros((n_sets, self.k, 2), dtype=torch.int64, device=imgs.device)
             own = new(torch.int32) if model is None else None
-            for g0, n, ws in self._model_steps(imgs, mode, None, self._opt if model is None else None, own):
+            for g0, n, ws in self._model_steps(imgs, mode, None, self._model_opt if model is None else None, own):
                 if model is None:
                     cent, ns = ws["cent"], n if mode == "per_image" else 1
                 else:
@@ -1823,6 +1952,71 @@ class Segmenter:
         pixel on its centroid. ``model``, ``mode``: as in ``evaluate_device``."""
         res = self.evaluate_device(imgs, model, mode, labels=True, best=True, second=True, stats=False)
         return res["labels"], confidence_of(res["best"], res["second"])
+
+    # ---- the regulariser (SPEC.md §30)
+    def kmeans_costs_device(self, imgs, model=None, mode="per_image"):
+        """(B,H,W,3) uint8 device tensor -> (costs (B,k,H,W) int64, labels (B,H,W) int32, stats (n_sets,k,2) int64): the cost
+        volume of SPEC.md §30 - the squared distance of every pixel to every centroid - under ``model``'s codebooks as they are or,
+        without one, under the centroids the plan's own Lloyd loop ends on in ``mode``, with the labels and the table of SPEC.md
+        §28 (``labels`` is the argmin of ``costs`` over j, ties to the lowest j). Ignores the plan's ``regularize``."""
+        torch = _torch()
+        imgs, model, _ = self._model_args(imgs, mode, model)
+        if not hasattr(self.ops, "kmeans_costs"):
+            raise ValueError("the cost volume needs ops that have kmeans_costs")
+        b, h, w, _ = imgs.shape
+        n_sets = model.n_sets if model is not None else (b if mode == "per_image" else 1)
+        plain = self._model_opt._replace(clusters=False, n_regions=0)    # (the loop alone: no node map, no tree)
+        with self._device():
+            costs = torch.empty((b, self.k, h, w), dtype=torch.int64, device=imgs.device)
+            labels = torch.empty((b, h, w), dtype=torch.int32, device=imgs.device)
+            stats = torch.zeros((n_sets, self.k, 2), dtype=torch.int64, device=imgs.device)
+            own = torch.empty_like(labels) if model is None else None
+            for g0, n, ws in self._model_steps(imgs, mode, None, plain if model is None else None, own):
+                if model is None:
+                    cent, ns = ws["cent"], n if mode == "per_image" else 1
+                else:
+                    ns = 1 if n_sets == 1 else n
+                    cent = model.centroids.view(torch.int16)[0 if n_sets == 1 else g0:][:ns]
+                part = torch.empty((ns, self.k, 2), dtype=torch.int64, device=imgs.device)
+                self.ops.kmeans_evaluate(ws["feats"], cent, n, h, w, self.k, ns, labels=labels[g0:g0 + n], stats=part)
+                self.ops.kmeans_costs(ws["feats"], cent, n, h, w, self.k, ns, costs[g0:g0 + n])
+                stats[0 if n_sets == 1 else g0:][:ns] += part    # (one codebook over several groups: the groups' tables add up)
+        return costs, labels, stats
+
+    def relax_labels_device(self, costs, labels, beta, sweeps=4, neighbours=8):
+        """SPEC.md §30 on any cost volume: ``costs`` (B,k,H,W) int64 in 0 .. 2^62 - 1, ``labels`` (B,H,W) int32 (a value outside
+        0..k-1 is "no label"), ``beta`` an integer or a (B,) int64 tensor -> (labels (B,H,W) int32 after ``sweeps`` (0..64) sweeps
+        over ``neighbours`` (4 or 8), changed (B, sweeps) int32, energy (B, 2) int64 = (unary, pairs) of the delivered map). The
+        inputs are not changed. Ignores the plan's options: k is the volume's."""
+        torch = _torch()
+        if not hasattr(self.ops, "label_relax"):
+            raise ValueError("relax_labels_device needs ops that have label_relax")
+        s, n = _as_int(sweeps), _as_int(neighbours)
+        if s is None or not 0 <= s <= 64:
+            raise ValueError(f"sweeps must be an integer in 0..64, got {sweeps!r}")
+        if n not in (4, 8):
+            raise ValueError(f"neighbours must be 4 or 8, got {neighbours!r}")
+        if costs.dtype != torch.int64 or costs.ndim != 4 or not 1 <= costs.shape[1] <= _lib.K_MAX:
+            raise ValueError("costs must be a (B,k,H,W) int64 tensor with k in 1..16")
+        b, k, h, w = costs.shape
+        if labels.dtype != torch.int32 or tuple(labels.shape) != (b, h, w) or labels.device != costs.device:
+            raise ValueError("labels must be a (B,H,W) int32 tensor on the device of costs")
+        if not (1 <= b <= 65535 and 1 <= h <= 4096 and 1 <= w <= 4096):
+            raise ValueError("relax_labels_device takes 1..65535 images of 1..4096 rows and columns")
+        if not isinstance(beta, torch.Tensor):
+            if _as_int(beta) is None:
+                raise ValueError(f"beta must be an integer or a (B,) int64 tensor, got {beta!r}")
+            beta = torch.full((b,), _as_int(beta), dtype=torch.int64, device=costs.device)
+        elif beta.dtype != torch.int64 or tuple(beta.shape) != (b,) or beta.device != costs.device:
+            raise ValueError("beta must be an integer or a (B,) int64 tensor on the device of costs")
+        with self._device():
+            out = torch.empty((b, h, w), dtype=torch.int32, device=costs.device)
+            changed = torch.empty((b, s), dtype=torch.int32, device=costs.device)
+            energy = torch.empty((b, 2), dtype=torch.int64, device=costs.device)
+            work = torch.empty((b, h, w), dtype=torch.int32, device=costs.device)
+            self.ops.label_relax(costs.contiguous(), beta.contiguous(), b, h, w, k, n, s, labels.contiguous(), out, workspace=work,
+                                 changed=changed, energy=energy)
+        return out, changed, energy
 
     def _superpixel_check(self, h, w, mode="per_image", out_dtype=None, dist_group=None):
         """The argument rules of SPEC.md §13 for one image shape (``h`` None: only those that need no shape), before anything is
@@ -2127,6 +2321,8 @@ class Segmenter:
 
     def _check_strips(self):
         """The options the two row-strip entry points refuse."""
+        if self._relax:
+            raise ValueError("regularize > 0 is not supported on row strips (a strip would need a halo of 4 rows per sweep)")
         if self._seeding:
             raise ValueError('init = "kmeans++" is not supported on row strips (the candidates would be one strip\'s)')
         if self.n_superpixels > 0:
@@ -2349,8 +2545,8 @@ class Segmenter:
                 raise ValueError(f"the {what} edge map needs ops that have it")
 
     def _need_plain_map(self, who):
-        if self.n_superpixels > 0 or self._clusters or self._post_passes:
-            raise ValueError(f"{who} needs the plain k-means map (no n_superpixels, tree_nodes or post-pass)")
+        if self.n_superpixels > 0 or self._clusters or self._post_passes or self._relax:
+            raise ValueError(f"{who} needs the plain k-means map (no n_superpixels, tree_nodes, post-pass or regularize)")
 
     def _edges_chain(self, what, imgs, mode, joined, cluster, launch, thin=0):
         """The chain behind ``texton_edges_device`` and ``cue_edges_device`` on one feature slab, once the caller has checked its
